@@ -12,9 +12,15 @@ per CU, so that no two workgroups running at the same time read the same bytes) 
 device and the batch of 1000 cycles through it; every batch entry still gets its own histogram and
 image.  Generation is outside the timed region.
 
-Side legs at N=1, each in the same JSON line and none of them `value`: `config4` (BASELINE.json
-configs[3]: k=9 cgr, 100 samples, both base distributions -- the LDS-spill path), `cpu_baseline`,
-`end_to_end` (files on disk -> PNG files).
+A plain run sets up, warms up, times `--steps` steps and prints the line; nothing else.  The side
+legs run only with `--full`, each in the same JSON line and none of them `value`.  At N=1: `config4`
+(BASELINE.json configs[3]: k=9 cgr, 100 samples, both base distributions -- the LDS-spill path),
+`cpu_baseline` (which also checks the first batch entries against the oracle), `realistic`, `ladder`,
+`query`, `end_to_end` (files on disk -> PNG files) and the live rocprofv3 traffic passes; at N>1:
+`end_to_end` and `ladder_shard`.
+
+`--dump-outputs DIR` writes what the last timed step computed (images, histograms, status words) as
+.npy files in DIR, for comparing two builds output for output: see dump_outputs().
 
 N>1 = BASELINE.json configs[2]: 10000 samples sharded over the N GPUs (ceil(10000/N) per rank per
 step, no data-path collective: samples are independent, as in the reference's sample-level pool,
@@ -84,7 +90,16 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="process-group backend for N>1 (nccl = RCCL); "
                     "gloo allows a 2-rank rehearsal on a single GPU together with --all-on-device0")
     ap.add_argument("--all-on-device0", action="store_true", help="rehearsal only: every rank uses cuda:0")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the side legs (CPU baseline and oracle check, config4, "
+                    "realistic, ladder, query, end_to_end, live traffic; ladder_shard at N>1); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all; rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def cpu_budget():
@@ -921,6 +936,30 @@ def spawn_ranks(args):
     return rc
 
 
+DUMP_BYTES = 60_000_000    # the .npy files' data, under the 64 MB the contract allows (headers are a few hundred bytes)
+
+
+def dump_outputs(path, hist, img, status):
+    """What the caller of the timed path receives from its last step, as .npy files in `path`:
+    images.npy (float32 [rows, side, side], the uint8 pixels), histograms.npy (float64 [rows, 4^k], the
+    u32 counts -- exact in float64), status.npy (float64 [samples], every batch entry's framing status word)
+    and rows.npy (float64: the batch entries `rows` stands for).  Where every entry's image and histogram
+    would not fit DUMP_BYTES, `rows` is a seeded sample of the batch (rng seed 0, sorted), so that the
+    same arguments give the same rows."""
+    import torch
+    samples = int(hist.shape[0])
+    per_row = img[0].numel() * 4 + hist[0].numel() * 8
+    nrows = max(1, min(samples, (DUMP_BYTES - samples * 16) // per_row))     # (status.npy and rows.npy: 8 bytes a sample each)
+    rows = np.arange(samples) if nrows == samples else \
+        np.sort(np.random.default_rng(0).choice(samples, nrows, replace=False))
+    sel = torch.from_numpy(rows).to(hist.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "images.npy"), img.index_select(0, sel).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "histograms.npy"), hist.index_select(0, sel).cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1004,13 +1043,15 @@ def main():
         elapsed = float(t.item())
 
     bad = int((status != 0).sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hist, img, status)
     e2e_ranks = None
-    if world > 1 and not args.no_e2e:   # (every rank takes part: it is a node-level measurement)
+    if world > 1 and args.full and not args.no_e2e:   # (every rank takes part: it is a node-level measurement)
         hist = img = None
         torch.cuda.empty_cache()
         e2e_ranks = end_to_end_ranks(eng, args, rank, world, dist, red_dev)
     lshard = None
-    if world > 1 and args.ladder_shard_samples > 0 and args.k <= 7:   # (every rank takes part)
+    if world > 1 and args.full and args.ladder_shard_samples > 0 and args.k <= 7:   # (every rank takes part)
         hist = img = None
         torch.cuda.empty_cache()
         lshard = ladder_shard(eng, args, rank, world, dist, red_dev)
@@ -1082,12 +1123,12 @@ def main():
             out["end_to_end"] = e2e_ranks
         if lshard is not None:
             out["ladder_shard"] = lshard
-        if world == 1 and not args.no_config4 and args.k <= 7:
+        if world == 1 and args.full and not args.no_config4 and args.k <= 7:
             try:
                 out["config4"] = config4(args, local_rank)
             except Exception as e:  # a side measurement: never lose the bench line over it
                 out["config4"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 # (hist / img: as the last timed step left them; batch entry i = pool sample i for i < pool)
                 out["cpu_baseline"] = cpu_baseline(eng, fastq, poffs, plens, args, args.cpu_seconds, hist, img)
@@ -1101,17 +1142,17 @@ def main():
                 out["cpu_baseline"] = {"error": repr(e)}
         hist = img = fastq = None    # make room: the legs below allocate their own batches
         torch.cuda.empty_cache()
-        if world == 1 and not args.no_realistic and args.k <= 7:
+        if world == 1 and args.full and not args.no_realistic and args.k <= 7:
             try:
                 out["realistic"] = realistic(args, local_rank)
             except Exception as e:  # a side measurement: never lose the bench line over it
                 out["realistic"] = {"error": repr(e)}
-        if world == 1 and not args.no_ladder and args.k <= 7:
+        if world == 1 and args.full and not args.no_ladder and args.k <= 7:
             try:
                 out["ladder"] = ladder(args, local_rank)
             except Exception as e:  # a side measurement: never lose the bench line over it
                 out["ladder"] = {"error": repr(e)}
-        if world == 1 and not args.no_query and args.k <= 7:
+        if world == 1 and args.full and not args.no_query and args.k <= 7:
             try:
                 out["query"] = query_leg(args, local_rank)
             except VerifyError as e:
@@ -1120,14 +1161,14 @@ def main():
                 bad = max(bad, 1)
             except Exception as e:  # a side measurement: never lose the bench line over it
                 out["query"] = {"error": repr(e)}
-        if world == 1 and not args.no_e2e:
+        if world == 1 and args.full and not args.no_e2e:
             try:
                 out["end_to_end"] = end_to_end(eng, args)
             except Exception as e:  # a side measurement: never lose the bench line over it
                 out["end_to_end"] = {"error": repr(e)}
         under_profiler = any("rocprof" in os.environ.get(v, "").lower() for v in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES")) or \
             any(v.startswith(("ROCPROF", "ROCPROFILER")) for v in os.environ)
-        if world == 1 and not args.no_live_traffic and not under_profiler:
+        if world == 1 and args.full and not args.no_live_traffic and not under_profiler:
             # roofline.traffic measured in THIS run: the sample pools of every leg above are freed by now, and so is this
             # process's engine (its workspaces would sit beside the children's on the card)
             eng.close()

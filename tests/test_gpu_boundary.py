@@ -256,13 +256,13 @@ def test_abi_argument_errors(engines):
 
 
 def test_bench_script_runs_end_to_end(tmp_path):
-    """bench.py with a tiny workload: the JSON contract fields are all there."""
+    """bench.py --full with a tiny workload: the JSON contract fields and every side leg are all there."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--samples", "16", "--pool", "8", "--reads", "20000", "--cpu-seconds", "0.5", "--e2e-files", "6",
                           "--e2e-reads", "5000", "--config4-samples", "6", "--config4-steps", "2", "--realistic-pool", "8", "--realistic-steps", "2", "--ladder-samples", "3",
                           "--query-samples", "12", "--query-batch", "8", "--query-steps", "2"],
@@ -320,7 +320,7 @@ def test_bench_script_runs_end_to_end(tmp_path):
 
 
 def test_bench_gpus_flag_starts_the_ranks_itself():
-    """`bench.py --gpus 2` with no launcher: the script starts its two ranks (both on cuda:0 here,
+    """`bench.py --gpus 2 --full` with no launcher: the script starts its two ranks (both on cuda:0 here,
     gloo for the control plane) and the line it prints says so; each rank runs half of the batch."""
     import json
     import os
@@ -328,7 +328,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--all-on-device0",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--all-on-device0", "--full",
                           "--backend", "gloo", "--steps", "2", "--warmup", "1", "--total-samples", "24", "--pool", "6",
                           "--reads", "20000", "--e2e-files-per-rank", "3", "--e2e-reads", "5000", "--ladder-shard-samples", "2"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)
@@ -352,6 +352,51 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1"],
                          capture_output=True, text=True, timeout=300, cwd=root, env=dict(env, WORLD_SIZE="1", RANK="0"))
     assert bad.returncode == 2 and "WORLD_SIZE" in bad.stderr
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path, engines):
+    """A plain bench.py run: `--steps` timed steps and no side leg in the line; `--dump-outputs` writes the last
+    timed step's images and histograms -- the same for the same arguments, whatever the number of steps, and the
+    oracle's for every batch entry."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    k, mapping, pool, samples, reads = 7, "varKode", 4, 12, 20000
+    common = ["--samples", str(samples), "--pool", str(pool), "--reads", str(reads), "--warmup", "1"]
+    dumps = {}
+    for steps in (3, 1):
+        d = tmp_path / ("steps%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--dump-outputs", str(d)] + common,
+                             capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["bad_status_samples"] == 0
+        assert line["unit"] == "Gbases/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+        assert len(line["roofline"]["count_ms_by_step"]) == steps
+        for leg in ("cpu_baseline", "verified_samples", "config4", "realistic", "ladder", "query", "end_to_end", "live_traffic_seconds"):
+            assert leg not in line, leg
+        files = sorted(os.listdir(d))
+        assert files == ["histograms.npy", "images.npy", "rows.npy", "status.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64_000_000
+        dumps[steps] = {f[:-4]: np.load(d / f) for f in files}
+    a, b = dumps[3], dumps[1]
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    n = side(k, mapping)
+    assert list(a["rows"]) == list(range(samples)) and not a["status"].any()
+    assert a["images"].shape == (samples, n, n) and a["histograms"].shape == (samples, 4 ** k)
+    # batch entry i is pool sample i % pool, generated on the device from the same seed as the bench's
+    fastq, offs, lens = engines(k, mapping).synth(0, pool, reads, 150)
+    lut = pixel_lut(k, mapping)
+    for s in range(pool):
+        buf = fastq[int(offs[s]):int(offs[s]) + int(lens[s])].cpu().numpy()
+        want_h, _, st = oracle.count_fastq(buf, k)
+        want_i, _, _ = oracle.fastq_to_image(buf, k, lut, n * n)
+        assert st == 0
+        for r in range(s, samples, pool):
+            assert np.array_equal(a["histograms"][r], want_h) and np.array_equal(a["images"][r].ravel(), want_i), r
 
 
 def test_c_abi_from_plain_c(tmp_path):
