@@ -221,6 +221,44 @@ int vk_upload_mapped(vk_ctx* ctx, void* d_dst, const uint64_t* dst_offsets, cons
 int vk_host_register(vk_ctx* ctx, const void* p, uint64_t nbytes);
 int vk_host_unregister(vk_ctx* ctx, const void* p);
 
+/* Step B: replaces clean_reads (commands/image.py:317-575: concatenate_reads, then fastp with --dedup,
+ * --trim_front1/--trim_tail1, --trim_poly_g, --detect_adapter_for_pe, --merge --include_unmerged, no quality or
+ * length filter) for a batch of samples whose raw FASTQ files are resident in HBM.  The rules are this project's
+ * restatement of those options ("Step B", and tests/clean_ref.py), not fastp bit for bit.
+ *
+ * vk_clean_lines_device: lines[i] (host) = the '\n' bytes of file i, d_text[offsets[i] .. +lengths[i]) -- `wc -l`
+ * of count_total_reads (:117-160), whose // 4 is the file's read count.  Synchronises.
+ *
+ * vk_clean_device: file i belongs to sample samples[i] as roles[i] (VK_CL_ROLE_*) and gives its first records[i]
+ * records (the read budget of calculate_reads_needed, :164-221; the caller computes it).  A sample's R1 records,
+ * in the order its R1 files are listed, pair up with its R2 records in the order of its R2 files.  flags:
+ * VK_CL_* options.  d_ws: caller-allocated device workspace of vk_clean_workspace_size bytes (same lengths /
+ * records).  Output: sample s's cleaned FASTQ text goes to d_out + out_offsets[s] (host array, 16-byte aligned;
+ * the region must hold the sum of the sample's file lengths rounded up to 16, and d_out is out_bytes long), its
+ * length to d_out_lengths[s] (the bytes up to the 16-byte rounded end are zeroed), its stats to
+ * d_stats[s][VK_CL_NSTAT] (u64: output sequence bases, output records, then for cycles c = 0..39 of the first
+ * group's output reads the counts of A C G T at [2 + 4c + 0..3] and the reads that reach c at [162 + c]) and its
+ * VK_CL_* status bits to d_status[s] (a sample with a non-zero status gets no text).  No allocation, no
+ * synchronisation: everything is enqueued on the context's stream. */
+#define VK_CL_ROLE_UNPAIRED 0u
+#define VK_CL_ROLE_R1 1u
+#define VK_CL_ROLE_R2 2u
+#define VK_CL_ADAPTER 1u       /* adapter trimming by pair overlap (not -a) */
+#define VK_CL_MERGE 2u         /* merge overlapping pairs, keep the others (not -r) */
+#define VK_CL_DEDUP 4u         /* drop exact duplicate reads / pairs (not -D) */
+#define VK_CL_BAD_FRAMING 1u   /* a budgeted record lacks lines, its header is not '@', its third line not '+', or quality and sequence lengths differ */
+#define VK_CL_RAGGED 2u        /* the sample's R1 files and R2 files give different numbers of records */
+#define VK_CL_NSTAT 202
+int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                          uint32_t nfiles, uint64_t* lines);
+int vk_clean_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
+                            uint64_t* bytes);
+int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                    const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                    uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
+                    uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
+                    uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -1,13 +1,16 @@
 """`python -m varkoder_amd image ...`: steps D+E of `varKoder image` on the GPU
 (`python -m varkoder_amd convert ...`: `varKoder convert`, see convert.convert_folder).
 
-Same flags as the reference's `image` sub-command (varKoder/cli.py:69-166).  Steps B/C of
-the reference (fastp cleaning, reformat.sh subsampling) are external CPU tools outside this
-path: run the reference once with `-X/--no-image -i INT` (clean + split only, cli.py:155-160)
-and point this command at INT (or at its `split_fastqs/` folder).  Every file
-`<sample>@<bp>K.fq[.gz]` becomes `<outdir>/<sample>@<bp>K+<mapping>+k<k>.png` with the
-reference's metadata; `stats.csv` (and `labels.csv` with -t) are written like
-process_stats does (commands/image.py:1144-1185).  With torchrun, ranks shard the files.
+Same flags as the reference's `image` sub-command (varKoder/cli.py:69-166).  By default the input is the
+intermediate folder of a reference run with `-X/--no-image -i INT` (clean + split only, cli.py:155-160), or its
+`split_fastqs/` folder: every file `<sample>@<bp>K.fq[.gz]` becomes `<outdir>/<sample>@<bp>K+<mapping>+k<k>.png`
+with the reference's metadata.  `--from-clean` enters at step C (cleaned, unsplit reads: the subsample ladder is
+drawn on the GPU).  `--from-raw` enters at step B like the reference's own `varKoder image <folder of raw reads>`:
+the input is a folder `<taxon>/<sample>/<reads>.fq[.gz]` or a CSV `labels,sample,files`, the reads are cleaned on
+the GPU (rules: INTEGRATION.md, "Step B"; -a/-D/-r/-T take effect, -M sets the read budget) and go on to the ladder
+without leaving the device; with `-i INT` the cleaned reads and their base-content report are also written to
+`INT/clean_reads/` (and reused there by a later run unless -x).  `stats.csv` (and `labels.csv` with -t) are written
+like process_stats does (commands/image.py:1144-1185).  With torchrun, ranks shard the files (samples).
 """
 import argparse
 import math
@@ -40,20 +43,29 @@ def setup_parser():
     p.add_argument("-c", "--cpus-per-thread", type=int, default=1, help="accepted for parity, unused")
     p.add_argument("-o", "--outdir", default="images", help="path to folder where to write final images.")
     p.add_argument("-f", "--stats-file", default="stats.csv", help="path to file where sample statistics will be saved.")
-    p.add_argument("-i", "--int-folder", help="accepted for parity (the input IS the intermediate folder)")
-    p.add_argument("-m", "--min-bp", type=str, default="500K", help="applied upstream by the split step; accepted for parity")
-    p.add_argument("-M", "--max-bp", default="200M", help="applied upstream by the split step; accepted for parity")
+    p.add_argument("-i", "--int-folder", help="with --from-raw: folder for the cleaned reads (clean_reads/); "
+                                              "otherwise accepted for parity (the input IS the intermediate folder)")
+    p.add_argument("-m", "--min-bp", type=str, default="500K",
+                   help="with --from-raw / --from-clean: smallest subsample; otherwise applied upstream by the split step")
+    p.add_argument("-M", "--max-bp", default="200M",
+                   help="with --from-raw / --from-clean: largest subsample (and, --from-raw, 5x of it the read budget); "
+                        "otherwise applied upstream by the split step")
     p.add_argument("-t", "--label-table", action="store_true", help="also write labels.csv")
-    p.add_argument("-a", "--no-adapter", action="store_true", help="upstream (fastp) option; accepted for parity")
-    p.add_argument("-D", "--no-deduplicate", action="store_true", help="upstream (fastp) option; accepted for parity")
-    p.add_argument("-r", "--no-merge", action="store_true", help="upstream (fastp) option; accepted for parity")
+    p.add_argument("-a", "--no-adapter", action="store_true", help="with --from-raw: no adapter trimming; otherwise accepted for parity")
+    p.add_argument("-D", "--no-deduplicate", action="store_true", help="with --from-raw: no deduplication; otherwise accepted for parity")
+    p.add_argument("-r", "--no-merge", action="store_true", help="with --from-raw: no merging of read pairs; otherwise accepted for parity")
     p.add_argument("-X", "--no-image", action="store_true", help="nothing to do here without images")
-    p.add_argument("-T", "--trim-bp", default="10,10", help="upstream (fastp) option; accepted for parity")
+    p.add_argument("-T", "--trim-bp", default="10,10",
+                   help="with --from-raw: bases trimmed from the front and the tail of every read; otherwise accepted for parity")
     p.add_argument("--labels-csv", help="optional CSV `sample,labels` (labels separated by ';')")
-    p.add_argument("--from-clean", action="store_true",
-                   help="input holds cleaned but UNSPLIT reads (`<int>/clean_reads/<sample>.fq.gz`): draw the "
-                        "1-2-5 ladder of subsamples between --min-bp and --max-bp on the GPU (stands in for "
-                        "reformat.sh; statistically equivalent, not the same random reads)")
+    entry = p.add_mutually_exclusive_group()
+    entry.add_argument("--from-clean", action="store_true",
+                       help="input holds cleaned but UNSPLIT reads (`<int>/clean_reads/<sample>.fq.gz`): draw the "
+                            "1-2-5 ladder of subsamples between --min-bp and --max-bp on the GPU (stands in for "
+                            "reformat.sh; statistically equivalent, not the same random reads)")
+    entry.add_argument("--from-raw", action="store_true",
+                       help="input holds RAW reads (`<taxon>/<sample>/*.fq[.gz]` or a CSV labels,sample,files): clean them "
+                            "on the GPU (step B, the reference's fastp pass) and go on with the ladder")
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query cleaned reads or images against a trained network (cli.py:327-446).")
     q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads) or, with "
@@ -309,6 +321,61 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
     finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, base_sd)
 
 
+def run_image_from_raw(args, outdir, rank, world, local_rank):
+    """`image --from-raw`: steps B-E per sample (run_clean2img, commands/image.py:938-1127) with step B on the GPU."""
+    import numpy as np
+    from .image import base_sd_table
+    from .pipeline import clean_to_images, raw_to_images
+    from .rawinput import process_input
+    from .shard import agreed_weights, io_threads_per_rank
+    table = process_input(args.input)
+    if not table:
+        raise Exception("No files found in input. Please check.")
+    samples = [s for s, _, _ in table]
+    labels = {s: lab for s, lab, _ in table}
+    max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)     # cli.py:496-501
+    front, tail = (int(x) for x in str(args.trim_bp).split(","))
+    rng = np.random.default_rng(args.seed)
+    # image.py:1017: str(row index) + str(random integer), one draw per sample in row order
+    seeds = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(samples)}
+    clean_dir = Path(args.int_folder) / "clean_reads" if args.int_folder else None
+    # a cleaned file from an earlier run is used as it is (clean_reads, commands/image.py:350-352)
+    reuse = {s for s in samples if clean_dir is not None and not args.overwrite and (clean_dir / (s + ".fq.gz")).is_file()}
+    for s in sorted(reuse):
+        eprint("Skipping cleaning for", s + ":", "File exists.")
+    raw = [(s, files) for s, _, files in table if s not in reuse]
+    done_clean = [clean_dir / (s + ".fq.gz") for s in samples if s in reuse]
+    eprint("Cleaning reads, subsampling, counting kmers and creating images for", len(samples), "samples")
+    per_sample, base_sd, error = OrderedDict(), {}, None
+    # (collectives: before the try block, while every rank is still here)
+    every = [f for _, files in raw for f in files]
+    fw = agreed_weights(every) if every else []
+    weights, at = [], 0
+    for _, files in raw:
+        weights.append(sum(fw[at:at + len(files)]))
+        at += len(files)
+    cw = agreed_weights(done_clean) if done_clean else []
+    try:   # (a rank whose share fails still reaches the gather below: see finish_image_job)
+        failpoint(rank)
+        common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
+                      seeds=seeds, labels=labels, device=local_rank, rank=rank, world=world,
+                      io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
+        if raw:
+            got, sds = raw_to_images(raw, outdir, weights=weights, trim=(front, tail), adapter=not args.no_adapter,
+                                     merge=not args.no_merge, dedup=not args.no_deduplicate, clean_dir=clean_dir, **common)
+            per_sample.update(got)
+            base_sd.update(sds)
+        if done_clean:
+            sds = base_sd_table(clean_dir, sorted(reuse))
+            base_sd.update(sds)
+            per_sample.update(clean_to_images(done_clean, outdir, weights=cw, base_sd=sds, **common))
+        for s, v in per_sample.items():
+            v["base_frequencies_sd"] = base_sd.get(s, 0)
+    except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
+        error = e
+    finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, base_sd)
+
+
 def failpoint(rank):
     """Test hook: VARKODER_AMD_FAULT=rank<r> makes rank r's share of an `image` job raise before it starts (the tests of
     the job's failure isolation need a rank that fails for a reason no input file carries: a device out of memory, a
@@ -336,9 +403,11 @@ def finish_image_job(args, outdir, rank, world, per_sample, error, samples, labe
             rows = [OrderedDict([("sample", s)] + list(v.items())) for s, v in merged.items()]
             pd.DataFrame(rows).to_csv(args.stats_file, index=False)
             if args.label_table and not errors:                               # image.py:1172-1185
+                # (a sample of another rank whose figure only travelled with the stats: --from-raw computes it there)
+                sd = {s: base_sd.get(s, merged.get(s, {}).get("base_frequencies_sd", 0)) for s in samples}
                 lt = pd.DataFrame({"sample": samples,
                                    "labels": [LABELS_SEP.join(labels.get(s, [])) for s in samples],
-                                   "possible_low_quality": [base_sd.get(s, 0) > QUAL_THRESH for s in samples]})
+                                   "possible_low_quality": [sd[s] > QUAL_THRESH for s in samples]})
                 lt.to_csv(outdir / "labels.csv", index=False)
             if errors:
                 eprint("image failed on", "; ".join(errors))
@@ -387,6 +456,8 @@ def run_image(args):
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
     if args.from_clean:
         return run_image_from_clean(args, outdir, rank, world, local_rank)
+    if args.from_raw:
+        return run_image_from_raw(args, outdir, rank, world, local_rank)
     src = Path(args.input)
     if (src / "split_fastqs").is_dir():
         src = src / "split_fastqs"

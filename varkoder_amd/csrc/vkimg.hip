@@ -28,6 +28,7 @@
 //   vk_remap_kernel / vk_preprocess_kernel: `convert`'s remap and the input side of `query`.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +47,7 @@
 #include "vk_image.h"
 #include "vk_inflate.h"
 #include "vk_aux.h"
+#include "vk_clean.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -121,6 +123,9 @@ struct vk_ctx {
     bool spill_packed = false;     // VKIMG_SPILL_PACKED=1: k = 8, 9 pass A in two kernels, vk_pack_kernel + the partition of the packed stream (measured slower than the one kernel that classifies every byte: 21.1 against 16.3 ms per 100 samples; tests, A/B timing)
     bool spill_pairs = false;      // VKIMG_SPILL_PAIRS=1: a plain k = 8, 9 count through the pair route of rounds 1-4 (u16 per two windows, wave-private queues; what subsampled and packed launches still use) instead of the quad route (tests, A/B timing)
     bool spill_force_wide = false; // VKIMG_SPILL_FORCE_WIDE=1: every k = 8, 9 replay job through the u32 window counters (tests)
+    uint8_t* d_clines = nullptr;   // vk_clean_lines_device: files | chunk bases | line counters
+    size_t clines_cap = 0;
+    uint32_t clean_hash_bits = 64; // VKIMG_CLEAN_HASH_BITS=n: vk_clean_device's dedup keeps n bits of its 64-bit hash (tests: collisions on purpose)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -540,6 +545,11 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
         ctx->spill_pairs = sq && sq[0] == '1';
         const char* fw = getenv("VKIMG_SPILL_FORCE_WIDE");
         ctx->spill_force_wide = fw && fw[0] == '1';
+        const char* hb = getenv("VKIMG_CLEAN_HASH_BITS");
+        if (hb && hb[0]) {
+            const unsigned long v = strtoul(hb, nullptr, 10);
+            ctx->clean_hash_bits = v >= 1 && v <= 64 ? static_cast<uint32_t>(v) : 64u;
+        }
         const char* kc = getenv("VKIMG_K1_CLASSIC");
         ctx->k1_classic = kc && kc[0] == '1';
     }
@@ -564,7 +574,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -1585,6 +1595,213 @@ int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uin
     if (grid) *grid = ctx->last_grid;
     if (block) *block = ctx->last_block;
     if (lds_bytes) *lds_bytes = ctx->last_lds;
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------- step B ---------
+
+namespace {
+
+size_t cl_align(size_t x) { return (x + 255) / 256 * 256; }
+
+// byte offsets of the pieces of a vk_clean_device workspace
+struct ClLayout {
+    size_t files, fchunk, samples, unit_base, ccount, cprefix, sums, recs, hashes, slot_of, plans, obytes, oprefix, table, total;
+    uint64_t nchunks, nrec, nslots;
+};
+
+ClLayout cl_layout(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
+    ClLayout L{};
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        L.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        L.nrec += records[i];
+    }
+    L.nslots = 1024;
+    while (L.nslots < 2 * L.nrec) L.nslots <<= 1;
+    const uint64_t nb = std::max((L.nchunks + kClScanBlock - 1) / kClScanBlock, (L.nrec + kClScanBlock - 1) / kClScanBlock);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += cl_align(bytes); return o; };
+    L.files = take(nfiles * sizeof(ClFile));
+    L.fchunk = take(nfiles * 8ull);
+    L.samples = take(nsamples * sizeof(ClSample));
+    L.unit_base = take((nsamples + 1ull) * 8);
+    L.ccount = take(L.nchunks * 8);
+    L.cprefix = take((L.nchunks + 1) * 8);
+    L.sums = take((nb + 1) * 8);
+    L.recs = take(L.nrec * sizeof(ClRec));
+    L.hashes = take(L.nrec * 8);
+    L.slot_of = take(L.nrec * 4);
+    L.plans = take(L.nrec * sizeof(ClPlan));
+    L.obytes = take(L.nrec * 8);
+    L.oprefix = take((L.nrec + 1) * 8);
+    L.table = take(L.nslots * 8);
+    L.total = at;
+    return L;
+}
+
+int cl_scan(vk_ctx* ctx, const uint64_t* in, uint64_t n, uint64_t* sums, uint64_t* out) {
+    VK_HIP(ctx, hipMemsetAsync(out, 0, sizeof(uint64_t), ctx->stream));   // (n = 0: out[0] = 0)
+    if (n == 0) return VK_OK;
+    const uint64_t nb = (n + kClScanBlock - 1) / kClScanBlock;
+    hipLaunchKernelGGL(vk_cl_scan_reduce_kernel, dim3(nb), dim3(kClThreads), 0, ctx->stream, in, n, sums);
+    hipLaunchKernelGGL(vk_cl_scan_top_kernel, dim3(1), dim3(kClThreads), 0, ctx->stream, sums, nb);
+    hipLaunchKernelGGL(vk_cl_scan_apply_kernel, dim3(nb), dim3(kClThreads), 0, ctx->stream, in, n, sums, out);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                          uint32_t nfiles, uint64_t* lines) {
+    if (!ctx || !offsets || !lengths || !lines || (nfiles && !d_text)) return VK_EINVAL;
+    if (nfiles == 0) return VK_OK;
+    std::vector<ClFile> files(nfiles);
+    std::vector<uint64_t> fchunk(nfiles);
+    uint64_t nchunks = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        if (offsets[i] % 16) return VK_EINVAL;
+        files[i] = ClFile{offsets[i], lengths[i], 0, 0, nchunks};
+        fchunk[i] = nchunks;
+        nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+    }
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t o_chunk = cl_align(nfiles * sizeof(ClFile)), o_lines = o_chunk + cl_align(nfiles * 8ull);
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, o_lines + nfiles * 8ull);
+    if (rc) return rc;
+    uint8_t* m = ctx->d_clines;
+    VK_HIP(ctx, hipMemcpyAsync(m, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(m + o_chunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(m + o_lines, 0, nfiles * 8ull, ctx->stream));
+    if (nchunks)
+        hipLaunchKernelGGL(vk_cl_lines_kernel, dim3(nchunks), dim3(kClThreads), 0, ctx->stream, static_cast<const uint8_t*>(d_text),
+                           reinterpret_cast<const ClFile*>(m), reinterpret_cast<const uint64_t*>(m + o_chunk), nfiles,
+                           reinterpret_cast<unsigned long long*>(m + o_lines));
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(lines, m + o_lines, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VK_OK;
+}
+
+int vk_clean_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
+                            uint64_t* bytes) {
+    if (!bytes || (nfiles && (!lengths || !records))) return VK_EINVAL;
+    *bytes = cl_layout(lengths, records, nfiles, nsamples).total;
+    return VK_OK;
+}
+
+int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                    const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                    uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
+                    uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
+                    uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status) {
+    if (!ctx || nsamples == 0 || !out_offsets || !d_out || !d_out_lengths || !d_stats || !d_status || !d_ws) return VK_EINVAL;
+    if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
+    if (flags & ~(VK_CL_ADAPTER | VK_CL_MERGE | VK_CL_DEDUP)) return VK_EINVAL;
+    if (trim_front > (1u << 30) || trim_tail > (1u << 30)) return VK_EINVAL;
+    const ClLayout L = cl_layout(lengths, records, nfiles, nsamples);
+    if (ws_bytes < L.total || L.nrec >= kClEmpty) return VK_EINVAL;
+    // the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order
+    std::vector<uint32_t> order(nfiles);
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
+        order[i] = i;
+    }
+    auto rank = [&](uint32_t i) { return roles[i] == VK_CL_ROLE_UNPAIRED ? 2u : roles[i] - 1u; };
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return samples[a] != samples[b] ? samples[a] < samples[b] : rank(a) < rank(b);
+    });
+    std::vector<ClFile> files(nfiles);
+    std::vector<uint64_t> fchunk(nfiles);
+    std::vector<ClSample> smp(nsamples);
+    std::vector<uint64_t> cnt(3ull * nsamples, 0), first(3ull * nsamples, ~0ull), cap(nsamples, 0);
+    uint64_t chunk = 0, rec = 0;
+    for (uint32_t j = 0; j < nfiles; ++j) {
+        const uint32_t i = order[j], s = samples[i], g = rank(i);
+        files[j] = ClFile{offsets[i], lengths[i], records[i], rec, chunk};
+        fchunk[j] = chunk;
+        chunk += (lengths[i] + kClChunk - 1) / kClChunk;
+        if (first[3ull * s + g] == ~0ull) first[3ull * s + g] = rec;
+        cnt[3ull * s + g] += records[i];
+        rec += records[i];
+        cap[s] += lengths[i];
+    }
+    std::vector<uint64_t> unit_base(nsamples + 1ull, 0);
+    for (uint32_t s = 0; s < nsamples; ++s) {
+        ClSample& d = smp[s];
+        d.r1 = first[3ull * s] == ~0ull ? 0 : first[3ull * s];
+        d.r2 = first[3ull * s + 1] == ~0ull ? 0 : first[3ull * s + 1];
+        d.se = first[3ull * s + 2] == ~0ull ? 0 : first[3ull * s + 2];
+        d.flags = cnt[3ull * s] != cnt[3ull * s + 1] ? VK_CL_RAGGED : 0u;
+        d.npairs = d.flags ? 0 : cnt[3ull * s];
+        d.nse = d.flags ? 0 : cnt[3ull * s + 2];
+        d.out_off = out_offsets[s];
+        d.out_cap = cap[s];
+        if (out_offsets[s] % 16 || out_offsets[s] + (cap[s] + 15) / 16 * 16 > out_bytes) return VK_EINVAL;
+        unit_base[s + 1] = unit_base[s] + d.npairs + d.nse;
+    }
+    const uint64_t nunits = unit_base[nsamples];
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* w = static_cast<uint8_t*>(d_ws);
+    auto* dfiles = reinterpret_cast<ClFile*>(w + L.files);
+    auto* dfchunk = reinterpret_cast<uint64_t*>(w + L.fchunk);
+    auto* dsmp = reinterpret_cast<ClSample*>(w + L.samples);
+    auto* dub = reinterpret_cast<uint64_t*>(w + L.unit_base);
+    auto* ccount = reinterpret_cast<uint64_t*>(w + L.ccount);
+    auto* cprefix = reinterpret_cast<uint64_t*>(w + L.cprefix);
+    auto* sums = reinterpret_cast<uint64_t*>(w + L.sums);
+    auto* recs = reinterpret_cast<ClRec*>(w + L.recs);
+    auto* hashes = reinterpret_cast<uint64_t*>(w + L.hashes);
+    auto* slot_of = reinterpret_cast<uint32_t*>(w + L.slot_of);
+    auto* plans = reinterpret_cast<ClPlan*>(w + L.plans);
+    auto* obytes = reinterpret_cast<uint64_t*>(w + L.obytes);
+    auto* oprefix = reinterpret_cast<uint64_t*>(w + L.oprefix);
+    auto* table = reinterpret_cast<uint32_t*>(w + L.table);
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    if (nfiles) {
+        VK_HIP(ctx, hipMemcpyAsync(dfiles, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(dfchunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    }
+    VK_HIP(ctx, hipMemcpyAsync(dsmp, smp.data(), nsamples * sizeof(ClSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(dub, unit_base.data(), (nsamples + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (L.nrec) VK_HIP(ctx, hipMemsetAsync(recs, 0xFF, L.nrec * sizeof(ClRec), ctx->stream));
+    if (flags & VK_CL_DEDUP) VK_HIP(ctx, hipMemsetAsync(table, 0xFF, L.nslots * 8, ctx->stream));
+    const uint32_t ninit = std::max(nsamples, nfiles);
+    hipLaunchKernelGGL(vk_cl_init_kernel, dim3((ninit + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                       dsmp, nsamples, dfiles, nfiles, recs, d_stats, static_cast<uint32_t>(VK_CL_NSTAT), d_status);
+    if (L.nchunks) {
+        hipLaunchKernelGGL(vk_cl_nl_count_kernel, dim3(L.nchunks), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
+                           nfiles, ccount);
+        int rc = cl_scan(ctx, ccount, L.nchunks, sums, cprefix);
+        if (rc) return rc;
+        hipLaunchKernelGGL(vk_cl_nl_write_kernel, dim3(L.nchunks), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
+                           nfiles, cprefix, recs);
+    }
+    const uint64_t ug = (nunits + kClThreads - 1) / kClThreads;
+    const uint64_t hash_mask = ctx->clean_hash_bits >= 64 ? ~0ull : ((1ull << ctx->clean_hash_bits) - 1);
+    if (nunits) {
+        hipLaunchKernelGGL(vk_cl_hash_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples, nunits,
+                           recs, hash_mask, hashes, d_status);
+        if (flags & VK_CL_DEDUP)
+            hipLaunchKernelGGL(vk_cl_dedup_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
+                               nunits, recs, hashes, d_status, table, L.nslots - 1, slot_of);
+        hipLaunchKernelGGL(vk_cl_clean_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples, nunits,
+                           recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes);
+    }
+    VK_HIP(ctx, hipGetLastError());
+    int rc = cl_scan(ctx, obytes, nunits, sums, oprefix);
+    if (rc) return rc;
+    if (nunits)
+        hipLaunchKernelGGL(vk_cl_write_kernel, dim3((nunits + kClUnitsPerBlock - 1) / kClUnitsPerBlock), dim3(kClThreads), 0,
+                           ctx->stream, text, dsmp, dub, nsamples, nunits, recs, plans, oprefix, d_out, d_stats,
+                           static_cast<uint32_t>(VK_CL_NSTAT));
+    hipLaunchKernelGGL(vk_cl_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, dsmp, dub, nsamples, oprefix,
+                       d_status, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }
 

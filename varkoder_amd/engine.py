@@ -594,6 +594,56 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_index_device")
         return hist, sites, st_h
 
+    def clean_lines(self, fastq, offsets, lengths):
+        """Newline bytes of each file in HBM (vk_clean_lines_device; // 4 = its records).  Synchronises."""
+        offs, lens = self._desc(offsets, lengths)
+        lines = np.zeros(len(offs), dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        st = self.L.vk_clean_lines_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
+                                          len(offs), lines.ctypes.data_as(u64p))
+        _capi.check(self.ctx, st, "vk_clean_lines_device")
+        return lines
+
+    def clean(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim=(10, 10), adapter=True, merge=True,
+              dedup=True):
+        """Step B for a batch of samples whose raw files are in HBM (vk_clean_device): file i gives its first
+        records[i] records to sample samples[i] as roles[i] (_capi.VK_CL_ROLE_*).  Returns (text uint8 tensor on the
+        device, offsets uint64[nsamples], lengths uint64[nsamples], stats uint64[nsamples, VK_CL_NSTAT], status
+        uint32[nsamples]); the arrays on the host (the call waits for the kernels)."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        roles = np.ascontiguousarray(roles, dtype=np.uint32)
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = len(offs)
+        if not (len(recs) == len(roles) == len(samples) == n):
+            raise ValueError("one record budget, role and sample per file")
+        cap = np.zeros(nsamples, dtype=np.uint64)
+        np.add.at(cap, samples.astype(np.int64), lens)
+        rounded = (cap + np.uint64(15)) // np.uint64(16) * np.uint64(16)
+        out_offs = np.zeros(nsamples, dtype=np.uint64)
+        if nsamples > 1:
+            out_offs[1:] = np.cumsum(rounded[:-1])
+        total = int(rounded.sum()) + 16
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_clean_workspace_size(lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p), n, nsamples,
+                                                             C.byref(ws_bytes)), "vk_clean_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        out = torch.empty(total, dtype=torch.uint8, device=self.device)
+        out_lens = torch.empty(nsamples, dtype=torch.int64, device=self.device)
+        stats = torch.empty((nsamples, _capi.VK_CL_NSTAT), dtype=torch.int64, device=self.device)
+        status = torch.empty(nsamples, dtype=torch.int32, device=self.device)
+        flags = (_capi.VK_CL_ADAPTER if adapter else 0) | (_capi.VK_CL_MERGE if merge else 0) | (_capi.VK_CL_DEDUP if dedup else 0)
+        st = self.L.vk_clean_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
+                                    recs.ctypes.data_as(u64p), roles.ctypes.data_as(u32p), samples.ctypes.data_as(u32p), n,
+                                    nsamples, int(trim[0]), int(trim[1]), flags, self._ptr(ws), ws.numel(), self._ptr(out),
+                                    out_offs.ctypes.data_as(u64p), total, self._ptr(out_lens), self._ptr(stats),
+                                    self._ptr(status))
+        _capi.check(self.ctx, st, "vk_clean_device")
+        return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
+                status.cpu().numpy().astype(np.uint32))
+
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""
         torch = _torch()

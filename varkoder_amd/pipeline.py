@@ -273,10 +273,7 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
     import os
 
-    import torch
-
     from .engine import ImageEngine
-    from .subsample import ladder_counts, split_name
     files = [Path(f) for f in files]
     labels, base_sd, seeds = labels or {}, base_sd or {}, seeds or {}
     if weights is None:
@@ -305,42 +302,8 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
             i += len(batch)
             names = [str(f.name.removesuffix("".join(f.suffixes))) for f in batch]
             dev, offs, lens = eng.upload_files(batch, pool)
-            recs = []
-            # one seed per launch: samples with different seeds go in separate calls
-            by_seed = OrderedDict()
-            for j, s in enumerate(names):
-                by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
-            recs = [None] * len(batch)
-            for seed, idx in by_seed.items():
-                for j, r in zip(idx, ladder_counts(eng, dev, offs[idx], lens[idx], seed=seed, min_bp=min_bp,
-                                                   max_bp=max_bp, is_query=is_query)):
-                    recs[j] = r
-            t1 = time.perf_counter()
-            flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
-            imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
-            nz = [bool((h != 0).any().item()) for _, _, h in flat]
-            t2 = time.perf_counter()
-            for j, s in enumerate(names):
-                st = stats.setdefault(s, OrderedDict())
-                if recs[j]["error"]:
-                    eprint("SPLIT FAIL:", batch[j], "-", recs[j]["error"])
-                    st["failed_step"] = "split"
-                    continue
-                st["splitting_time"] = (t1 - t0) / len(batch)
-                st["splitting_bp_per_file"] = ",".join(str(bp) for bp, _, _ in recs[j]["steps"])
-                st[str(k) + "mer_counting_time"] = (t1 - t0) / len(batch)
-            for n, (j, bp, _) in enumerate(flat):
-                s = names[j]
-                if not nz[n]:
-                    eprint("IMAGE FAIL:", split_name(s, bp))
-                    stats[s]["failed_step"] = "image"
-                    continue
-                name = png_name(split_name(s, bp) + "+k" + str(k) + ".fq.h5", mapping_code)
-                d = shard_folder(outdir, name, subfolder_levels)
-                d.mkdir(parents=True, exist_ok=True)
-                pending.append((s, time.perf_counter(),
-                                pool.submit(write_png, imgs[n].copy(), d / name, labels.get(s, []), base_sd.get(s, 0),
-                                            QUAL_THRESH, mapping_code)))
+            t1, t2 = _ladder_images(eng, dev, offs, lens, names, batch, t0, outdir, stats, pending, pool, k, mapping_code,
+                                    min_bp, max_bp, is_query, seeds, labels, base_sd, subfolder_levels)
             if verbose:
                 eprint(f"batch of {len(batch)} samples, {nbytes} bytes: upload+ladder {t1 - t0:.3f}s images {t2 - t1:.3f}s")
         for s, t, fut in pending:
@@ -355,3 +318,202 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     if engine is None:
         eng.close()
     return stats
+
+
+def _ladder_images(eng, dev, offs, lens, names, sources, t0, outdir, stats, pending, pool, k, mapping_code, min_bp, max_bp,
+                   is_query, seeds, labels, base_sd, subfolder_levels):
+    """Steps C+D+E for one batch of cleaned samples in HBM (dev[offs[i] .. +lens[i]) is sample names[i], read from
+    sources[i]): the ladder, the images, the stats rows and the PNG jobs (appended to `pending`).  Returns the times
+    the ladder and the images were done."""
+    import torch
+
+    from .subsample import ladder_counts, split_name
+    # one seed per launch: samples with different seeds go in separate calls
+    by_seed = OrderedDict()
+    for j, s in enumerate(names):
+        by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
+    recs = [None] * len(names)
+    for seed, idx in by_seed.items():
+        for j, r in zip(idx, ladder_counts(eng, dev, offs[idx], lens[idx], seed=seed, min_bp=min_bp,
+                                           max_bp=max_bp, is_query=is_query)):
+            recs[j] = r
+    t1 = time.perf_counter()
+    flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
+    imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
+    nz = [bool((h != 0).any().item()) for _, _, h in flat]
+    t2 = time.perf_counter()
+    for j, s in enumerate(names):
+        st = stats.setdefault(s, OrderedDict())
+        if recs[j]["error"]:
+            eprint("SPLIT FAIL:", sources[j], "-", recs[j]["error"])
+            st["failed_step"] = "split"
+            continue
+        st["splitting_time"] = (t1 - t0) / len(names)
+        st["splitting_bp_per_file"] = ",".join(str(bp) for bp, _, _ in recs[j]["steps"])
+        st[str(k) + "mer_counting_time"] = (t1 - t0) / len(names)
+    for n, (j, bp, _) in enumerate(flat):
+        s = names[j]
+        if not nz[n]:
+            eprint("IMAGE FAIL:", split_name(s, bp))
+            stats[s]["failed_step"] = "image"
+            continue
+        name = png_name(split_name(s, bp) + "+k" + str(k) + ".fq.h5", mapping_code)
+        d = shard_folder(outdir, name, subfolder_levels)
+        d.mkdir(parents=True, exist_ok=True)
+        pending.append((s, time.perf_counter(),
+                        pool.submit(write_png, imgs[n].copy(), d / name, labels.get(s, []), base_sd.get(s, 0),
+                                    QUAL_THRESH, mapping_code)))
+    return t1, t2
+
+
+def _sample_files(files):
+    """A raw sample's files in the order step B reads them: (path, role) with single-end files first, then R1, then R2,
+    each sorted (rawinput.pair_files; concatenate_reads, commands/image.py:264-315)."""
+    from . import _capi
+    from .rawinput import pair_files
+    p = pair_files(files)
+    return ([(f, _capi.VK_CL_ROLE_UNPAIRED) for f in sorted(p["unpaired"])] + [(f, _capi.VK_CL_ROLE_R1) for f in sorted(p["R1"])] +
+            [(f, _capi.VK_CL_ROLE_R2) for f in sorted(p["R2"])])
+
+
+def _budget(eng, dev, offs, lens, lines, sample_files, max_bp):
+    """Records of each file (rawinput.reads_needed) for one sample: sample_files [(path, role)], its files' slots in
+    the batch (offs / lens) and newline counts."""
+    from . import _capi
+    from .rawinput import avg_read_length, reads_needed
+    info = {"unpaired": [], "R1": [], "R2": []}
+    key = {_capi.VK_CL_ROLE_UNPAIRED: "unpaired", _capi.VK_CL_ROLE_R1: "R1", _capi.VK_CL_ROLE_R2: "R2"}
+    for j, (f, role) in enumerate(sample_files):
+        avg = 0
+        if max_bp is not None:   # (the mean length of the first 10,000 reads: from the head of the text in HBM)
+            o, n, take = int(offs[j]), int(lens[j]), 4 << 20
+            while True:
+                head = dev[o:o + min(n, take)].cpu().numpy().tobytes()
+                if take >= n or head.count(b"\n") >= 4 * 10000 + 1:
+                    break
+                take *= 4
+            avg = round(avg_read_length(head))
+        info[key[role]].append({"file": f, "avg_length": avg, "total_reads": int(lines[j]) // 4})
+    take = reads_needed(info, max_bp)
+    return [int(take.get(f, 0)) for f, _ in sample_files]
+
+
+def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
+                  merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
+                  batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None):
+    """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
+    rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
+    (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
+    leaving the device.  clean_dir: also write `<sample>.fq.gz` and `<sample>_fastp_gpu.json` (the content curves
+    get_basefrequency_sd reads) there, as the reference's intermediate folder holds them.
+
+    Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
+    (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
+    clean_to_images, or `failed_step`."""
+    import gzip
+    import json
+    import os
+
+    import numpy as np
+
+    from .engine import ImageEngine
+    from .rawinput import content_curves, curves_sd
+    labels, seeds = labels or {}, seeds or {}
+    plans = [(s, _sample_files(files)) for s, files in samples]
+    if weights is None:   # (per sample: the sum of its files' weights; a collective when sharded)
+        every = [f for _, sf in plans for f, _ in sf]
+        fw = agreed_weights(every) if world > 1 else file_weights(every)
+        weights, at = [], 0
+        for _, sf in plans:
+            weights.append(sum(fw[at:at + len(sf)]))
+            at += len(sf)
+    mine = [plans[i] for i in shard_by_size(weights, rank, world)]
+    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    if clean_dir is not None:
+        Path(clean_dir).mkdir(parents=True, exist_ok=True)
+    stats, base_sd = OrderedDict(), {}
+    pool = ThreadPoolExecutor(io_threads)
+    pending, writes = [], []
+    if batch_bytes is None:
+        batch_bytes = DEFAULT_BATCH_BYTES
+
+    def text_bytes(f):
+        f = Path(f)
+        return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
+
+    def write_clean(sample, text, curves):
+        with open(Path(clean_dir) / (sample + ".fq.gz"), "wb") as fh:
+            fh.write(gzip.compress(text, compresslevel=1))
+        with open(Path(clean_dir) / (sample + "_fastp_gpu.json"), "w") as fh:
+            json.dump({"read1_after_filtering": {"content_curves": curves}}, fh)
+
+    done = False
+    try:   # (an error below must not leave the pool writing files into outdir behind the caller's back)
+        i = 0
+        while i < len(mine):
+            batch, nbytes = [], 0
+            t0 = time.perf_counter()
+            for s, sf in mine[i:]:
+                sz = sum(text_bytes(f) for f, _ in sf)
+                if batch and nbytes + sz > batch_bytes:
+                    break
+                batch.append((s, sf))
+                nbytes += sz
+            i += len(batch)
+            paths = [Path(f) for _, sf in batch for f, _ in sf]
+            dev, offs, lens = eng.upload_files(paths, pool)
+            lines = eng.clean_lines(dev, offs, lens)
+            records, roles, owner, failed = [], [], [], set()
+            at = 0
+            for j, (s, sf) in enumerate(batch):
+                sl = slice(at, at + len(sf))
+                try:
+                    records += _budget(eng, dev, offs[sl], lens[sl], lines[sl], sf, max_bp)
+                except ZeroDivisionError:     # (a file without reads and a read budget: the reference fails here too)
+                    records += [0] * len(sf)
+                    failed.add(j)
+                roles += [r for _, r in sf]
+                owner += [j] * len(sf)
+                at += len(sf)
+            out, ooffs, olens, cst, status = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
+                                                       adapter=adapter, merge=merge, dedup=dedup)
+            del dev
+            tc = time.perf_counter()
+            ok = []
+            for j, (s, sf) in enumerate(batch):
+                st = stats.setdefault(s, OrderedDict())
+                if status[j] or j in failed:
+                    eprint("CLEAN FAIL:", [f for f, _ in sf], "- status", int(status[j]))
+                    st["failed_step"] = "clean"
+                    continue
+                row = cst[j]
+                curves = content_curves(row[2:2 + 160], row[162:202])
+                base_sd[s] = curves_sd(curves)
+                st["clean_basepairs"] = int(row[0]) if (adapter or merge) else float("nan")
+                st["cleaning_time"] = (tc - t0) / len(batch)
+                if clean_dir is not None:
+                    text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
+                    writes.append(pool.submit(write_clean, s, text, curves))
+                ok.append(j)
+            if ok:
+                _ladder_images(eng, out, ooffs[ok], olens[ok], [batch[j][0] for j in ok], [batch[j][0] for j in ok], tc,
+                               outdir, stats, pending, pool, k, mapping_code, min_bp, max_bp, False, seeds, labels,
+                               base_sd, subfolder_levels)
+            if verbose:
+                eprint(f"batch of {len(batch)} samples, {nbytes} raw bytes: upload+clean {tc - t0:.3f}s")
+        for w in writes:
+            w.result()
+        for s, t, fut in pending:
+            fut.result()
+            key = "k" + str(k) + "_img_time"
+            stats[s][key] = stats[s].get(key, 0) + (time.perf_counter() - t)
+        done = True
+    finally:
+        pool.shutdown(wait=True, cancel_futures=not done)
+        if not done and engine is None:
+            eng.close()
+    if engine is None:
+        eng.close()
+    return stats, base_sd
