@@ -259,6 +259,33 @@ int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, co
                     uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
                     uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status);
 
+/* Step B's adapters by sequence ("Step B"; tests/adapter_ref.py).  A sample has three groups: its
+ * R1 records, its R2 records and its single reads; group g of sample s is entry 3 s + g (0 R1, 1 R2, 2 unpaired) of
+ * the adapter arrays, which hold a length (0: none) and VK_CL_MAX_ADAPTER bytes per group.
+ *
+ * vk_clean_detect_device: the same files, records, roles and samples as vk_clean_device, and -T's tail value.
+ * Detects each group's adapter from its first VK_CL_DETECT_RECORDS budgeted records and writes it to the host arrays
+ * adapter_lengths[3 nsamples] / adapter_seqs[3 nsamples][VK_CL_MAX_ADAPTER].  d_ws: device workspace of
+ * vk_clean_detect_workspace_size bytes.  May grow a buffer of the context; synchronises.
+ *
+ * vk_clean_adapters_device: vk_clean_device, and with VK_CL_ADAPTER each read is also trimmed by its group's adapter
+ * (host arrays as above, 0..VK_CL_MAX_ADAPTER bytes, compared as they are).  d_adapter_stats[s][2] (u64): reads and
+ * bases of sample s cut by sequence.  May grow a buffer of the context; no synchronisation. */
+#define VK_CL_MAX_ADAPTER 64
+#define VK_CL_DETECT_RECORDS 262144
+int vk_clean_detect_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
+                                   uint64_t* bytes);
+int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                           const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                           uint32_t nsamples, uint32_t trim_tail, void* d_ws, uint64_t ws_bytes, uint32_t* adapter_lengths,
+                           uint8_t* adapter_seqs);
+int vk_clean_adapters_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                             const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                             uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
+                             uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
+                             uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* adapter_lengths,
+                             const uint8_t* adapter_seqs, uint64_t* d_adapter_stats);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -7,7 +7,11 @@ time (best of --reps, device-synchronised), GB/s of raw text, and the time of ea
 the wall time can be read off.  Under `rocprofv3 --kernel-trace --stats -- python tools/clean_time.py` the
 per-kernel times come from the trace.
 
-usage: python tools/clean_time.py [--pairs N] [--len L] [--reps R]
+--single-end cleans the R1 text alone, as one file of single reads.  --detect-adapters times adapter detection
+(vk_clean_detect_device) plus the clean with trimming by sequence (vk_clean_adapters_device) as one call, and adds
+the detection's own time and what it found to the line.
+
+usage: python tools/clean_time.py [--pairs N] [--len L] [--reps R] [--single-end] [--detect-adapters]
 """
 import argparse
 import json
@@ -60,6 +64,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=1_000_000)
     ap.add_argument("--len", type=int, default=150)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--single-end", action="store_true", help="the R1 text alone, as single reads")
+    ap.add_argument("--detect-adapters", action="store_true", help="detection + trimming by sequence in the timed call")
     a = ap.parse_args()
     import torch
     from varkoder_amd import _capi
@@ -67,24 +73,36 @@ def main():
     from varkoder_amd.subsample import ladder_counts
     eng = ImageEngine(k=7, mapping="cgr", device=0)
     r1, r2 = make_pairs(a.pairs, a.len)
-    raw = len(r1) + len(r2)
+    texts = [r1] if a.single_end else [r1, r2]
+    raw = sum(len(x) for x in texts)
     sync = torch.cuda.synchronize
     t = time.perf_counter()
-    dev, offs, lens = eng.upload([r1, r2])
+    dev, offs, lens = eng.upload(texts)
     sync()
     t_upload = time.perf_counter() - t
     t = time.perf_counter()
     lines = eng.clean_lines(dev, offs, lens)
     t_lines = time.perf_counter() - t
     recs = lines // 4
-    roles, owner = [_capi.VK_CL_ROLE_R1, _capi.VK_CL_ROLE_R2], [0, 0]
-    best = []
+    roles, owner = ([_capi.VK_CL_ROLE_UNPAIRED], [0]) if a.single_end else ([_capi.VK_CL_ROLE_R1, _capi.VK_CL_ROLE_R2], [0, 0])
+    best, detect, extra = [], [], {}
     for _ in range(a.reps):
         sync()
         t = time.perf_counter()
-        out, oo, ol, st, status = eng.clean(dev, offs, lens, recs, roles, owner, 1)   # (waits for the kernels)
+        if a.detect_adapters:
+            found = eng.detect_adapters(dev, offs, lens, recs, roles, owner, 1)
+            detect.append(time.perf_counter() - t)
+            out, oo, ol, st, status, ast = eng.clean(dev, offs, lens, recs, roles, owner, 1, adapters=found)
+        else:
+            out, oo, ol, st, status = eng.clean(dev, offs, lens, recs, roles, owner, 1)   # (waits for the kernels)
         best.append(time.perf_counter() - t)
     assert not status.any(), status
+    if a.detect_adapters:
+        extra = {"detect_s_best": min(detect), "detect_s_all": detect,
+                 "adapters": [x.decode() if x is not None else None for x in found[0]],
+                 "adapter_trimmed_reads": int(ast[0][0]), "adapter_trimmed_bases": int(ast[0][1])}
+    if a.single_end:
+        extra["single_end"] = True
     sync()
     t = time.perf_counter()
     rec = ladder_counts(eng, out, oo, ol, seed=1, min_bp=500000, max_bp=200_000_000)[0]
@@ -98,7 +116,7 @@ def main():
         "clean_s_best": clean_s, "clean_s_all": best, "clean_gb_s": raw / clean_s / 1e9,
         "upload_s": t_upload, "upload_gb_s": raw / t_upload / 1e9, "lines_s": t_lines, "ladder_images_s": t_ladder,
         "ladder_steps": len(rec["steps"]), "images": int(imgs.shape[0]),
-        "clean_share_of_device_path": clean_s / total}))
+        "clean_share_of_device_path": clean_s / total, **extra}))
     eng.close()
 
 

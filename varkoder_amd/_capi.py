@@ -12,6 +12,7 @@ VK_CL_ROLE_UNPAIRED, VK_CL_ROLE_R1, VK_CL_ROLE_R2 = 0, 1, 2
 VK_CL_ADAPTER, VK_CL_MERGE, VK_CL_DEDUP = 1, 2, 4
 VK_CL_BAD_FRAMING, VK_CL_RAGGED = 1, 2
 VK_CL_NSTAT = 202
+VK_CL_MAX_ADAPTER, VK_CL_DETECT_RECORDS = 64, 262144
 VK_GZ_BAD_HEADER, VK_GZ_BAD_DATA, VK_GZ_TRUNCATED, VK_GZ_OVERFLOW, VK_GZ_BAD_SIZE, VK_GZ_BAD_CRC = 1, 2, 4, 8, 16, 32
 
 # every symbol include/vkimg.h declares
@@ -20,7 +21,8 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_fastq_to_image_device", "vk_count_host", "vk_image_host", "vk_synth_fastq_device", "vk_remap_host", "vk_preprocess_device",
            "vk_last_count_launch", "vk_count_sampled_device", "vk_inflate_device", "vk_upload_mapped", "vk_host_register", "vk_host_unregister",
            "vk_synth_shaped_lengths", "vk_synth_shaped_device", "vk_last_count_general", "vk_read_index_device", "vk_count_index_device",
-           "vk_clean_lines_device", "vk_clean_workspace_size", "vk_clean_device")
+           "vk_clean_lines_device", "vk_clean_workspace_size", "vk_clean_device", "vk_clean_detect_workspace_size",
+           "vk_clean_detect_device", "vk_clean_adapters_device")
 
 _lib = None
 
@@ -72,6 +74,12 @@ def lib():
     L.vk_clean_workspace_size.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, u64p]
     L.vk_clean_device.argtypes = [vp, vp, u64p, u64p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint32, vp, C.c_uint64, vp, u64p, C.c_uint64, vp, vp, vp]
+    L.vk_clean_detect_workspace_size.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, u64p]
+    L.vk_clean_detect_device.argtypes = [vp, vp, u64p, u64p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                         C.c_uint64, u32p, u8p]
+    L.vk_clean_adapters_device.argtypes = [vp, vp, u64p, u64p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p, C.c_uint64, vp, vp, vp, u32p,
+                                           u8p, vp]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]
     L.vk_preprocess_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float, vp]

@@ -66,6 +66,14 @@ def setup_parser():
     entry.add_argument("--from-raw", action="store_true",
                        help="input holds RAW reads (`<taxon>/<sample>/*.fq[.gz]` or a CSV labels,sample,files): clean them "
                             "on the GPU (step B, the reference's fastp pass) and go on with the ladder")
+    # (SUPPRESS: a namespace without these flags is the one from before they existed; read them with getattr)
+    p.add_argument("--detect-adapters", action="store_true", default=argparse.SUPPRESS,
+                   help="with --from-raw: also detect each read group's adapter from its first reads and trim it by "
+                        "sequence (fastp's adapter detection, as INTEGRATION.md restates it)")
+    p.add_argument("--adapter-sequence", default=argparse.SUPPRESS, metavar="SEQ",
+                   help="with --from-raw: trim R1 and single reads by this adapter (4-64 bases of ACGT)")
+    p.add_argument("--adapter-sequence-r2", default=argparse.SUPPRESS, metavar="SEQ",
+                   help="with --from-raw: trim R2 by this adapter (default: --adapter-sequence)")
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query cleaned reads or images against a trained network (cli.py:327-446).")
     q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads) or, with "
@@ -118,6 +126,31 @@ def setup_parser():
     c.add_argument("input", help="path to folder with png images files to be converted.")
     c.add_argument("outdir", help="path to the folder where results will be saved.")
     return main
+
+
+ADAPTER_FLAGS = (("detect_adapters", "--detect-adapters"), ("adapter_sequence", "--adapter-sequence"),
+                 ("adapter_sequence_r2", "--adapter-sequence-r2"))
+
+
+def parse_args(argv=None):
+    """The parsed command line; the adapter flags of `image` are refused (exit 2) without --from-raw or with -a, and
+    their sequences are checked."""
+    parser = setup_parser()
+    args = parser.parse_args(argv)
+    if args.command == "image":
+        given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
+        if given and not args.from_raw:
+            parser.error(f"{', '.join(given)}: only with --from-raw")
+        if given and args.no_adapter:
+            parser.error(f"{', '.join(given)}: not with -a/--no-adapter")
+        from .adapters import parse_adapter
+        for name, flag in ADAPTER_FLAGS[1:]:
+            if hasattr(args, name):
+                try:
+                    setattr(args, name, parse_adapter(getattr(args, name)))
+                except ValueError as e:
+                    parser.error(f"{flag}: {e}")
+    return args
 
 
 def run_convert(args):
@@ -361,8 +394,11 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
                       seeds=seeds, labels=labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
         if raw:
+            a1, a2 = getattr(args, "adapter_sequence", None), getattr(args, "adapter_sequence_r2", None)
             got, sds = raw_to_images(raw, outdir, weights=weights, trim=(front, tail), adapter=not args.no_adapter,
-                                     merge=not args.no_merge, dedup=not args.no_deduplicate, clean_dir=clean_dir, **common)
+                                     merge=not args.no_merge, dedup=not args.no_deduplicate, clean_dir=clean_dir,
+                                     adapters=(a1, a2) if a1 is not None or a2 is not None else None,
+                                     detect_adapters=getattr(args, "detect_adapters", False), **common)
             per_sample.update(got)
             base_sd.update(sds)
         if done_clean:
@@ -506,7 +542,7 @@ def run_image(args):
 
 
 def main(argv=None):
-    args = setup_parser().parse_args(argv)
+    args = parse_args(argv)
     if not Path(args.input).exists():                                       # cli.py:503-505
         raise Exception("Input path", args.input, "does not exist. Please check.")
     if args.command == "image":

@@ -466,70 +466,125 @@ __device__ inline bool cl_trim(uint32_t len, uint32_t F, uint32_t T, uint32_t* a
     return true;
 }
 
+// an adapter of vk_clean_adapters_device: 2-bit codes (A0 C1 T2 G3, as ClWin) at the even bits of lo (positions 0..31)
+// and hi (32..63), non-ACGT flags at the same bits; len 0: none
+constexpr uint32_t kClMaxAdapter = 64;
+struct ClAdapter {
+    uint64_t lo, hi, nlo, nhi;
+    uint32_t len, pad;
+    uint8_t seq[kClMaxAdapter];
+};
+
+// trimming by sequence (vk_adapter.h, after this file in the translation unit)
+__device__ inline uint32_t cl_seq_cut(const uint8_t* p, uint32_t len, const ClAdapter* ad, uint32_t* nread, uint32_t* nbase);
+
+// kSeq: vk_clean_adapters_device -- adapters[3 sample + group] (R1, R2, single reads) trim by sequence, and the reads /
+// bases they cut go to ad_stats[2 sample + 0 / 1]; without it (vk_clean_device) both are unused
+template <bool kSeq>
 __global__ void __launch_bounds__(kClThreads) vk_cl_clean_kernel(const uint8_t* text, const ClSample* samples,
                                                                 const uint64_t* unit_base, uint32_t nsamples,
                                                                 uint64_t nunits, const ClRec* recs,
                                                                 const uint32_t* status, const uint32_t* table,
                                                                 const uint32_t* slot_of, uint32_t F, uint32_t T,
-                                                                uint32_t flags, ClPlan* plans, uint64_t* out_bytes) {
+                                                                uint32_t flags, ClPlan* plans, uint64_t* out_bytes,
+                                                                const ClAdapter* adapters, uint64_t* ad_stats) {
     const uint64_t u = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (u >= nunits) return;
-    const uint32_t si = cl_unit_sample(unit_base, nsamples, u);
-    ClPlan pl = {};
-    uint64_t bytes = 0;
-    bool keep = status[si] == 0;
-    if (keep && (flags & 4u)) keep = table[2ull * slot_of[u] + 1] == static_cast<uint32_t>(u);   // VK_CL_DEDUP
-    if (keep) {
-        const ClSample s = samples[si];
-        uint64_t r1, r2;
-        cl_unit_recs(s, u - unit_base[si], &r1, &r2);
-        const ClRec a = recs[r1];
-        const uint8_t* s1 = text + a.he + 1;
-        const uint32_t len1 = static_cast<uint32_t>(a.se - a.he - 1);
-        if (r2 == ~0ull) {
-            if (cl_trim(len1, F, T, &pl.a1, &pl.l1)) {
-                pl.l1 = cl_poly_g(s1 + pl.a1, pl.l1);
-                if (pl.l1) {
-                    pl.flags = 1;
-                    bytes = (a.he - a.h) + 2ull * pl.l1 + 5;
-                }
-            }
-        } else {
-            const ClRec b = recs[r2];
-            const uint8_t* s2 = text + b.he + 1;
-            const uint32_t len2 = static_cast<uint32_t>(b.se - b.he - 1);
-            if (cl_trim(len1, F, T, &pl.a1, &pl.l1) && cl_trim(len2, F, T, &pl.a2, &pl.l2)) {
-                pl.l1 = cl_poly_g(s1 + pl.a1, pl.l1);
-                pl.l2 = cl_poly_g(s2 + pl.a2, pl.l2);
-                int off;
-                uint32_t ol;
-                if ((flags & 1u) && cl_overlap(s1 + pl.a1, pl.l1, s2 + pl.a2, pl.l2, &off, &ol) && off < 0) {   // VK_CL_ADAPTER
-                    pl.l1 = min(pl.l1, ol + F);
-                    pl.l2 = min(pl.l2, ol + F);
-                }
-                if ((flags & 2u) && cl_overlap(s1 + pl.a1, pl.l1, s2 + pl.a2, pl.l2, &off, &ol)) {    // VK_CL_MERGE
-                    pl.m1 = ol + (off > 0 ? static_cast<uint32_t>(off) : 0u);
-                    pl.t0 = ol;
-                    pl.m2 = off > 0 ? pl.l2 - ol : 0u;
-                    if (pl.m1 + pl.m2) {
-                        pl.flags = 1 | 4;
-                        bytes = (a.he - a.h) + 2ull * (pl.m1 + pl.m2) + 5;
+    if constexpr (!kSeq) {
+        if (u >= nunits) return;
+    }
+    uint32_t si = 0, nread = 0, nbase = 0;   // (kSeq: reads and bases of this unit cut by sequence)
+    if (u < nunits) {
+        si = cl_unit_sample(unit_base, nsamples, u);
+        ClPlan pl = {};
+        uint64_t bytes = 0;
+        bool keep = status[si] == 0;
+        if (keep && (flags & 4u)) keep = table[2ull * slot_of[u] + 1] == static_cast<uint32_t>(u);   // VK_CL_DEDUP
+        if (keep) {
+            const ClSample s = samples[si];
+            uint64_t r1, r2;
+            cl_unit_recs(s, u - unit_base[si], &r1, &r2);
+            const ClRec a = recs[r1];
+            const uint8_t* s1 = text + a.he + 1;
+            const uint32_t len1 = static_cast<uint32_t>(a.se - a.he - 1);
+            if (r2 == ~0ull) {
+                if (cl_trim(len1, F, T, &pl.a1, &pl.l1)) {
+                    pl.l1 = cl_poly_g(s1 + pl.a1, pl.l1);
+                    if constexpr (kSeq) {
+                        if (flags & 1u) pl.l1 = cl_seq_cut(s1 + pl.a1, pl.l1, adapters + 3ull * si + 2, &nread, &nbase);
                     }
-                } else {
                     if (pl.l1) {
-                        pl.flags |= 1;
-                        bytes += (a.he - a.h) + 2ull * pl.l1 + 5;
+                        pl.flags = 1;
+                        bytes = (a.he - a.h) + 2ull * pl.l1 + 5;
                     }
-                    if (pl.l2) {
-                        pl.flags |= 2;
-                        bytes += (b.he - b.h) + 2ull * pl.l2 + 5;
+                }
+            } else {
+                const ClRec b = recs[r2];
+                const uint8_t* s2 = text + b.he + 1;
+                const uint32_t len2 = static_cast<uint32_t>(b.se - b.he - 1);
+                if (cl_trim(len1, F, T, &pl.a1, &pl.l1) && cl_trim(len2, F, T, &pl.a2, &pl.l2)) {
+                    pl.l1 = cl_poly_g(s1 + pl.a1, pl.l1);
+                    pl.l2 = cl_poly_g(s2 + pl.a2, pl.l2);
+                    int off;
+                    uint32_t ol;
+                    bool cut = false;
+                    if ((flags & 1u) && cl_overlap(s1 + pl.a1, pl.l1, s2 + pl.a2, pl.l2, &off, &ol) && off < 0) {   // VK_CL_ADAPTER
+                        pl.l1 = min(pl.l1, ol + F);
+                        pl.l2 = min(pl.l2, ol + F);
+                        cut = true;
+                    }
+                    if constexpr (kSeq) {
+                        if ((flags & 1u) && !cut) {   // the overlap did not cut the pair: each mate by its adapter
+                            pl.l1 = cl_seq_cut(s1 + pl.a1, pl.l1, adapters + 3ull * si, &nread, &nbase);
+                            pl.l2 = cl_seq_cut(s2 + pl.a2, pl.l2, adapters + 3ull * si + 1, &nread, &nbase);
+                        }
+                    }
+                    if ((flags & 2u) && cl_overlap(s1 + pl.a1, pl.l1, s2 + pl.a2, pl.l2, &off, &ol)) {    // VK_CL_MERGE
+                        pl.m1 = ol + (off > 0 ? static_cast<uint32_t>(off) : 0u);
+                        pl.t0 = ol;
+                        pl.m2 = off > 0 ? pl.l2 - ol : 0u;
+                        if (pl.m1 + pl.m2) {
+                            pl.flags = 1 | 4;
+                            bytes = (a.he - a.h) + 2ull * (pl.m1 + pl.m2) + 5;
+                        }
+                    } else {
+                        if (pl.l1) {
+                            pl.flags |= 1;
+                            bytes += (a.he - a.h) + 2ull * pl.l1 + 5;
+                        }
+                        if (pl.l2) {
+                            pl.flags |= 2;
+                            bytes += (b.he - b.h) + 2ull * pl.l2 + 5;
+                        }
                     }
                 }
             }
         }
+        plans[u] = pl;
+        out_bytes[u] = bytes;
     }
-    plans[u] = pl;
-    out_bytes[u] = bytes;
+    if constexpr (kSeq) {
+        // the workgroup's first sample: summed in LDS, one global add; a unit of another sample adds its own
+        __shared__ uint64_t red[2][kClThreads];
+        const uint32_t s0 = cl_unit_sample(unit_base, nsamples, static_cast<uint64_t>(blockIdx.x) * blockDim.x);
+        const bool local = u < nunits && si == s0;
+        if (!local && nread) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(ad_stats + 2ull * si), static_cast<unsigned long long>(nread));
+            atomicAdd(reinterpret_cast<unsigned long long*>(ad_stats + 2ull * si + 1), static_cast<unsigned long long>(nbase));
+        }
+        red[0][threadIdx.x] = local ? nread : 0;
+        red[1][threadIdx.x] = local ? nbase : 0;
+        __syncthreads();
+        for (uint32_t s = kClThreads / 2; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+                red[0][threadIdx.x] += red[0][threadIdx.x + s];
+                red[1][threadIdx.x] += red[1][threadIdx.x + s];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x < 2 && red[threadIdx.x][0])
+            atomicAdd(reinterpret_cast<unsigned long long*>(ad_stats + 2ull * s0 + threadIdx.x),
+                      static_cast<unsigned long long>(red[threadIdx.x][0]));
+    }
 }
 
 // the wave's copy of n bytes: out[i] = f(i), lanes take consecutive bytes

@@ -35,6 +35,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -48,6 +49,7 @@
 #include "vk_inflate.h"
 #include "vk_aux.h"
 #include "vk_clean.h"
+#include "vk_adapter.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -125,6 +127,10 @@ struct vk_ctx {
     bool spill_force_wide = false; // VKIMG_SPILL_FORCE_WIDE=1: every k = 8, 9 replay job through the u32 window counters (tests)
     uint8_t* d_clines = nullptr;   // vk_clean_lines_device: files | chunk bases | line counters
     size_t clines_cap = 0;
+    uint8_t* d_cladapt = nullptr;  // vk_clean_adapters_device: the adapter table (ClAdapter per sample and group)
+    size_t cladapt_cap = 0;
+    uint8_t* d_cldetect = nullptr; // vk_clean_detect_device: a slice's seed occurrences and their states
+    size_t cldetect_cap = 0;
     uint32_t clean_hash_bits = 64; // VKIMG_CLEAN_HASH_BITS=n: vk_clean_device's dedup keeps n bits of its 64-bit hash (tests: collisions on purpose)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
@@ -574,7 +580,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -1694,34 +1700,44 @@ int vk_clean_workspace_size(const uint64_t* lengths, const uint64_t* records, ui
     return VK_OK;
 }
 
-int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
-                    const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
-                    uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
-                    uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
-                    uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status) {
+}  // extern "C"
+
+namespace {
+
+uint32_t cl_rank(uint32_t role) { return role == VK_CL_ROLE_UNPAIRED ? 2u : role - 1u; }   // a file's group: R1, R2, single reads
+
+// the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order
+std::vector<uint32_t> cl_order(const uint32_t* roles, const uint32_t* samples, uint32_t nfiles) {
+    std::vector<uint32_t> order(nfiles);
+    for (uint32_t i = 0; i < nfiles; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return samples[a] != samples[b] ? samples[a] < samples[b] : cl_rank(roles[a]) < cl_rank(roles[b]);
+    });
+    return order;
+}
+
+// vk_clean_device, and with ad_lengths vk_clean_adapters_device
+int cl_clean(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+             const uint32_t* roles, const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint32_t trim_front,
+             uint32_t trim_tail, uint32_t flags, void* d_ws, uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets,
+             uint64_t out_bytes, uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* ad_lengths,
+             const uint8_t* ad_seqs, uint64_t* d_ad_stats) {
     if (!ctx || nsamples == 0 || !out_offsets || !d_out || !d_out_lengths || !d_stats || !d_status || !d_ws) return VK_EINVAL;
     if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
     if (flags & ~(VK_CL_ADAPTER | VK_CL_MERGE | VK_CL_DEDUP)) return VK_EINVAL;
     if (trim_front > (1u << 30) || trim_tail > (1u << 30)) return VK_EINVAL;
     const ClLayout L = cl_layout(lengths, records, nfiles, nsamples);
     if (ws_bytes < L.total || L.nrec >= kClEmpty) return VK_EINVAL;
-    // the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order
-    std::vector<uint32_t> order(nfiles);
-    for (uint32_t i = 0; i < nfiles; ++i) {
+    for (uint32_t i = 0; i < nfiles; ++i)
         if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
-        order[i] = i;
-    }
-    auto rank = [&](uint32_t i) { return roles[i] == VK_CL_ROLE_UNPAIRED ? 2u : roles[i] - 1u; };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return samples[a] != samples[b] ? samples[a] < samples[b] : rank(a) < rank(b);
-    });
+    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
     std::vector<ClFile> files(nfiles);
     std::vector<uint64_t> fchunk(nfiles);
     std::vector<ClSample> smp(nsamples);
     std::vector<uint64_t> cnt(3ull * nsamples, 0), first(3ull * nsamples, ~0ull), cap(nsamples, 0);
     uint64_t chunk = 0, rec = 0;
     for (uint32_t j = 0; j < nfiles; ++j) {
-        const uint32_t i = order[j], s = samples[i], g = rank(i);
+        const uint32_t i = order[j], s = samples[i], g = cl_rank(roles[i]);
         files[j] = ClFile{offsets[i], lengths[i], records[i], rec, chunk};
         fchunk[j] = chunk;
         chunk += (lengths[i] + kClChunk - 1) / kClChunk;
@@ -1746,6 +1762,27 @@ int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, co
     }
     const uint64_t nunits = unit_base[nsamples];
     VK_HIP(ctx, hipSetDevice(ctx->device));
+    const ClAdapter* dads = nullptr;
+    if (ad_lengths) {   // the adapter table as 2-bit codes, in a buffer of the context
+        std::vector<ClAdapter> ads(3ull * nsamples);
+        for (uint64_t g = 0; g < ads.size(); ++g) {
+            ClAdapter& d = ads[g];
+            d = ClAdapter{};
+            d.len = ad_lengths[g];
+            for (uint32_t i = 0; i < d.len; ++i) {
+                const uint8_t b = ad_seqs[g * kAdMaxAdapter + i];
+                const uint64_t c = (b >> 1) & 3u, bad = (b == 'A' || b == 'C' || b == 'G' || b == 'T') ? 0u : 1u;
+                d.seq[i] = b;
+                (i < 32 ? d.lo : d.hi) |= c << (2 * (i % 32));
+                (i < 32 ? d.nlo : d.nhi) |= bad << (2 * (i % 32));
+            }
+        }
+        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cladapt), &ctx->cladapt_cap, ads.size() * sizeof(ClAdapter));
+        if (rc) return rc;
+        VK_HIP(ctx, hipMemcpyAsync(ctx->d_cladapt, ads.data(), ads.size() * sizeof(ClAdapter), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_ad_stats, 0, 2ull * nsamples * sizeof(uint64_t), ctx->stream));
+        dads = reinterpret_cast<const ClAdapter*>(ctx->d_cladapt);
+    }
     uint8_t* w = static_cast<uint8_t*>(d_ws);
     auto* dfiles = reinterpret_cast<ClFile*>(w + L.files);
     auto* dfchunk = reinterpret_cast<uint64_t*>(w + L.fchunk);
@@ -1789,8 +1826,14 @@ int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, co
         if (flags & VK_CL_DEDUP)
             hipLaunchKernelGGL(vk_cl_dedup_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
                                nunits, recs, hashes, d_status, table, L.nslots - 1, slot_of);
-        hipLaunchKernelGGL(vk_cl_clean_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples, nunits,
-                           recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes);
+        if (dads)
+            hipLaunchKernelGGL(vk_cl_clean_kernel<true>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
+                               nunits, recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes, dads,
+                               d_ad_stats);
+        else
+            hipLaunchKernelGGL(vk_cl_clean_kernel<false>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
+                               nunits, recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes,
+                               static_cast<const ClAdapter*>(nullptr), static_cast<uint64_t*>(nullptr));
     }
     VK_HIP(ctx, hipGetLastError());
     int rc = cl_scan(ctx, obytes, nunits, sums, oprefix);
@@ -1802,6 +1845,227 @@ int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, co
     hipLaunchKernelGGL(vk_cl_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, dsmp, dub, nsamples, oprefix,
                        d_status, d_out, d_out_lengths);
     VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                    const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                    uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
+                    uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
+                    uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status) {
+    return cl_clean(ctx, d_text, offsets, lengths, records, roles, samples, nfiles, nsamples, trim_front, trim_tail, flags,
+                    d_ws, ws_bytes, d_out, out_offsets, out_bytes, d_out_lengths, d_stats, d_status, nullptr, nullptr, nullptr);
+}
+
+int vk_clean_adapters_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                             const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                             uint32_t nsamples, uint32_t trim_front, uint32_t trim_tail, uint32_t flags, void* d_ws,
+                             uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_bytes,
+                             uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* adapter_lengths,
+                             const uint8_t* adapter_seqs, uint64_t* d_adapter_stats) {
+    if (!adapter_lengths || !adapter_seqs || !d_adapter_stats) return VK_EINVAL;
+    for (uint64_t g = 0; g < 3ull * nsamples; ++g)
+        if (adapter_lengths[g] > kAdMaxAdapter) return VK_EINVAL;
+    return cl_clean(ctx, d_text, offsets, lengths, records, roles, samples, nfiles, nsamples, trim_front, trim_tail, flags,
+                    d_ws, ws_bytes, d_out, out_offsets, out_bytes, d_out_lengths, d_stats, d_status, adapter_lengths,
+                    adapter_seqs, d_adapter_stats);
+}
+
+}  // extern "C"
+
+namespace {
+
+// byte offsets of the pieces of a vk_clean_detect_device workspace: the record index of vk_clean_device's layout, then
+// a slice's tables
+struct AdLayout {
+    ClLayout c;
+    size_t hist, groups, gbase, ranked, totals, cands, counts, ext, total;
+    uint32_t slice;
+};
+
+AdLayout ad_layout(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
+    AdLayout L{};
+    L.c = cl_layout(lengths, records, nfiles, nsamples);
+    L.slice = static_cast<uint32_t>(std::min<uint64_t>(kAdSlice, 3ull * nsamples));
+    size_t at = L.c.total;
+    auto take = [&](size_t bytes) { const size_t o = at; at += cl_align(bytes); return o; };
+    L.hist = take(static_cast<size_t>(L.slice) * kAdKeys * 4);
+    L.groups = take(L.slice * sizeof(AdGroup));
+    L.gbase = take((L.slice + 1ull) * 8);
+    L.ranked = take(L.slice * kAdTop * 8ull);
+    L.totals = take(L.slice * 8ull);
+    L.cands = take(L.slice * kAdTop * sizeof(AdCand));
+    L.counts = take(L.slice * kAdTop * 4ull);
+    L.ext = take(L.slice * kAdTop * sizeof(AdExt));
+    L.total = at;
+    return L;
+}
+
+// D = reverse(backward) + seed + forward, its first kAdMaxLen bytes
+std::string ad_detected(const AdExt& e, uint32_t key) {
+    std::string d;
+    const uint32_t nb = std::min(e.nb, kAdMaxLen);
+    for (uint32_t i = 0; i < nb; ++i) d += static_cast<char>(e.back[(e.nb - 1 - i) % kAdKeep]);
+    for (uint32_t i = 0; i < kAdK; ++i) d += "ACGT"[(key >> (2 * (kAdK - 1 - i))) & 3u];
+    for (uint32_t i = 0; i < std::min(e.nf, kAdKeep); ++i) d += static_cast<char>(e.fwd[i]);
+    if (d.size() > kAdMaxLen) d.resize(kAdMaxLen);
+    return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_clean_detect_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
+                                   uint64_t* bytes) {
+    if (!bytes || (nfiles && (!lengths || !records))) return VK_EINVAL;
+    *bytes = ad_layout(lengths, records, nfiles, nsamples).total;
+    return VK_OK;
+}
+
+int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                           const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
+                           uint32_t nsamples, uint32_t trim_tail, void* d_ws, uint64_t ws_bytes, uint32_t* adapter_lengths,
+                           uint8_t* adapter_seqs) {
+    if (!ctx || nsamples == 0 || !d_ws || !adapter_lengths || !adapter_seqs) return VK_EINVAL;
+    if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
+    if (trim_tail > (1u << 30)) return VK_EINVAL;
+    const AdLayout L = ad_layout(lengths, records, nfiles, nsamples);
+    if (ws_bytes < L.total || L.c.nrec >= kClEmpty) return VK_EINVAL;
+    for (uint32_t i = 0; i < nfiles; ++i)
+        if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
+    const uint64_t ngroups = 3ull * nsamples;
+    std::fill(adapter_lengths, adapter_lengths + ngroups, 0u);
+    std::fill(adapter_seqs, adapter_seqs + ngroups * kAdMaxAdapter, uint8_t{0});
+    // the index holds each group's evaluation set: its first kAdEval records, in the order of its files
+    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
+    std::vector<ClFile> files(nfiles);
+    std::vector<uint64_t> fchunk(nfiles), taken(ngroups, 0), first(ngroups, 0);
+    uint64_t chunk = 0, rec = 0;
+    for (uint32_t j = 0; j < nfiles; ++j) {
+        const uint32_t i = order[j];
+        const uint64_t g = 3ull * samples[i] + cl_rank(roles[i]);
+        const uint64_t n = std::min<uint64_t>(records[i], kAdEval - taken[g]);
+        if (taken[g] == 0) first[g] = rec;
+        files[j] = ClFile{offsets[i], lengths[i], n, rec, chunk};
+        fchunk[j] = chunk;
+        chunk += (lengths[i] + kClChunk - 1) / kClChunk;
+        taken[g] += n;
+        rec += n;
+    }
+    std::vector<uint64_t> active;   // groups with records
+    for (uint64_t g = 0; g < ngroups; ++g)
+        if (taken[g]) active.push_back(g);
+    if (active.empty()) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* w = static_cast<uint8_t*>(d_ws);
+    auto* dfiles = reinterpret_cast<ClFile*>(w + L.c.files);
+    auto* dfchunk = reinterpret_cast<uint64_t*>(w + L.c.fchunk);
+    auto* ccount = reinterpret_cast<uint64_t*>(w + L.c.ccount);
+    auto* cprefix = reinterpret_cast<uint64_t*>(w + L.c.cprefix);
+    auto* sums = reinterpret_cast<uint64_t*>(w + L.c.sums);
+    auto* recs = reinterpret_cast<ClRec*>(w + L.c.recs);
+    auto* hist = reinterpret_cast<uint32_t*>(w + L.hist);
+    auto* dgroups = reinterpret_cast<AdGroup*>(w + L.groups);
+    auto* gbase = reinterpret_cast<uint64_t*>(w + L.gbase);
+    auto* ranked = reinterpret_cast<uint64_t*>(w + L.ranked);
+    auto* totals = reinterpret_cast<uint64_t*>(w + L.totals);
+    auto* dcands = reinterpret_cast<AdCand*>(w + L.cands);
+    auto* counts = reinterpret_cast<uint32_t*>(w + L.counts);
+    auto* dext = reinterpret_cast<AdExt*>(w + L.ext);
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    VK_HIP(ctx, hipMemcpyAsync(dfiles, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(dfchunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(recs, 0xFF, rec * sizeof(ClRec), ctx->stream));
+    hipLaunchKernelGGL(vk_cl_init_kernel, dim3((nfiles + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                       static_cast<const ClSample*>(nullptr), 0u, dfiles, nfiles, recs, static_cast<uint64_t*>(nullptr), 0u,
+                       static_cast<uint32_t*>(nullptr));
+    if (chunk) {
+        hipLaunchKernelGGL(vk_cl_nl_count_kernel, dim3(chunk), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk, nfiles,
+                           ccount);
+        int rc = cl_scan(ctx, ccount, chunk, sums, cprefix);
+        if (rc) return rc;
+        hipLaunchKernelGGL(vk_cl_nl_write_kernel, dim3(chunk), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
+                           nfiles, cprefix, recs);
+    }
+    VK_HIP(ctx, hipGetLastError());
+    const uint32_t shift_tail = std::max(1u, trim_tail);
+    for (size_t g0 = 0; g0 < active.size(); g0 += L.slice) {
+        const uint32_t ng = static_cast<uint32_t>(std::min<size_t>(L.slice, active.size() - g0));
+        std::vector<AdGroup> grp(ng);
+        std::vector<uint64_t> base(ng + 1ull, 0);
+        for (uint32_t k = 0; k < ng; ++k) {
+            grp[k] = AdGroup{first[active[g0 + k]], taken[active[g0 + k]]};
+            base[k + 1] = base[k] + grp[k].n;
+        }
+        const uint64_t nrec = base[ng];
+        VK_HIP(ctx, hipMemcpyAsync(dgroups, grp.data(), ng * sizeof(AdGroup), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(gbase, base.data(), (ng + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(hist, 0, static_cast<size_t>(ng) * kAdKeys * 4, ctx->stream));
+        hipLaunchKernelGGL(vk_ad_hist_kernel, dim3((nrec + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                           text, recs, dgroups, gbase, ng, hist);
+        hipLaunchKernelGGL(vk_ad_top_kernel, dim3(ng), dim3(kAdThreads), 0, ctx->stream, hist, ranked, totals);
+        VK_HIP(ctx, hipGetLastError());
+        std::vector<uint64_t> rk(ng * kAdTop), tot(ng);
+        VK_HIP(ctx, hipMemcpyAsync(rk.data(), ranked, rk.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(tot.data(), totals, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // candidates: ranked keys with count * 4^10 / total > 20; each gets room for `count` occurrences (the
+        // extension's positions are a part of the counted ones)
+        std::vector<AdCand> cand(ng * kAdTop);
+        uint64_t nocc = 0;
+        for (uint32_t k = 0; k < ng; ++k)
+            for (uint32_t c = 0; c < kAdTop; ++c) {
+                const uint64_t v = rk[k * kAdTop + c], cnt = v >> 20;
+                AdCand& d = cand[k * kAdTop + c];
+                d = AdCand{static_cast<uint32_t>(kAdKeys - 1 - (v & (kAdKeys - 1))), 0, nocc};
+                if (v && tot[k] && cnt * kAdKeys / tot[k] > kAdFold) {
+                    d.cap = static_cast<uint32_t>(cnt);
+                    nocc += cnt;
+                }
+            }
+        if (nocc == 0) continue;
+        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cldetect), &ctx->cldetect_cap,
+                        cl_align(nocc * sizeof(AdOcc)) + nocc * sizeof(uint16_t));
+        if (rc) return rc;
+        auto* occ = reinterpret_cast<AdOcc*>(ctx->d_cldetect);
+        auto* state = reinterpret_cast<uint16_t*>(ctx->d_cldetect + cl_align(nocc * sizeof(AdOcc)));
+        VK_HIP(ctx, hipMemcpyAsync(dcands, cand.data(), cand.size() * sizeof(AdCand), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(counts, 0, cand.size() * 4, ctx->stream));
+        hipLaunchKernelGGL(vk_ad_collect_kernel, dim3((nrec + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                           text, recs, dgroups, gbase, ng, dcands, shift_tail, counts, occ);
+        hipLaunchKernelGGL(vk_ad_extend_kernel, dim3(ng * kAdTop), dim3(kAdThreads), 0, ctx->stream, text, dcands, counts, occ,
+                           state, dext);
+        VK_HIP(ctx, hipGetLastError());
+        std::vector<AdExt> ext(ng * kAdTop);
+        VK_HIP(ctx, hipMemcpyAsync(ext.data(), dext, ext.size() * sizeof(AdExt), hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // the first candidate accepted: snapped to a listed adapter, or both directions ran out
+        for (uint32_t k = 0; k < ng; ++k)
+            for (uint32_t c = 0; c < kAdTop; ++c) {
+                const AdCand& d = cand[k * kAdTop + c];
+                if (!d.cap || ext[k * kAdTop + c].nocc < kAdMinVotes) continue;   // (no evidence either way)
+                const std::string D = ad_detected(ext[k * kAdTop + c], d.key);
+                std::string got;
+                for (const char* known : kAdKnown) {
+                    const std::string ad(known);
+                    if (D.find(ad.substr(0, kAdSnap)) != std::string::npos) {
+                        got = ad;
+                        break;
+                    }
+                }
+                if (got.empty() && (ext[k * kAdTop + c].flags & 3u) == 3u) got = D;
+                if (got.empty()) continue;
+                const uint64_t g = active[g0 + k];
+                adapter_lengths[g] = static_cast<uint32_t>(got.size());
+                memcpy(adapter_seqs + g * kAdMaxAdapter, got.data(), got.size());
+                break;
+            }
+    }
     return VK_OK;
 }
 

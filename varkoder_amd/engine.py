@@ -604,12 +604,43 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_clean_lines_device")
         return lines
 
+    def detect_adapters(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim_tail=10):
+        """Each group's adapter detected from its first reads (vk_clean_detect_device; the files, records, roles and
+        samples of clean()): a list of [R1's, R2's, the single reads'] per sample, bytes or None.  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        roles = np.ascontiguousarray(roles, dtype=np.uint32)
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        n = len(offs)
+        if not (len(recs) == len(roles) == len(samples) == n):
+            raise ValueError("one record budget, role and sample per file")
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_clean_detect_workspace_size(lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p), n,
+                                                                    nsamples, C.byref(ws_bytes)),
+                    "vk_clean_detect_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        alen = np.zeros(3 * nsamples, dtype=np.uint32)
+        aseq = np.zeros((3 * nsamples, _capi.VK_CL_MAX_ADAPTER), dtype=np.uint8)
+        st = self.L.vk_clean_detect_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
+                                           recs.ctypes.data_as(u64p), roles.ctypes.data_as(u32p),
+                                           samples.ctypes.data_as(u32p), n, nsamples, int(trim_tail), self._ptr(ws),
+                                           ws.numel(), alen.ctypes.data_as(u32p),
+                                           aseq.ctypes.data_as(C.POINTER(C.c_uint8)))
+        _capi.check(self.ctx, st, "vk_clean_detect_device")
+        return [[aseq[3 * j + g, :alen[3 * j + g]].tobytes() if alen[3 * j + g] else None for g in range(3)]
+                for j in range(nsamples)]
+
     def clean(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim=(10, 10), adapter=True, merge=True,
-              dedup=True):
+              dedup=True, adapters=None):
         """Step B for a batch of samples whose raw files are in HBM (vk_clean_device): file i gives its first
         records[i] records to sample samples[i] as roles[i] (_capi.VK_CL_ROLE_*).  Returns (text uint8 tensor on the
         device, offsets uint64[nsamples], lengths uint64[nsamples], stats uint64[nsamples, VK_CL_NSTAT], status
-        uint32[nsamples]); the arrays on the host (the call waits for the kernels)."""
+        uint32[nsamples]); the arrays on the host (the call waits for the kernels).
+
+        adapters: per sample [R1's, R2's, the single reads'] adapter (bytes or None) to trim by sequence as well
+        (vk_clean_adapters_device); the result then ends with adapter stats uint64[nsamples, 2] (reads, bases cut)."""
         torch = _torch()
         offs, lens = self._desc(offsets, lengths)
         recs = np.ascontiguousarray(records, dtype=np.uint64)
@@ -635,14 +666,33 @@ class ImageEngine:
         stats = torch.empty((nsamples, _capi.VK_CL_NSTAT), dtype=torch.int64, device=self.device)
         status = torch.empty(nsamples, dtype=torch.int32, device=self.device)
         flags = (_capi.VK_CL_ADAPTER if adapter else 0) | (_capi.VK_CL_MERGE if merge else 0) | (_capi.VK_CL_DEDUP if dedup else 0)
-        st = self.L.vk_clean_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
-                                    recs.ctypes.data_as(u64p), roles.ctypes.data_as(u32p), samples.ctypes.data_as(u32p), n,
-                                    nsamples, int(trim[0]), int(trim[1]), flags, self._ptr(ws), ws.numel(), self._ptr(out),
-                                    out_offs.ctypes.data_as(u64p), total, self._ptr(out_lens), self._ptr(stats),
-                                    self._ptr(status))
-        _capi.check(self.ctx, st, "vk_clean_device")
+        args = (self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p),
+                roles.ctypes.data_as(u32p), samples.ctypes.data_as(u32p), n, nsamples, int(trim[0]), int(trim[1]), flags,
+                self._ptr(ws), ws.numel(), self._ptr(out), out_offs.ctypes.data_as(u64p), total, self._ptr(out_lens),
+                self._ptr(stats), self._ptr(status))
+        if adapters is None:
+            st = self.L.vk_clean_device(*args)
+            _capi.check(self.ctx, st, "vk_clean_device")
+            return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
+                    status.cpu().numpy().astype(np.uint32))
+        if len(adapters) != nsamples:
+            raise ValueError("one adapter triple per sample")
+        alen = np.zeros(3 * nsamples, dtype=np.uint32)
+        aseq = np.zeros((3 * nsamples, _capi.VK_CL_MAX_ADAPTER), dtype=np.uint8)
+        for j, triple in enumerate(adapters):
+            for g, a in enumerate(triple):
+                if a is None:
+                    continue
+                if not 0 < len(a) <= _capi.VK_CL_MAX_ADAPTER:
+                    raise ValueError(f"an adapter is 1..{_capi.VK_CL_MAX_ADAPTER} bytes: {a!r}")
+                alen[3 * j + g] = len(a)
+                aseq[3 * j + g, :len(a)] = np.frombuffer(bytes(a), dtype=np.uint8)
+        ad_stats = torch.empty((nsamples, 2), dtype=torch.int64, device=self.device)
+        st = self.L.vk_clean_adapters_device(*args, alen.ctypes.data_as(u32p), aseq.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             self._ptr(ad_stats))
+        _capi.check(self.ctx, st, "vk_clean_adapters_device")
         return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
-                status.cpu().numpy().astype(np.uint32))
+                status.cpu().numpy().astype(np.uint32), ad_stats.cpu().numpy().astype(np.uint64))
 
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""

@@ -400,12 +400,17 @@ def _budget(eng, dev, offs, lens, lines, sample_files, max_bp):
 
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
-                  batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None):
+                  batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
+                  detect_adapters=False):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
     leaving the device.  clean_dir: also write `<sample>.fq.gz` and `<sample>_fastp_gpu.json` (the content curves
     get_basefrequency_sd reads) there, as the reference's intermediate folder holds them.
+
+    adapters = (R1 and single reads' sequence, R2's sequence or None: the first) and detect_adapters: also trim by
+    sequence ("Step B"); an explicit sequence wins over detection for its groups, detection runs per
+    batch (ImageEngine.detect_adapters) after the read budget.  The JSON then holds `adapter_cutting`.
 
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
@@ -419,6 +424,13 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     from .engine import ImageEngine
     from .rawinput import content_curves, curves_sd
     labels, seeds = labels or {}, seeds or {}
+    by_sequence = adapters is not None or detect_adapters
+    if by_sequence and not adapter:
+        raise ValueError("adapters by sequence need adapter trimming (not -a)")
+    explicit = [None, None, None]
+    if adapters is not None:
+        a1, a2 = adapters
+        explicit = [a1, a2 if a2 is not None else a1, a1]
     plans = [(s, _sample_files(files)) for s, files in samples]
     if weights is None:   # (per sample: the sum of its files' weights; a collective when sharded)
         every = [f for _, sf in plans for f, _ in sf]
@@ -443,11 +455,14 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
         f = Path(f)
         return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
 
-    def write_clean(sample, text, curves):
+    def write_clean(sample, text, curves, cutting=None):
         with open(Path(clean_dir) / (sample + ".fq.gz"), "wb") as fh:
             fh.write(gzip.compress(text, compresslevel=1))
+        report = {"read1_after_filtering": {"content_curves": curves}}
+        if cutting is not None:
+            report["adapter_cutting"] = cutting
         with open(Path(clean_dir) / (sample + "_fastp_gpu.json"), "w") as fh:
-            json.dump({"read1_after_filtering": {"content_curves": curves}}, fh)
+            json.dump(report, fh)
 
     done = False
     try:   # (an error below must not leave the pool writing files into outdir behind the caller's back)
@@ -477,8 +492,16 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                 roles += [r for _, r in sf]
                 owner += [j] * len(sf)
                 at += len(sf)
-            out, ooffs, olens, cst, status = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
-                                                       adapter=adapter, merge=merge, dedup=dedup)
+            if by_sequence:
+                found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=trim[1])
+                         if detect_adapters else [[None] * 3 for _ in batch])
+                table = [[e if e is not None else d for e, d in zip(explicit, det)] for det in found]
+                out, ooffs, olens, cst, status, ast = eng.clean(dev, offs, lens, records, roles, owner, len(batch),
+                                                                trim=trim, adapter=adapter, merge=merge, dedup=dedup,
+                                                                adapters=table)
+            else:
+                out, ooffs, olens, cst, status = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
+                                                           adapter=adapter, merge=merge, dedup=dedup)
             del dev
             tc = time.perf_counter()
             ok = []
@@ -495,7 +518,13 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                 st["cleaning_time"] = (tc - t0) / len(batch)
                 if clean_dir is not None:
                     text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
-                    writes.append(pool.submit(write_clean, s, text, curves))
+                    cutting = None
+                    if by_sequence:
+                        name = [a.decode("latin-1") if a is not None else None for a in table[j]]
+                        cutting = {"read1_adapter_sequence": name[0], "read2_adapter_sequence": name[1],
+                                   "single_adapter_sequence": name[2], "adapter_trimmed_reads": int(ast[j][0]),
+                                   "adapter_trimmed_bases": int(ast[j][1])}
+                    writes.append(pool.submit(write_clean, s, text, curves, cutting))
                 ok.append(j)
             if ok:
                 _ladder_images(eng, out, ooffs[ok], olens[ok], [batch[j][0] for j in ok], [batch[j][0] for j in ok], tc,
