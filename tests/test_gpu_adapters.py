@@ -66,6 +66,31 @@ def test_detection_equals_reference(eng):
     assert want[3][:3] == [A.NEXTERA, SMALL_RNA, A.TRUSEQ1]
 
 
+def sliced_batch():
+    """12 samples with R1, R2 and single reads each: 36 groups with records, more than the 32 that detection takes per
+    slice, so its slice loop runs twice.  The second slice holds sample 10's single reads and sample 11; the adapters
+    rotate over the samples, so the groups on either side of the boundary differ."""
+    rota = [(A.TRUSEQ1, A.TRUSEQ2, A.NEXTERA), (A.NEXTERA, SMALL_RNA, A.TRUSEQ1), (SMALL_RNA, A.NEXTERA, A.TRUSEQ2)]
+    samples = []
+    for j in range(12):
+        a1, a2, a3 = rota[j % 3]
+        r1, r2 = A.pairs_with_adapters(60 + 2 * j, 3000, 0.3, adapter1=a1, adapter2=a2)
+        samples.append((r1, r2, A.se_readthrough(61 + 2 * j, 3000, 0.2, adapter=a3)))
+    return samples, [list(rota[j % 3]) for j in range(12)]
+
+
+def test_detection_over_two_slices(eng):
+    samples, planted = sliced_batch()
+    texts, roles, owner = layout(samples)
+    assert len(texts) == 36
+    dev, offs, lens = eng.upload(texts)
+    records = eng.clean_lines(dev, offs, lens) // 4
+    got = eng.detect_adapters(dev, offs, lens, records, roles, owner, len(samples), trim_tail=10)
+    want = [A.group_adapters(r1, r2, se, T=10) for r1, r2, se in samples]
+    assert got == want
+    assert want == planted
+
+
 def test_detection_unsnapped_and_tail(eng):
     """An unlisted dimer is accepted as its consensus; T changes the forward extension's reach."""
     samples = [([], [], A.dimers(31, 6000, 0.1)), ([], [], A.repeat_reads(32, 6000, 0.2)),

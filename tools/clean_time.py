@@ -85,19 +85,18 @@ def main():
     t_lines = time.perf_counter() - t
     recs = lines // 4
     roles, owner = ([_capi.VK_CL_ROLE_UNPAIRED], [0]) if a.single_end else ([_capi.VK_CL_ROLE_R1, _capi.VK_CL_ROLE_R2], [0, 0])
-    best, detect, extra = [], [], {}
+    best, detect, extra, found = [], [], {}, None
     for _ in range(a.reps):
         sync()
         t = time.perf_counter()
         if a.detect_adapters:
             found = eng.detect_adapters(dev, offs, lens, recs, roles, owner, 1)
             detect.append(time.perf_counter() - t)
-            out, oo, ol, st, status, ast = eng.clean(dev, offs, lens, recs, roles, owner, 1, adapters=found)
-        else:
-            out, oo, ol, st, status = eng.clean(dev, offs, lens, recs, roles, owner, 1)   # (waits for the kernels)
+        out, oo, ol, st, status, *rest = eng.clean(dev, offs, lens, recs, roles, owner, 1, adapters=found)   # (waits for the kernels)
         best.append(time.perf_counter() - t)
     assert not status.any(), status
     if a.detect_adapters:
+        ast = rest[0]
         extra = {"detect_s_best": min(detect), "detect_s_all": detect,
                  "adapters": [x.decode() if x is not None else None for x in found[0]],
                  "adapter_trimmed_reads": int(ast[0][0]), "adapter_trimmed_bases": int(ast[0][1])}

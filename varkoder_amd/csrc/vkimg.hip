@@ -1612,13 +1612,30 @@ namespace {
 
 size_t cl_align(size_t x) { return (x + 255) / 256 * 256; }
 
-// byte offsets of the pieces of a vk_clean_device workspace
+// Hands out the pieces of a workspace one after another, each at a multiple of 256 bytes.  A piece is stated once: the
+// typed pointer it fills and its element count.  Without a base only the sizes add up (the *_workspace_size calls).
+struct ClTake {
+    uint8_t* base;
+    size_t at;
+    template <class T> void operator()(T*& piece, size_t count) {
+        piece = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += cl_align(count * sizeof(T));
+    }
+};
+
+// the pieces of a vk_clean_device workspace
 struct ClLayout {
-    size_t files, fchunk, samples, unit_base, ccount, cprefix, sums, recs, hashes, slot_of, plans, obytes, oprefix, table, total;
+    ClFile* files;
+    uint64_t *fchunk, *unit_base, *ccount, *cprefix, *sums, *hashes, *obytes, *oprefix;
+    ClSample* samples;
+    ClRec* recs;
+    ClPlan* plans;
+    uint32_t *slot_of, *table;
+    size_t total;
     uint64_t nchunks, nrec, nslots;
 };
 
-ClLayout cl_layout(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
+ClLayout cl_layout(void* d_ws, const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
     ClLayout L{};
     for (uint32_t i = 0; i < nfiles; ++i) {
         L.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
@@ -1627,23 +1644,51 @@ ClLayout cl_layout(const uint64_t* lengths, const uint64_t* records, uint32_t nf
     L.nslots = 1024;
     while (L.nslots < 2 * L.nrec) L.nslots <<= 1;
     const uint64_t nb = std::max((L.nchunks + kClScanBlock - 1) / kClScanBlock, (L.nrec + kClScanBlock - 1) / kClScanBlock);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += cl_align(bytes); return o; };
-    L.files = take(nfiles * sizeof(ClFile));
-    L.fchunk = take(nfiles * 8ull);
-    L.samples = take(nsamples * sizeof(ClSample));
-    L.unit_base = take((nsamples + 1ull) * 8);
-    L.ccount = take(L.nchunks * 8);
-    L.cprefix = take((L.nchunks + 1) * 8);
-    L.sums = take((nb + 1) * 8);
-    L.recs = take(L.nrec * sizeof(ClRec));
-    L.hashes = take(L.nrec * 8);
-    L.slot_of = take(L.nrec * 4);
-    L.plans = take(L.nrec * sizeof(ClPlan));
-    L.obytes = take(L.nrec * 8);
-    L.oprefix = take((L.nrec + 1) * 8);
-    L.table = take(L.nslots * 8);
-    L.total = at;
+    ClTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.files, nfiles);
+    take(L.fchunk, nfiles);
+    take(L.samples, nsamples);
+    take(L.unit_base, nsamples + 1ull);
+    take(L.ccount, L.nchunks);
+    take(L.cprefix, L.nchunks + 1);
+    take(L.sums, nb + 1);
+    take(L.recs, L.nrec);
+    take(L.hashes, L.nrec);
+    take(L.slot_of, L.nrec);
+    take(L.plans, L.nrec);
+    take(L.obytes, L.nrec);
+    take(L.oprefix, L.nrec + 1);
+    take(L.table, 2 * L.nslots);   // (a slot is two words)
+    L.total = take.at;
+    return L;
+}
+
+// the pieces of a vk_clean_detect_device workspace: the record index of vk_clean_device's layout, then a slice's tables
+struct AdLayout {
+    ClLayout c;
+    uint32_t *hist, *counts;
+    AdGroup* groups;
+    uint64_t *gbase, *ranked, *totals;
+    AdCand* cands;
+    AdExt* ext;
+    size_t total;
+    uint32_t slice;
+};
+
+AdLayout ad_layout(void* d_ws, const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
+    AdLayout L{};
+    L.c = cl_layout(d_ws, lengths, records, nfiles, nsamples);
+    L.slice = static_cast<uint32_t>(std::min<uint64_t>(kAdSlice, 3ull * nsamples));
+    ClTake take{static_cast<uint8_t*>(d_ws), L.c.total};
+    take(L.hist, static_cast<size_t>(L.slice) * kAdKeys);
+    take(L.groups, L.slice);
+    take(L.gbase, L.slice + 1ull);
+    take(L.ranked, L.slice * kAdTop);
+    take(L.totals, L.slice);
+    take(L.cands, L.slice * kAdTop);
+    take(L.counts, L.slice * kAdTop);
+    take(L.ext, L.slice * kAdTop);
+    L.total = take.at;
     return L;
 }
 
@@ -1658,6 +1703,229 @@ int cl_scan(vk_ctx* ctx, const uint64_t* in, uint64_t n, uint64_t* sums, uint64_
     return VK_OK;
 }
 
+uint32_t cl_rank(uint32_t role) { return role == VK_CL_ROLE_UNPAIRED ? 2u : role - 1u; }   // a file's group: R1, R2, single reads
+
+// the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order (no roles: the caller's)
+std::vector<uint32_t> cl_order(const uint32_t* roles, const uint32_t* samples, uint32_t nfiles) {
+    std::vector<uint32_t> order(nfiles);
+    for (uint32_t i = 0; i < nfiles; ++i) order[i] = i;
+    if (roles)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            return samples[a] != samples[b] ? samples[a] < samples[b] : cl_rank(roles[a]) < cl_rank(roles[b]);
+        });
+    return order;
+}
+
+// The record index of a launch as the host states it: the file tables that the kernels read and, per group
+// (3 * sample + cl_rank), the ordinal of its first record and the records it gives.
+struct ClIndex {
+    std::vector<ClFile> files;
+    std::vector<uint64_t> fchunk, first, count;
+    uint64_t nchunks = 0, nrec = 0;
+};
+
+// A file gives its budget records[i], the files of a group no more than group_cap between them (detection's evaluation
+// set: a group's first kAdEval records, in the order of its files).  Without records (vk_clean_lines_device) the files
+// stay in the caller's order and nothing is indexed.
+ClIndex cl_index(const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records, const uint32_t* roles,
+                 const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint64_t group_cap) {
+    ClIndex ix;
+    ix.files.resize(nfiles);
+    ix.fchunk.resize(nfiles);
+    ix.first.assign(3ull * nsamples, 0);
+    ix.count.assign(3ull * nsamples, 0);
+    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
+    for (uint32_t j = 0; j < nfiles; ++j) {
+        const uint32_t i = order[j];
+        uint64_t n = 0;
+        if (records) {
+            const uint64_t g = 3ull * samples[i] + cl_rank(roles[i]);
+            n = std::min(records[i], group_cap - ix.count[g]);
+            // (a group's files are adjacent and those ahead of its first record give none, so this is the ordinal at the
+            // group's first file as well; a group without files keeps 0)
+            if (ix.count[g] == 0) ix.first[g] = ix.nrec;
+            ix.count[g] += n;
+        }
+        ix.files[j] = ClFile{offsets[i], lengths[i], n, ix.nrec, ix.nchunks};
+        ix.fchunk[j] = ix.nchunks;
+        ix.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        ix.nrec += n;
+    }
+    return ix;
+}
+
+// Uploads the index's tables and has the GPU find every record's line ends.  The sample rows and the stats and status
+// words that the init kernel resets are vk_clean_device's; detection has none (nulls, nsamples 0).
+int cl_index_run(vk_ctx* ctx, const uint8_t* text, const ClIndex& ix, const ClLayout& L, const ClSample* dsmp, uint32_t nsamples,
+                 uint64_t* d_stats, uint32_t* d_status) {
+    const uint32_t nfiles = static_cast<uint32_t>(ix.files.size());
+    if (nfiles) {
+        VK_HIP(ctx, hipMemcpyAsync(L.files, ix.files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.fchunk, ix.fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (ix.nrec) VK_HIP(ctx, hipMemsetAsync(L.recs, 0xFF, ix.nrec * sizeof(ClRec), ctx->stream));
+    const uint32_t ninit = std::max(nsamples, nfiles);
+    hipLaunchKernelGGL(vk_cl_init_kernel, dim3((ninit + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, dsmp,
+                       nsamples, L.files, nfiles, L.recs, d_stats, d_stats ? static_cast<uint32_t>(VK_CL_NSTAT) : 0u, d_status);
+    if (ix.nchunks) {
+        hipLaunchKernelGGL(vk_cl_nl_count_kernel, dim3(ix.nchunks), dim3(kClThreads), 0, ctx->stream, text, L.files, L.fchunk,
+                           nfiles, L.ccount);
+        int rc = cl_scan(ctx, L.ccount, ix.nchunks, L.sums, L.cprefix);
+        if (rc) return rc;
+        hipLaunchKernelGGL(vk_cl_nl_write_kernel, dim3(ix.nchunks), dim3(kClThreads), 0, ctx->stream, text, L.files, L.fchunk,
+                           nfiles, L.cprefix, L.recs);
+    }
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// what vk_clean_device and vk_clean_detect_device ask of the arguments they share
+int cl_check(const vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+             const uint32_t* roles, const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint32_t trim_tail,
+             const void* d_ws) {
+    if (!ctx || nsamples == 0 || !d_ws || trim_tail > (1u << 30)) return VK_EINVAL;
+    if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
+    uint64_t nrec = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
+        nrec += records[i];
+    }
+    return nrec >= kClEmpty ? VK_EINVAL : VK_OK;   // (the dedup table holds unit ordinals as 32-bit words, kClEmpty for a free slot)
+}
+
+// an adapter triple table as the clean kernel reads it: each sequence's bytes, 2-bit codes and non-ACGT marks
+std::vector<ClAdapter> ad_pack(const uint32_t* ad_lengths, const uint8_t* ad_seqs, uint64_t ngroups) {
+    std::vector<ClAdapter> ads(ngroups);
+    for (uint64_t g = 0; g < ngroups; ++g) {
+        ClAdapter& d = ads[g];
+        d = ClAdapter{};
+        d.len = ad_lengths[g];
+        for (uint32_t i = 0; i < d.len; ++i) {
+            const uint8_t b = ad_seqs[g * kAdMaxAdapter + i];
+            const uint64_t c = (b >> 1) & 3u, bad = (b == 'A' || b == 'C' || b == 'G' || b == 'T') ? 0u : 1u;
+            d.seq[i] = b;
+            (i < 32 ? d.lo : d.hi) |= c << (2 * (i % 32));
+            (i < 32 ? d.nlo : d.nhi) |= bad << (2 * (i % 32));
+        }
+    }
+    return ads;
+}
+
+// A slice's candidates: ranked keys with count * 4^10 / total > 20; each gets room for `count` occurrences (the
+// extension's positions are a part of the counted ones).  Returns the room of all.
+uint64_t ad_candidates(const std::vector<uint64_t>& ranked, const std::vector<uint64_t>& totals, std::vector<AdCand>& cand) {
+    uint64_t nocc = 0;
+    for (size_t k = 0; k < totals.size(); ++k)
+        for (uint32_t c = 0; c < kAdTop; ++c) {
+            const uint64_t v = ranked[k * kAdTop + c], cnt = v >> 20;
+            AdCand& d = cand[k * kAdTop + c];
+            d = AdCand{static_cast<uint32_t>(kAdKeys - 1 - (v & (kAdKeys - 1))), 0, nocc};
+            if (v && totals[k] && cnt * kAdKeys / totals[k] > kAdFold) {
+                d.cap = static_cast<uint32_t>(cnt);
+                nocc += cnt;
+            }
+        }
+    return nocc;
+}
+
+// D = reverse(backward) + seed + forward, its first kAdMaxLen bytes
+std::string ad_detected(const AdExt& e, uint32_t key) {
+    std::string d;
+    const uint32_t nb = std::min(e.nb, kAdMaxLen);
+    for (uint32_t i = 0; i < nb; ++i) d += static_cast<char>(e.back[(e.nb - 1 - i) % kAdKeep]);
+    for (uint32_t i = 0; i < kAdK; ++i) d += "ACGT"[(key >> (2 * (kAdK - 1 - i))) & 3u];
+    for (uint32_t i = 0; i < std::min(e.nf, kAdKeep); ++i) d += static_cast<char>(e.fwd[i]);
+    if (d.size() > kAdMaxLen) d.resize(kAdMaxLen);
+    return d;
+}
+
+// what an extension is accepted as: the listed adapter D snaps to, else D when both directions ran out, else nothing
+std::string ad_accept(const AdExt& e, uint32_t key) {
+    const std::string D = ad_detected(e, key);
+    for (const char* known : kAdKnown) {
+        const std::string ad(known);
+        if (D.find(ad.substr(0, kAdSnap)) != std::string::npos) return ad;
+    }
+    return (e.flags & 3u) == 3u ? D : std::string();
+}
+
+// vk_clean_device, and with ad_lengths vk_clean_adapters_device
+int cl_clean(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+             const uint32_t* roles, const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint32_t trim_front,
+             uint32_t trim_tail, uint32_t flags, void* d_ws, uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets,
+             uint64_t out_bytes, uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* ad_lengths,
+             const uint8_t* ad_seqs, uint64_t* d_ad_stats) {
+    if (!out_offsets || !d_out || !d_out_lengths || !d_stats || !d_status) return VK_EINVAL;
+    if ((flags & ~(VK_CL_ADAPTER | VK_CL_MERGE | VK_CL_DEDUP)) || trim_front > (1u << 30)) return VK_EINVAL;
+    int rc = cl_check(ctx, d_text, offsets, lengths, records, roles, samples, nfiles, nsamples, trim_tail, d_ws);
+    if (rc) return rc;
+    const ClLayout L = cl_layout(d_ws, lengths, records, nfiles, nsamples);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles, samples, nfiles, nsamples, ~0ull);
+    std::vector<uint64_t> cap(nsamples, 0), unit_base(nsamples + 1ull, 0);
+    for (uint32_t i = 0; i < nfiles; ++i) cap[samples[i]] += lengths[i];
+    std::vector<ClSample> smp(nsamples);
+    for (uint32_t s = 0; s < nsamples; ++s) {
+        const uint64_t *first = &ix.first[3ull * s], *cnt = &ix.count[3ull * s];
+        ClSample& d = smp[s];
+        d.r1 = first[0];
+        d.r2 = first[1];
+        d.se = first[2];
+        d.flags = cnt[0] != cnt[1] ? VK_CL_RAGGED : 0u;
+        d.npairs = d.flags ? 0 : cnt[0];
+        d.nse = d.flags ? 0 : cnt[2];
+        d.out_off = out_offsets[s];
+        d.out_cap = cap[s];
+        if (out_offsets[s] % 16 || out_offsets[s] + (cap[s] + 15) / 16 * 16 > out_bytes) return VK_EINVAL;
+        unit_base[s + 1] = unit_base[s] + d.npairs + d.nse;
+    }
+    const uint64_t nunits = unit_base[nsamples];
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const ClAdapter* dads = nullptr;
+    if (ad_lengths) {   // the adapter table in a buffer of the context
+        const std::vector<ClAdapter> ads = ad_pack(ad_lengths, ad_seqs, 3ull * nsamples);
+        rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cladapt), &ctx->cladapt_cap, ads.size() * sizeof(ClAdapter));
+        if (rc) return rc;
+        VK_HIP(ctx, hipMemcpyAsync(ctx->d_cladapt, ads.data(), ads.size() * sizeof(ClAdapter), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_ad_stats, 0, 2ull * nsamples * sizeof(uint64_t), ctx->stream));
+        dads = reinterpret_cast<const ClAdapter*>(ctx->d_cladapt);
+    }
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(ClSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.unit_base, unit_base.data(), (nsamples + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (flags & VK_CL_DEDUP) VK_HIP(ctx, hipMemsetAsync(L.table, 0xFF, L.nslots * 8, ctx->stream));
+    rc = cl_index_run(ctx, text, ix, L, L.samples, nsamples, d_stats, d_status);
+    if (rc) return rc;
+    const uint64_t ug = (nunits + kClThreads - 1) / kClThreads;
+    const uint64_t hash_mask = ctx->clean_hash_bits >= 64 ? ~0ull : ((1ull << ctx->clean_hash_bits) - 1);
+    if (nunits) {
+        hipLaunchKernelGGL(vk_cl_hash_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.unit_base, nsamples,
+                           nunits, L.recs, hash_mask, L.hashes, d_status);
+        if (flags & VK_CL_DEDUP)
+            hipLaunchKernelGGL(vk_cl_dedup_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.unit_base,
+                               nsamples, nunits, L.recs, L.hashes, d_status, L.table, L.nslots - 1, L.slot_of);
+        if (dads)
+            hipLaunchKernelGGL(vk_cl_clean_kernel<true>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.unit_base,
+                               nsamples, nunits, L.recs, d_status, L.table, L.slot_of, trim_front, trim_tail, flags, L.plans,
+                               L.obytes, dads, d_ad_stats);
+        else
+            hipLaunchKernelGGL(vk_cl_clean_kernel<false>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.unit_base,
+                               nsamples, nunits, L.recs, d_status, L.table, L.slot_of, trim_front, trim_tail, flags, L.plans,
+                               L.obytes, static_cast<const ClAdapter*>(nullptr), static_cast<uint64_t*>(nullptr));
+    }
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.obytes, nunits, L.sums, L.oprefix);
+    if (rc) return rc;
+    if (nunits)
+        hipLaunchKernelGGL(vk_cl_write_kernel, dim3((nunits + kClUnitsPerBlock - 1) / kClUnitsPerBlock), dim3(kClThreads), 0,
+                           ctx->stream, text, L.samples, L.unit_base, nsamples, nunits, L.recs, L.plans, L.oprefix, d_out,
+                           d_stats, static_cast<uint32_t>(VK_CL_NSTAT));
+    hipLaunchKernelGGL(vk_cl_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, L.samples, L.unit_base, nsamples,
+                       L.oprefix, d_status, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1666,27 +1934,21 @@ int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
                           uint32_t nfiles, uint64_t* lines) {
     if (!ctx || !offsets || !lengths || !lines || (nfiles && !d_text)) return VK_EINVAL;
     if (nfiles == 0) return VK_OK;
-    std::vector<ClFile> files(nfiles);
-    std::vector<uint64_t> fchunk(nfiles);
-    uint64_t nchunks = 0;
-    for (uint32_t i = 0; i < nfiles; ++i) {
+    for (uint32_t i = 0; i < nfiles; ++i)
         if (offsets[i] % 16) return VK_EINVAL;
-        files[i] = ClFile{offsets[i], lengths[i], 0, 0, nchunks};
-        fchunk[i] = nchunks;
-        nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-    }
+    const ClIndex ix = cl_index(offsets, lengths, nullptr, nullptr, nullptr, nfiles, 0, 0);
     VK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t o_chunk = cl_align(nfiles * sizeof(ClFile)), o_lines = o_chunk + cl_align(nfiles * 8ull);
     int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, o_lines + nfiles * 8ull);
     if (rc) return rc;
     uint8_t* m = ctx->d_clines;
-    VK_HIP(ctx, hipMemcpyAsync(m, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(m + o_chunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(m, ix.files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(m + o_chunk, ix.fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipMemsetAsync(m + o_lines, 0, nfiles * 8ull, ctx->stream));
-    if (nchunks)
-        hipLaunchKernelGGL(vk_cl_lines_kernel, dim3(nchunks), dim3(kClThreads), 0, ctx->stream, static_cast<const uint8_t*>(d_text),
-                           reinterpret_cast<const ClFile*>(m), reinterpret_cast<const uint64_t*>(m + o_chunk), nfiles,
-                           reinterpret_cast<unsigned long long*>(m + o_lines));
+    if (ix.nchunks)
+        hipLaunchKernelGGL(vk_cl_lines_kernel, dim3(ix.nchunks), dim3(kClThreads), 0, ctx->stream,
+                           static_cast<const uint8_t*>(d_text), reinterpret_cast<const ClFile*>(m),
+                           reinterpret_cast<const uint64_t*>(m + o_chunk), nfiles, reinterpret_cast<unsigned long long*>(m + o_lines));
     VK_HIP(ctx, hipGetLastError());
     VK_HIP(ctx, hipMemcpyAsync(lines, m + o_lines, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1696,161 +1958,9 @@ int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
 int vk_clean_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
                             uint64_t* bytes) {
     if (!bytes || (nfiles && (!lengths || !records))) return VK_EINVAL;
-    *bytes = cl_layout(lengths, records, nfiles, nsamples).total;
+    *bytes = cl_layout(nullptr, lengths, records, nfiles, nsamples).total;
     return VK_OK;
 }
-
-}  // extern "C"
-
-namespace {
-
-uint32_t cl_rank(uint32_t role) { return role == VK_CL_ROLE_UNPAIRED ? 2u : role - 1u; }   // a file's group: R1, R2, single reads
-
-// the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order
-std::vector<uint32_t> cl_order(const uint32_t* roles, const uint32_t* samples, uint32_t nfiles) {
-    std::vector<uint32_t> order(nfiles);
-    for (uint32_t i = 0; i < nfiles; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return samples[a] != samples[b] ? samples[a] < samples[b] : cl_rank(roles[a]) < cl_rank(roles[b]);
-    });
-    return order;
-}
-
-// vk_clean_device, and with ad_lengths vk_clean_adapters_device
-int cl_clean(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
-             const uint32_t* roles, const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint32_t trim_front,
-             uint32_t trim_tail, uint32_t flags, void* d_ws, uint64_t ws_bytes, uint8_t* d_out, const uint64_t* out_offsets,
-             uint64_t out_bytes, uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* ad_lengths,
-             const uint8_t* ad_seqs, uint64_t* d_ad_stats) {
-    if (!ctx || nsamples == 0 || !out_offsets || !d_out || !d_out_lengths || !d_stats || !d_status || !d_ws) return VK_EINVAL;
-    if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
-    if (flags & ~(VK_CL_ADAPTER | VK_CL_MERGE | VK_CL_DEDUP)) return VK_EINVAL;
-    if (trim_front > (1u << 30) || trim_tail > (1u << 30)) return VK_EINVAL;
-    const ClLayout L = cl_layout(lengths, records, nfiles, nsamples);
-    if (ws_bytes < L.total || L.nrec >= kClEmpty) return VK_EINVAL;
-    for (uint32_t i = 0; i < nfiles; ++i)
-        if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
-    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
-    std::vector<ClFile> files(nfiles);
-    std::vector<uint64_t> fchunk(nfiles);
-    std::vector<ClSample> smp(nsamples);
-    std::vector<uint64_t> cnt(3ull * nsamples, 0), first(3ull * nsamples, ~0ull), cap(nsamples, 0);
-    uint64_t chunk = 0, rec = 0;
-    for (uint32_t j = 0; j < nfiles; ++j) {
-        const uint32_t i = order[j], s = samples[i], g = cl_rank(roles[i]);
-        files[j] = ClFile{offsets[i], lengths[i], records[i], rec, chunk};
-        fchunk[j] = chunk;
-        chunk += (lengths[i] + kClChunk - 1) / kClChunk;
-        if (first[3ull * s + g] == ~0ull) first[3ull * s + g] = rec;
-        cnt[3ull * s + g] += records[i];
-        rec += records[i];
-        cap[s] += lengths[i];
-    }
-    std::vector<uint64_t> unit_base(nsamples + 1ull, 0);
-    for (uint32_t s = 0; s < nsamples; ++s) {
-        ClSample& d = smp[s];
-        d.r1 = first[3ull * s] == ~0ull ? 0 : first[3ull * s];
-        d.r2 = first[3ull * s + 1] == ~0ull ? 0 : first[3ull * s + 1];
-        d.se = first[3ull * s + 2] == ~0ull ? 0 : first[3ull * s + 2];
-        d.flags = cnt[3ull * s] != cnt[3ull * s + 1] ? VK_CL_RAGGED : 0u;
-        d.npairs = d.flags ? 0 : cnt[3ull * s];
-        d.nse = d.flags ? 0 : cnt[3ull * s + 2];
-        d.out_off = out_offsets[s];
-        d.out_cap = cap[s];
-        if (out_offsets[s] % 16 || out_offsets[s] + (cap[s] + 15) / 16 * 16 > out_bytes) return VK_EINVAL;
-        unit_base[s + 1] = unit_base[s] + d.npairs + d.nse;
-    }
-    const uint64_t nunits = unit_base[nsamples];
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    const ClAdapter* dads = nullptr;
-    if (ad_lengths) {   // the adapter table as 2-bit codes, in a buffer of the context
-        std::vector<ClAdapter> ads(3ull * nsamples);
-        for (uint64_t g = 0; g < ads.size(); ++g) {
-            ClAdapter& d = ads[g];
-            d = ClAdapter{};
-            d.len = ad_lengths[g];
-            for (uint32_t i = 0; i < d.len; ++i) {
-                const uint8_t b = ad_seqs[g * kAdMaxAdapter + i];
-                const uint64_t c = (b >> 1) & 3u, bad = (b == 'A' || b == 'C' || b == 'G' || b == 'T') ? 0u : 1u;
-                d.seq[i] = b;
-                (i < 32 ? d.lo : d.hi) |= c << (2 * (i % 32));
-                (i < 32 ? d.nlo : d.nhi) |= bad << (2 * (i % 32));
-            }
-        }
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cladapt), &ctx->cladapt_cap, ads.size() * sizeof(ClAdapter));
-        if (rc) return rc;
-        VK_HIP(ctx, hipMemcpyAsync(ctx->d_cladapt, ads.data(), ads.size() * sizeof(ClAdapter), hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemsetAsync(d_ad_stats, 0, 2ull * nsamples * sizeof(uint64_t), ctx->stream));
-        dads = reinterpret_cast<const ClAdapter*>(ctx->d_cladapt);
-    }
-    uint8_t* w = static_cast<uint8_t*>(d_ws);
-    auto* dfiles = reinterpret_cast<ClFile*>(w + L.files);
-    auto* dfchunk = reinterpret_cast<uint64_t*>(w + L.fchunk);
-    auto* dsmp = reinterpret_cast<ClSample*>(w + L.samples);
-    auto* dub = reinterpret_cast<uint64_t*>(w + L.unit_base);
-    auto* ccount = reinterpret_cast<uint64_t*>(w + L.ccount);
-    auto* cprefix = reinterpret_cast<uint64_t*>(w + L.cprefix);
-    auto* sums = reinterpret_cast<uint64_t*>(w + L.sums);
-    auto* recs = reinterpret_cast<ClRec*>(w + L.recs);
-    auto* hashes = reinterpret_cast<uint64_t*>(w + L.hashes);
-    auto* slot_of = reinterpret_cast<uint32_t*>(w + L.slot_of);
-    auto* plans = reinterpret_cast<ClPlan*>(w + L.plans);
-    auto* obytes = reinterpret_cast<uint64_t*>(w + L.obytes);
-    auto* oprefix = reinterpret_cast<uint64_t*>(w + L.oprefix);
-    auto* table = reinterpret_cast<uint32_t*>(w + L.table);
-    const auto* text = static_cast<const uint8_t*>(d_text);
-    if (nfiles) {
-        VK_HIP(ctx, hipMemcpyAsync(dfiles, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(dfchunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    }
-    VK_HIP(ctx, hipMemcpyAsync(dsmp, smp.data(), nsamples * sizeof(ClSample), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(dub, unit_base.data(), (nsamples + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (L.nrec) VK_HIP(ctx, hipMemsetAsync(recs, 0xFF, L.nrec * sizeof(ClRec), ctx->stream));
-    if (flags & VK_CL_DEDUP) VK_HIP(ctx, hipMemsetAsync(table, 0xFF, L.nslots * 8, ctx->stream));
-    const uint32_t ninit = std::max(nsamples, nfiles);
-    hipLaunchKernelGGL(vk_cl_init_kernel, dim3((ninit + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
-                       dsmp, nsamples, dfiles, nfiles, recs, d_stats, static_cast<uint32_t>(VK_CL_NSTAT), d_status);
-    if (L.nchunks) {
-        hipLaunchKernelGGL(vk_cl_nl_count_kernel, dim3(L.nchunks), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
-                           nfiles, ccount);
-        int rc = cl_scan(ctx, ccount, L.nchunks, sums, cprefix);
-        if (rc) return rc;
-        hipLaunchKernelGGL(vk_cl_nl_write_kernel, dim3(L.nchunks), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
-                           nfiles, cprefix, recs);
-    }
-    const uint64_t ug = (nunits + kClThreads - 1) / kClThreads;
-    const uint64_t hash_mask = ctx->clean_hash_bits >= 64 ? ~0ull : ((1ull << ctx->clean_hash_bits) - 1);
-    if (nunits) {
-        hipLaunchKernelGGL(vk_cl_hash_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples, nunits,
-                           recs, hash_mask, hashes, d_status);
-        if (flags & VK_CL_DEDUP)
-            hipLaunchKernelGGL(vk_cl_dedup_kernel, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
-                               nunits, recs, hashes, d_status, table, L.nslots - 1, slot_of);
-        if (dads)
-            hipLaunchKernelGGL(vk_cl_clean_kernel<true>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
-                               nunits, recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes, dads,
-                               d_ad_stats);
-        else
-            hipLaunchKernelGGL(vk_cl_clean_kernel<false>, dim3(ug), dim3(kClThreads), 0, ctx->stream, text, dsmp, dub, nsamples,
-                               nunits, recs, d_status, table, slot_of, trim_front, trim_tail, flags, plans, obytes,
-                               static_cast<const ClAdapter*>(nullptr), static_cast<uint64_t*>(nullptr));
-    }
-    VK_HIP(ctx, hipGetLastError());
-    int rc = cl_scan(ctx, obytes, nunits, sums, oprefix);
-    if (rc) return rc;
-    if (nunits)
-        hipLaunchKernelGGL(vk_cl_write_kernel, dim3((nunits + kClUnitsPerBlock - 1) / kClUnitsPerBlock), dim3(kClThreads), 0,
-                           ctx->stream, text, dsmp, dub, nsamples, nunits, recs, plans, oprefix, d_out, d_stats,
-                           static_cast<uint32_t>(VK_CL_NSTAT));
-    hipLaunchKernelGGL(vk_cl_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, dsmp, dub, nsamples, oprefix,
-                       d_status, d_out, d_out_lengths);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
                     const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
@@ -1875,55 +1985,10 @@ int vk_clean_adapters_device(vk_ctx* ctx, const void* d_text, const uint64_t* of
                     adapter_seqs, d_adapter_stats);
 }
 
-}  // extern "C"
-
-namespace {
-
-// byte offsets of the pieces of a vk_clean_detect_device workspace: the record index of vk_clean_device's layout, then
-// a slice's tables
-struct AdLayout {
-    ClLayout c;
-    size_t hist, groups, gbase, ranked, totals, cands, counts, ext, total;
-    uint32_t slice;
-};
-
-AdLayout ad_layout(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
-    AdLayout L{};
-    L.c = cl_layout(lengths, records, nfiles, nsamples);
-    L.slice = static_cast<uint32_t>(std::min<uint64_t>(kAdSlice, 3ull * nsamples));
-    size_t at = L.c.total;
-    auto take = [&](size_t bytes) { const size_t o = at; at += cl_align(bytes); return o; };
-    L.hist = take(static_cast<size_t>(L.slice) * kAdKeys * 4);
-    L.groups = take(L.slice * sizeof(AdGroup));
-    L.gbase = take((L.slice + 1ull) * 8);
-    L.ranked = take(L.slice * kAdTop * 8ull);
-    L.totals = take(L.slice * 8ull);
-    L.cands = take(L.slice * kAdTop * sizeof(AdCand));
-    L.counts = take(L.slice * kAdTop * 4ull);
-    L.ext = take(L.slice * kAdTop * sizeof(AdExt));
-    L.total = at;
-    return L;
-}
-
-// D = reverse(backward) + seed + forward, its first kAdMaxLen bytes
-std::string ad_detected(const AdExt& e, uint32_t key) {
-    std::string d;
-    const uint32_t nb = std::min(e.nb, kAdMaxLen);
-    for (uint32_t i = 0; i < nb; ++i) d += static_cast<char>(e.back[(e.nb - 1 - i) % kAdKeep]);
-    for (uint32_t i = 0; i < kAdK; ++i) d += "ACGT"[(key >> (2 * (kAdK - 1 - i))) & 3u];
-    for (uint32_t i = 0; i < std::min(e.nf, kAdKeep); ++i) d += static_cast<char>(e.fwd[i]);
-    if (d.size() > kAdMaxLen) d.resize(kAdMaxLen);
-    return d;
-}
-
-}  // namespace
-
-extern "C" {
-
 int vk_clean_detect_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
                                    uint64_t* bytes) {
     if (!bytes || (nfiles && (!lengths || !records))) return VK_EINVAL;
-    *bytes = ad_layout(lengths, records, nfiles, nsamples).total;
+    *bytes = ad_layout(nullptr, lengths, records, nfiles, nsamples).total;
     return VK_OK;
 }
 
@@ -1931,134 +1996,68 @@ int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offs
                            const uint64_t* records, const uint32_t* roles, const uint32_t* samples, uint32_t nfiles,
                            uint32_t nsamples, uint32_t trim_tail, void* d_ws, uint64_t ws_bytes, uint32_t* adapter_lengths,
                            uint8_t* adapter_seqs) {
-    if (!ctx || nsamples == 0 || !d_ws || !adapter_lengths || !adapter_seqs) return VK_EINVAL;
-    if (nfiles && (!d_text || !offsets || !lengths || !records || !roles || !samples)) return VK_EINVAL;
-    if (trim_tail > (1u << 30)) return VK_EINVAL;
-    const AdLayout L = ad_layout(lengths, records, nfiles, nsamples);
-    if (ws_bytes < L.total || L.c.nrec >= kClEmpty) return VK_EINVAL;
-    for (uint32_t i = 0; i < nfiles; ++i)
-        if (samples[i] >= nsamples || roles[i] > VK_CL_ROLE_R2 || offsets[i] % 16) return VK_EINVAL;
+    if (!adapter_lengths || !adapter_seqs) return VK_EINVAL;
+    int rc = cl_check(ctx, d_text, offsets, lengths, records, roles, samples, nfiles, nsamples, trim_tail, d_ws);
+    if (rc) return rc;
+    const AdLayout L = ad_layout(d_ws, lengths, records, nfiles, nsamples);
+    if (ws_bytes < L.total) return VK_EINVAL;
     const uint64_t ngroups = 3ull * nsamples;
     std::fill(adapter_lengths, adapter_lengths + ngroups, 0u);
     std::fill(adapter_seqs, adapter_seqs + ngroups * kAdMaxAdapter, uint8_t{0});
     // the index holds each group's evaluation set: its first kAdEval records, in the order of its files
-    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
-    std::vector<ClFile> files(nfiles);
-    std::vector<uint64_t> fchunk(nfiles), taken(ngroups, 0), first(ngroups, 0);
-    uint64_t chunk = 0, rec = 0;
-    for (uint32_t j = 0; j < nfiles; ++j) {
-        const uint32_t i = order[j];
-        const uint64_t g = 3ull * samples[i] + cl_rank(roles[i]);
-        const uint64_t n = std::min<uint64_t>(records[i], kAdEval - taken[g]);
-        if (taken[g] == 0) first[g] = rec;
-        files[j] = ClFile{offsets[i], lengths[i], n, rec, chunk};
-        fchunk[j] = chunk;
-        chunk += (lengths[i] + kClChunk - 1) / kClChunk;
-        taken[g] += n;
-        rec += n;
-    }
+    const ClIndex ix = cl_index(offsets, lengths, records, roles, samples, nfiles, nsamples, kAdEval);
     std::vector<uint64_t> active;   // groups with records
     for (uint64_t g = 0; g < ngroups; ++g)
-        if (taken[g]) active.push_back(g);
+        if (ix.count[g]) active.push_back(g);
     if (active.empty()) return VK_OK;
     VK_HIP(ctx, hipSetDevice(ctx->device));
-    uint8_t* w = static_cast<uint8_t*>(d_ws);
-    auto* dfiles = reinterpret_cast<ClFile*>(w + L.c.files);
-    auto* dfchunk = reinterpret_cast<uint64_t*>(w + L.c.fchunk);
-    auto* ccount = reinterpret_cast<uint64_t*>(w + L.c.ccount);
-    auto* cprefix = reinterpret_cast<uint64_t*>(w + L.c.cprefix);
-    auto* sums = reinterpret_cast<uint64_t*>(w + L.c.sums);
-    auto* recs = reinterpret_cast<ClRec*>(w + L.c.recs);
-    auto* hist = reinterpret_cast<uint32_t*>(w + L.hist);
-    auto* dgroups = reinterpret_cast<AdGroup*>(w + L.groups);
-    auto* gbase = reinterpret_cast<uint64_t*>(w + L.gbase);
-    auto* ranked = reinterpret_cast<uint64_t*>(w + L.ranked);
-    auto* totals = reinterpret_cast<uint64_t*>(w + L.totals);
-    auto* dcands = reinterpret_cast<AdCand*>(w + L.cands);
-    auto* counts = reinterpret_cast<uint32_t*>(w + L.counts);
-    auto* dext = reinterpret_cast<AdExt*>(w + L.ext);
     const auto* text = static_cast<const uint8_t*>(d_text);
-    VK_HIP(ctx, hipMemcpyAsync(dfiles, files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(dfchunk, fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(recs, 0xFF, rec * sizeof(ClRec), ctx->stream));
-    hipLaunchKernelGGL(vk_cl_init_kernel, dim3((nfiles + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
-                       static_cast<const ClSample*>(nullptr), 0u, dfiles, nfiles, recs, static_cast<uint64_t*>(nullptr), 0u,
-                       static_cast<uint32_t*>(nullptr));
-    if (chunk) {
-        hipLaunchKernelGGL(vk_cl_nl_count_kernel, dim3(chunk), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk, nfiles,
-                           ccount);
-        int rc = cl_scan(ctx, ccount, chunk, sums, cprefix);
-        if (rc) return rc;
-        hipLaunchKernelGGL(vk_cl_nl_write_kernel, dim3(chunk), dim3(kClThreads), 0, ctx->stream, text, dfiles, dfchunk,
-                           nfiles, cprefix, recs);
-    }
-    VK_HIP(ctx, hipGetLastError());
+    rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
     const uint32_t shift_tail = std::max(1u, trim_tail);
     for (size_t g0 = 0; g0 < active.size(); g0 += L.slice) {
         const uint32_t ng = static_cast<uint32_t>(std::min<size_t>(L.slice, active.size() - g0));
         std::vector<AdGroup> grp(ng);
         std::vector<uint64_t> base(ng + 1ull, 0);
         for (uint32_t k = 0; k < ng; ++k) {
-            grp[k] = AdGroup{first[active[g0 + k]], taken[active[g0 + k]]};
+            grp[k] = AdGroup{ix.first[active[g0 + k]], ix.count[active[g0 + k]]};
             base[k + 1] = base[k] + grp[k].n;
         }
         const uint64_t nrec = base[ng];
-        VK_HIP(ctx, hipMemcpyAsync(dgroups, grp.data(), ng * sizeof(AdGroup), hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(gbase, base.data(), (ng + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemsetAsync(hist, 0, static_cast<size_t>(ng) * kAdKeys * 4, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.groups, grp.data(), ng * sizeof(AdGroup), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.gbase, base.data(), (ng + 1ull) * 8, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(L.hist, 0, static_cast<size_t>(ng) * kAdKeys * 4, ctx->stream));
         hipLaunchKernelGGL(vk_ad_hist_kernel, dim3((nrec + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
-                           text, recs, dgroups, gbase, ng, hist);
-        hipLaunchKernelGGL(vk_ad_top_kernel, dim3(ng), dim3(kAdThreads), 0, ctx->stream, hist, ranked, totals);
+                           text, L.c.recs, L.groups, L.gbase, ng, L.hist);
+        hipLaunchKernelGGL(vk_ad_top_kernel, dim3(ng), dim3(kAdThreads), 0, ctx->stream, L.hist, L.ranked, L.totals);
         VK_HIP(ctx, hipGetLastError());
         std::vector<uint64_t> rk(ng * kAdTop), tot(ng);
-        VK_HIP(ctx, hipMemcpyAsync(rk.data(), ranked, rk.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(tot.data(), totals, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(rk.data(), L.ranked, rk.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(tot.data(), L.totals, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
         VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        // candidates: ranked keys with count * 4^10 / total > 20; each gets room for `count` occurrences (the
-        // extension's positions are a part of the counted ones)
         std::vector<AdCand> cand(ng * kAdTop);
-        uint64_t nocc = 0;
-        for (uint32_t k = 0; k < ng; ++k)
-            for (uint32_t c = 0; c < kAdTop; ++c) {
-                const uint64_t v = rk[k * kAdTop + c], cnt = v >> 20;
-                AdCand& d = cand[k * kAdTop + c];
-                d = AdCand{static_cast<uint32_t>(kAdKeys - 1 - (v & (kAdKeys - 1))), 0, nocc};
-                if (v && tot[k] && cnt * kAdKeys / tot[k] > kAdFold) {
-                    d.cap = static_cast<uint32_t>(cnt);
-                    nocc += cnt;
-                }
-            }
+        const uint64_t nocc = ad_candidates(rk, tot, cand);
         if (nocc == 0) continue;
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cldetect), &ctx->cldetect_cap,
-                        cl_align(nocc * sizeof(AdOcc)) + nocc * sizeof(uint16_t));
+        rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cldetect), &ctx->cldetect_cap,
+                    cl_align(nocc * sizeof(AdOcc)) + nocc * sizeof(uint16_t));
         if (rc) return rc;
         auto* occ = reinterpret_cast<AdOcc*>(ctx->d_cldetect);
         auto* state = reinterpret_cast<uint16_t*>(ctx->d_cldetect + cl_align(nocc * sizeof(AdOcc)));
-        VK_HIP(ctx, hipMemcpyAsync(dcands, cand.data(), cand.size() * sizeof(AdCand), hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemsetAsync(counts, 0, cand.size() * 4, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.cands, cand.data(), cand.size() * sizeof(AdCand), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(L.counts, 0, cand.size() * 4, ctx->stream));
         hipLaunchKernelGGL(vk_ad_collect_kernel, dim3((nrec + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
-                           text, recs, dgroups, gbase, ng, dcands, shift_tail, counts, occ);
-        hipLaunchKernelGGL(vk_ad_extend_kernel, dim3(ng * kAdTop), dim3(kAdThreads), 0, ctx->stream, text, dcands, counts, occ,
-                           state, dext);
+                           text, L.c.recs, L.groups, L.gbase, ng, L.cands, shift_tail, L.counts, occ);
+        hipLaunchKernelGGL(vk_ad_extend_kernel, dim3(ng * kAdTop), dim3(kAdThreads), 0, ctx->stream, text, L.cands, L.counts, occ,
+                           state, L.ext);
         VK_HIP(ctx, hipGetLastError());
         std::vector<AdExt> ext(ng * kAdTop);
-        VK_HIP(ctx, hipMemcpyAsync(ext.data(), dext, ext.size() * sizeof(AdExt), hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(ext.data(), L.ext, ext.size() * sizeof(AdExt), hipMemcpyDeviceToHost, ctx->stream));
         VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        // the first candidate accepted: snapped to a listed adapter, or both directions ran out
-        for (uint32_t k = 0; k < ng; ++k)
+        for (uint32_t k = 0; k < ng; ++k)   // a group takes the first of its candidates that is accepted
             for (uint32_t c = 0; c < kAdTop; ++c) {
-                const AdCand& d = cand[k * kAdTop + c];
-                if (!d.cap || ext[k * kAdTop + c].nocc < kAdMinVotes) continue;   // (no evidence either way)
-                const std::string D = ad_detected(ext[k * kAdTop + c], d.key);
-                std::string got;
-                for (const char* known : kAdKnown) {
-                    const std::string ad(known);
-                    if (D.find(ad.substr(0, kAdSnap)) != std::string::npos) {
-                        got = ad;
-                        break;
-                    }
-                }
-                if (got.empty() && (ext[k * kAdTop + c].flags & 3u) == 3u) got = D;
+                const AdExt& e = ext[k * kAdTop + c];
+                if (!cand[k * kAdTop + c].cap || e.nocc < kAdMinVotes) continue;   // (no evidence either way)
+                const std::string got = ad_accept(e, cand[k * kAdTop + c].key);
                 if (got.empty()) continue;
                 const uint64_t g = active[g0 + k];
                 adapter_lengths[g] = static_cast<uint32_t>(got.size());

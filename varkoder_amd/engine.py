@@ -20,6 +20,19 @@ def _torch():
     return torch
 
 
+def _u64(a):
+    """A NumPy array's data as the C ABI takes it: uint64_t*; _u32, _u8 alike."""
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _u32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _u8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
 def bgzf_members(buf):
     """The members of a BGZF file (what `bgzip` and BBTools-through-bgzip write: gzip members of at most
     64 KiB, each with its own size in a 'BC' extra field), found by hopping from block header to block header
@@ -116,12 +129,12 @@ class ImageEngine:
                 st = self.L.vk_set_mapping(self.ctx, k, None, self.npix)
             else:
                 lut = np.ascontiguousarray(pixel_lut(k, mapping), dtype=np.uint32)
-                st = self.L.vk_set_mapping(self.ctx, k, lut.ctypes.data_as(C.POINTER(C.c_uint32)), self.npix)
+                st = self.L.vk_set_mapping(self.ctx, k, _u32(lut), self.npix)
         else:
             lut = np.ascontiguousarray(lut, dtype=np.uint32)
             self.npix = int(npix)
             self.side = int(round(self.npix ** 0.5))
-            st = self.L.vk_set_mapping(self.ctx, k, lut.ctypes.data_as(C.POINTER(C.c_uint32)), self.npix)
+            st = self.L.vk_set_mapping(self.ctx, k, _u32(lut), self.npix)
         _capi.check(self.ctx, st, "vk_set_mapping")
         self.ncode = 4 ** k
 
@@ -393,10 +406,8 @@ class ImageEngine:
             flags = np.array([1 if mapped[i][2] else 0 for i in idx], dtype=np.uint8)
             st = np.zeros(len(idx), dtype=np.uint32)
             _capi.check(self.ctx, self.L.vk_upload_mapped(
-                self.ctx, self._ptr(dev), np.ascontiguousarray(offs[idx]).ctypes.data_as(C.POINTER(C.c_uint64)), srcp,
-                np.ascontiguousarray(staged["disk"][idx]).ctypes.data_as(C.POINTER(C.c_uint64)),
-                flags.ctypes.data_as(C.POINTER(C.c_uint8)), len(idx), st.ctypes.data_as(C.POINTER(C.c_uint32))),
-                "vk_upload_mapped")
+                self.ctx, self._ptr(dev), _u64(np.ascontiguousarray(offs[idx])), srcp,
+                _u64(np.ascontiguousarray(staged["disk"][idx])), _u8(flags), len(idx), _u32(st)), "vk_upload_mapped")
             for j, i in enumerate(idx):
                 if st[j]:   # the pages could not be registered: through a pageable copy, once
                     dev[int(offs[i]):int(offs[i]) + views[j].size].copy_(torch.from_numpy(views[j].copy()))
@@ -513,11 +524,8 @@ class ImageEngine:
         lens = np.zeros(n, dtype=np.uint64)
         status = np.zeros(n, dtype=np.uint32)
         gzp = C.c_void_p(gz) if isinstance(gz, int) else self._ptr(gz)   # (an address: host memory pinned for the GPU)
-        st = self.L.vk_inflate_device(self.ctx, gzp, go.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      gl.ctypes.data_as(C.POINTER(C.c_uint64)), n, self._ptr(out),
-                                      oo.ctypes.data_as(C.POINTER(C.c_uint64)), oc.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      lens.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        st = self.L.vk_inflate_device(self.ctx, gzp, _u64(go), _u64(gl), n, self._ptr(out), _u64(oo), _u64(oc), _u64(lens),
+                                      _u32(status))
         _capi.check(self.ctx, st, "vk_inflate_device")
         return lens, status
 
@@ -531,9 +539,8 @@ class ImageEngine:
             hist = torch.empty((n, self.ncode), dtype=torch.int32, device=self.device)
         if status is None:
             status = torch.empty((n,), dtype=torch.int32, device=self.device)
-        st = self.L.vk_count_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                    lens.ctypes.data_as(C.POINTER(C.c_uint64)), n, self.k, parts,
-                                    self._ptr(hist), self._ptr(status))
+        st = self.L.vk_count_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), n, self.k, parts, self._ptr(hist),
+                                    self._ptr(status))
         _capi.check(self.ctx, st, "vk_count_device")
         return hist, status
 
@@ -554,11 +561,8 @@ class ImageEngine:
             status = torch.empty((n,), dtype=torch.int32, device=self.device)
         if sites is None:
             sites = torch.empty((n, 2), dtype=torch.int64, device=self.device)
-        u64p = C.POINTER(C.c_uint64)
-        st = self.L.vk_count_sampled_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p),
-                                            lens.ctypes.data_as(u64p), n, self.k, parts, seeds.ctypes.data_as(u64p),
-                                            thr.ctypes.data_as(u64p), self._ptr(hist), self._ptr(status),
-                                            self._ptr(sites))
+        st = self.L.vk_count_sampled_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), n, self.k, parts, _u64(seeds),
+                                            _u64(thr), self._ptr(hist), self._ptr(status), self._ptr(sites))
         _capi.check(self.ctx, st, "vk_count_sampled_device")
         return hist, status, sites
 
@@ -569,9 +573,8 @@ class ImageEngine:
         n = len(offs)
         sites = np.zeros(n, dtype=np.uint64)
         status = np.zeros(n, dtype=np.uint32)
-        u64p = C.POINTER(C.c_uint64)
-        st = self.L.vk_read_index_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p), n, parts,
-                                         sites.ctypes.data_as(u64p), status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        st = self.L.vk_read_index_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), n, parts, _u64(sites),
+                                         _u32(status))
         _capi.check(self.ctx, st, "vk_read_index_device")
         return sites, status
 
@@ -587,10 +590,8 @@ class ImageEngine:
             status = torch.empty((n,), dtype=torch.int32, device=self.device)
         sites = np.zeros(n, dtype=np.uint64)
         st_h = np.zeros(n, dtype=np.uint32)
-        u64p = C.POINTER(C.c_uint64)
-        st = self.L.vk_count_index_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p), n, self.k,
-                                          parts, self._ptr(hist), self._ptr(status), sites.ctypes.data_as(u64p),
-                                          st_h.ctypes.data_as(C.POINTER(C.c_uint32)))
+        st = self.L.vk_count_index_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), n, self.k, parts, self._ptr(hist),
+                                          self._ptr(status), _u64(sites), _u32(st_h))
         _capi.check(self.ctx, st, "vk_count_index_device")
         return hist, sites, st_h
 
@@ -598,16 +599,13 @@ class ImageEngine:
         """Newline bytes of each file in HBM (vk_clean_lines_device; // 4 = its records).  Synchronises."""
         offs, lens = self._desc(offsets, lengths)
         lines = np.zeros(len(offs), dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        st = self.L.vk_clean_lines_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
-                                          len(offs), lines.ctypes.data_as(u64p))
+        st = self.L.vk_clean_lines_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), len(offs), _u64(lines))
         _capi.check(self.ctx, st, "vk_clean_lines_device")
         return lines
 
-    def detect_adapters(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim_tail=10):
-        """Each group's adapter detected from its first reads (vk_clean_detect_device; the files, records, roles and
-        samples of clean()): a list of [R1's, R2's, the single reads'] per sample, bytes or None.  Synchronises."""
-        torch = _torch()
+    def _clean_call(self, offsets, lengths, records, roles, samples, nsamples, size_fn):
+        """What clean() and detect_adapters() do alike ahead of their call: the files' arrays in the C ABI's types, with
+        their count, and a workspace tensor of the size `size_fn` (vk_clean_workspace_size or its detect twin) asks."""
         offs, lens = self._desc(offsets, lengths)
         recs = np.ascontiguousarray(records, dtype=np.uint64)
         roles = np.ascontiguousarray(roles, dtype=np.uint32)
@@ -615,19 +613,22 @@ class ImageEngine:
         n = len(offs)
         if not (len(recs) == len(roles) == len(samples) == n):
             raise ValueError("one record budget, role and sample per file")
-        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
         ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_clean_detect_workspace_size(lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p), n,
-                                                                    nsamples, C.byref(ws_bytes)),
-                    "vk_clean_detect_workspace_size")
+        _capi.check(self.ctx, size_fn(_u64(lens), _u64(recs), n, nsamples, C.byref(ws_bytes)), size_fn.__name__)
+        torch = _torch()
         ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        return offs, lens, recs, roles, samples, n, ws
+
+    def detect_adapters(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim_tail=10):
+        """Each group's adapter detected from its first reads (vk_clean_detect_device; the files, records, roles and
+        samples of clean()): a list of [R1's, R2's, the single reads'] per sample, bytes or None.  Synchronises."""
+        offs, lens, recs, roles, samples, n, ws = self._clean_call(offsets, lengths, records, roles, samples, nsamples,
+                                                                   self.L.vk_clean_detect_workspace_size)
         alen = np.zeros(3 * nsamples, dtype=np.uint32)
         aseq = np.zeros((3 * nsamples, _capi.VK_CL_MAX_ADAPTER), dtype=np.uint8)
-        st = self.L.vk_clean_detect_device(self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
-                                           recs.ctypes.data_as(u64p), roles.ctypes.data_as(u32p),
-                                           samples.ctypes.data_as(u32p), n, nsamples, int(trim_tail), self._ptr(ws),
-                                           ws.numel(), alen.ctypes.data_as(u32p),
-                                           aseq.ctypes.data_as(C.POINTER(C.c_uint8)))
+        st = self.L.vk_clean_detect_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), _u64(recs), _u32(roles),
+                                           _u32(samples), n, nsamples, int(trim_tail), self._ptr(ws), ws.numel(), _u32(alen),
+                                           _u8(aseq))
         _capi.check(self.ctx, st, "vk_clean_detect_device")
         return [[aseq[3 * j + g, :alen[3 * j + g]].tobytes() if alen[3 * j + g] else None for g in range(3)]
                 for j in range(nsamples)]
@@ -642,13 +643,8 @@ class ImageEngine:
         adapters: per sample [R1's, R2's, the single reads'] adapter (bytes or None) to trim by sequence as well
         (vk_clean_adapters_device); the result then ends with adapter stats uint64[nsamples, 2] (reads, bases cut)."""
         torch = _torch()
-        offs, lens = self._desc(offsets, lengths)
-        recs = np.ascontiguousarray(records, dtype=np.uint64)
-        roles = np.ascontiguousarray(roles, dtype=np.uint32)
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        n = len(offs)
-        if not (len(recs) == len(roles) == len(samples) == n):
-            raise ValueError("one record budget, role and sample per file")
+        offs, lens, recs, roles, samples, n, ws = self._clean_call(offsets, lengths, records, roles, samples, nsamples,
+                                                                   self.L.vk_clean_workspace_size)
         cap = np.zeros(nsamples, dtype=np.uint64)
         np.add.at(cap, samples.astype(np.int64), lens)
         rounded = (cap + np.uint64(15)) // np.uint64(16) * np.uint64(16)
@@ -656,43 +652,35 @@ class ImageEngine:
         if nsamples > 1:
             out_offs[1:] = np.cumsum(rounded[:-1])
         total = int(rounded.sum()) + 16
-        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_clean_workspace_size(lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p), n, nsamples,
-                                                             C.byref(ws_bytes)), "vk_clean_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
         out = torch.empty(total, dtype=torch.uint8, device=self.device)
         out_lens = torch.empty(nsamples, dtype=torch.int64, device=self.device)
         stats = torch.empty((nsamples, _capi.VK_CL_NSTAT), dtype=torch.int64, device=self.device)
         status = torch.empty(nsamples, dtype=torch.int32, device=self.device)
+        results = [(out_lens, np.uint64), (stats, np.uint64), (status, np.uint32)]   # (device tensor, its type on the host)
         flags = (_capi.VK_CL_ADAPTER if adapter else 0) | (_capi.VK_CL_MERGE if merge else 0) | (_capi.VK_CL_DEDUP if dedup else 0)
-        args = (self.ctx, self._ptr(fastq), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p), recs.ctypes.data_as(u64p),
-                roles.ctypes.data_as(u32p), samples.ctypes.data_as(u32p), n, nsamples, int(trim[0]), int(trim[1]), flags,
-                self._ptr(ws), ws.numel(), self._ptr(out), out_offs.ctypes.data_as(u64p), total, self._ptr(out_lens),
-                self._ptr(stats), self._ptr(status))
+        args = (self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), _u64(recs), _u32(roles), _u32(samples), n, nsamples,
+                int(trim[0]), int(trim[1]), flags, self._ptr(ws), ws.numel(), self._ptr(out), _u64(out_offs), total,
+                self._ptr(out_lens), self._ptr(stats), self._ptr(status))
         if adapters is None:
-            st = self.L.vk_clean_device(*args)
-            _capi.check(self.ctx, st, "vk_clean_device")
-            return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
-                    status.cpu().numpy().astype(np.uint32))
-        if len(adapters) != nsamples:
-            raise ValueError("one adapter triple per sample")
-        alen = np.zeros(3 * nsamples, dtype=np.uint32)
-        aseq = np.zeros((3 * nsamples, _capi.VK_CL_MAX_ADAPTER), dtype=np.uint8)
-        for j, triple in enumerate(adapters):
-            for g, a in enumerate(triple):
-                if a is None:
-                    continue
-                if not 0 < len(a) <= _capi.VK_CL_MAX_ADAPTER:
-                    raise ValueError(f"an adapter is 1..{_capi.VK_CL_MAX_ADAPTER} bytes: {a!r}")
-                alen[3 * j + g] = len(a)
-                aseq[3 * j + g, :len(a)] = np.frombuffer(bytes(a), dtype=np.uint8)
-        ad_stats = torch.empty((nsamples, 2), dtype=torch.int64, device=self.device)
-        st = self.L.vk_clean_adapters_device(*args, alen.ctypes.data_as(u32p), aseq.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                             self._ptr(ad_stats))
-        _capi.check(self.ctx, st, "vk_clean_adapters_device")
-        return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
-                status.cpu().numpy().astype(np.uint32), ad_stats.cpu().numpy().astype(np.uint64))
+            _capi.check(self.ctx, self.L.vk_clean_device(*args), "vk_clean_device")
+        else:
+            if len(adapters) != nsamples:
+                raise ValueError("one adapter triple per sample")
+            alen = np.zeros(3 * nsamples, dtype=np.uint32)
+            aseq = np.zeros((3 * nsamples, _capi.VK_CL_MAX_ADAPTER), dtype=np.uint8)
+            for j, triple in enumerate(adapters):
+                for g, a in enumerate(triple):
+                    if a is None:
+                        continue
+                    if not 0 < len(a) <= _capi.VK_CL_MAX_ADAPTER:
+                        raise ValueError(f"an adapter is 1..{_capi.VK_CL_MAX_ADAPTER} bytes: {a!r}")
+                    alen[3 * j + g] = len(a)
+                    aseq[3 * j + g, :len(a)] = np.frombuffer(bytes(a), dtype=np.uint8)
+            ad_stats = torch.empty((nsamples, 2), dtype=torch.int64, device=self.device)
+            results.append((ad_stats, np.uint64))
+            st = self.L.vk_clean_adapters_device(*args, _u32(alen), _u8(aseq), self._ptr(ad_stats))
+            _capi.check(self.ctx, st, "vk_clean_adapters_device")
+        return (out, out_offs) + tuple(t.cpu().numpy().astype(dt) for t, dt in results)
 
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""
@@ -714,9 +702,7 @@ class ImageEngine:
             status = torch.empty((n,), dtype=torch.int32, device=self.device)
         if img is None:
             img = torch.empty((n, self.side, self.side), dtype=torch.uint8, device=self.device)
-        st = self.L.vk_fastq_to_image_device(self.ctx, self._ptr(fastq),
-                                             offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             lens.ctypes.data_as(C.POINTER(C.c_uint64)), n, self.k, parts,
+        st = self.L.vk_fastq_to_image_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), n, self.k, parts,
                                              self._ptr(hist), self._ptr(status), self._ptr(img))
         _capi.check(self.ctx, st, "vk_fastq_to_image_device")
         return img, hist, status
@@ -725,18 +711,17 @@ class ImageEngine:
         """Synthetic FASTQ for samples sample0..sample0+nsamples-1, generated in HBM (dist 0, 1: records of one
         size; dist 2: reads shaped like fastp's output, samples of different sizes -- synth.py)."""
         torch = _torch()
-        u64p = C.POINTER(C.c_uint64)
         if dist == 2:
             lens = np.zeros(nsamples, dtype=np.uint64)
             _capi.check(self.ctx, self.L.vk_synth_shaped_lengths(self.ctx, sample0, nsamples, reads, readlen, C.c_uint64(seed),
-                                                                  lens.ctypes.data_as(u64p)), "vk_synth_shaped_lengths")
+                                                                  _u64(lens)), "vk_synth_shaped_lengths")
             offs = np.zeros(nsamples, dtype=np.uint64)
             if nsamples > 1:
                 offs[1:] = np.cumsum((lens[:-1] + np.uint64(15)) // np.uint64(16) * np.uint64(16))
             total = int(offs[-1] + lens[-1]) if nsamples else 0
             if out is None or out.numel() < (total + 15) // 16 * 16 + 16:
                 out = torch.empty(((total + 15) // 16 * 16 + 16,), dtype=torch.uint8, device=self.device)
-            _capi.check(self.ctx, self.L.vk_synth_shaped_device(self.ctx, self._ptr(out), offs.ctypes.data_as(u64p), sample0,
+            _capi.check(self.ctx, self.L.vk_synth_shaped_device(self.ctx, self._ptr(out), _u64(offs), sample0,
                                                                  nsamples, reads, readlen, C.c_uint64(seed)), "vk_synth_shaped_device")
             return out, offs, lens
         rec = 2 * readlen + 20
@@ -767,8 +752,8 @@ class ImageEngine:
         buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
         hist = np.empty(self.ncode, dtype=np.uint32)
         stw = C.c_uint32(0)
-        st = self.L.vk_count_host(self.ctx, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, self.k,
-                                  hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stw))
+        st = self.L.vk_count_host(self.ctx, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, self.k, _u32(hist),
+                                  C.byref(stw))
         if st not in (_capi.VK_OK, _capi.VK_EFORMAT):
             _capi.check(self.ctx, st, "vk_count_host")
         return hist, stw.value
@@ -776,8 +761,7 @@ class ImageEngine:
     def image_host(self, hist):
         hist = np.ascontiguousarray(hist, dtype=np.uint32)
         img = np.empty(self.npix, dtype=np.uint8)
-        st = self.L.vk_image_host(self.ctx, hist.ctypes.data_as(C.POINTER(C.c_uint32)), self.k,
-                                  img.ctypes.data_as(C.POINTER(C.c_uint8)))
+        st = self.L.vk_image_host(self.ctx, _u32(hist), self.k, _u8(img))
         _capi.check(self.ctx, st, "vk_image_host")
         return img.reshape(self.side, self.side)
 

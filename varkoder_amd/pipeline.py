@@ -492,16 +492,14 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                 roles += [r for _, r in sf]
                 owner += [j] * len(sf)
                 at += len(sf)
+            table = None
             if by_sequence:
                 found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=trim[1])
                          if detect_adapters else [[None] * 3 for _ in batch])
                 table = [[e if e is not None else d for e, d in zip(explicit, det)] for det in found]
-                out, ooffs, olens, cst, status, ast = eng.clean(dev, offs, lens, records, roles, owner, len(batch),
-                                                                trim=trim, adapter=adapter, merge=merge, dedup=dedup,
-                                                                adapters=table)
-            else:
-                out, ooffs, olens, cst, status = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
-                                                           adapter=adapter, merge=merge, dedup=dedup)
+            out, ooffs, olens, cst, status, *rest = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
+                                                              adapter=adapter, merge=merge, dedup=dedup, adapters=table)
+            ast = rest[0] if rest else None   # (adapter stats: with a table only)
             del dev
             tc = time.perf_counter()
             ok = []
