@@ -245,6 +245,22 @@ def test_abi_argument_errors(engines):
     offs[0] = 0
     assert L.vk_count_device(eng.ctx, vp(fq), offs, lens, 1, 4, 0, vp(hist), vp(st)) == _capi.VK_EINVAL
     assert L.vk_count_device(eng.ctx, vp(fq), offs, lens, 0, 7, 0, vp(hist), vp(st)) == _capi.VK_OK   # empty batch
+    # the same three of the other entry points of the count path (vk_read_index_device has no k)
+    seeds, thr = (C.c_uint64 * 1)(1), (C.c_uint64 * 1)(1 << 31)
+    sites_d = torch.zeros(2, dtype=torch.int64, device="cuda")
+    sites_h, st_h = (C.c_uint64 * 1)(), (C.c_uint32 * 1)()
+    sampled = lambda n, k: L.vk_count_sampled_device(eng.ctx, vp(fq), offs, lens, n, k, 0, seeds, thr, vp(hist), vp(st), vp(sites_d))  # noqa: E731
+    index = lambda n, k: L.vk_read_index_device(eng.ctx, vp(fq), offs, lens, n, 0, sites_h, st_h)  # noqa: E731
+    both = lambda n, k: L.vk_count_index_device(eng.ctx, vp(fq), offs, lens, n, k, 0, vp(hist), vp(st), sites_h, st_h)  # noqa: E731
+    for call, has_k in ((sampled, True), (index, False), (both, True)):
+        offs[0] = 8
+        assert call(1, 7) == _capi.VK_EINVAL
+        offs[0] = 0
+        if has_k:
+            assert call(1, 4) == _capi.VK_EINVAL
+        assert call(0, 7) == _capi.VK_OK
+    thr[0] = (1 << 32) + 1
+    assert sampled(1, 7) == _capi.VK_EINVAL                                           # a threshold is at most 2^32
     ctx = C.c_void_p()
     assert L.vk_ctx_create(0, None, 1, C.byref(ctx)) == _capi.VK_OK
     img = torch.zeros(128 * 128, dtype=torch.uint8, device="cuda")

@@ -302,6 +302,55 @@ def test_spill_path_with_a_full_arena_counts_directly(route_engine, k, route):
             assert np.array_equal(got[i], oracle.count_fastq(fq, k)[0]), (parts, i)
 
 
+def _spill_bytes_per_sample(k, route, maxlen, parts):
+    """What vkimg.hip plans per sample of a k = 8, 9 sub-batch (spill_plan's callers): the arena's 4 KiB runs with their
+    headers, the route's fixed words, the tables pass B writes, the quad route's regions of partly countable quads."""
+    run, waves, pool = 4096, 16, 16
+    if route == "quads":
+        runs = (maxlen // 4 + maxlen // 32) // run + 16 + parts * (256 + waves * pool)
+        pshift = 6
+        while pshift < 21 and (1 << pshift) < (maxlen // parts + 64 * waves) // 16384 + 64:
+            pshift += 1
+        return (runs * (run + 8) + (3 * 256 + 2) * 4 + 256 * (4 << (2 * k - 8)) * 4
+                + parts * 256 * ((1 << pshift) + 1) * 4 + 64)
+    runs = (maxlen // 2 + maxlen // 16) // run + 16 + parts * waves * (16 + pool)
+    return runs * (run + 4) + 4 + 3 * 16 * 4 + 16 * (2 << (2 * k - 4)) * 4 + 64
+
+
+@pytest.mark.parametrize("case", ("quads", "pairs", "sampled"))
+@pytest.mark.parametrize("k", (8, 9))
+def test_spill_path_in_several_sub_batches(route_engine, k, case):
+    """The k = 8, 9 workspace is planned per sample and a batch that does not fit the budget runs in sub-batches, each
+    over its own slice of the histograms, the wave phases, the descriptors and (subsampled) the seeds, thresholds and
+    site counters.  VKIMG_SPILL_BUDGET set to two and a half samples' worth: five samples in sub-batches of 2, 2 and 1.
+    "sampled": vk_count_sampled_device without a read index, so the streaming pair kernels run."""
+    nsamples, parts = 5, 3
+    samples = [synth.sample_fastq(110 + i, 4000 + 500 * i, 150, dist=i % 3).tobytes() for i in range(nsamples)]
+    assert len(set(samples)) == nsamples
+    route = "quads" if case == "quads" else "pairs"
+    per_sample = _spill_bytes_per_sample(k, route, max(len(s) for s in samples), parts)
+    eng = route_engine(k, "pairs" if case == "pairs" else "quads", VKIMG_SPILL_BUDGET=5 * per_sample // 2,
+                       VKIMG_NO_READ_INDEX=1)
+    dev, offs, lens = eng.upload(samples)
+    if case == "sampled":
+        seeds = np.arange(7, 7 + nsamples, dtype=np.uint64)
+        thr = np.array([(1 << 32) * (i + 2) // 8 for i in range(nsamples)], dtype=np.uint64)
+        hist, status, sites = eng.count_sampled(dev, offs, lens, seeds, thr, parts=parts)
+        want = [oracle.count_fastq_sampled(s, k, int(seeds[i]), int(thr[i])) for i, s in enumerate(samples)]
+        si = sites.cpu().numpy()
+        for i in range(nsamples):
+            assert want[i][2] == 0 and tuple(int(x) for x in si[i]) == want[i][3], i
+    else:
+        hist, status = eng.count(dev, offs, lens, parts=parts)
+        want = [oracle.count_fastq(s, k) for s in samples]
+    assert not status.cpu().numpy().any()
+    got = hist.cpu().numpy().view(np.uint32)
+    for i in range(nsamples):
+        assert np.array_equal(got[i], want[i][0]), i
+    # the launch recorded is the last sub-batch's: one sample of the five
+    assert eng.last_count_launch()["grid"] == (nsamples % 2) * parts < nsamples * parts
+
+
 @pytest.mark.parametrize("k", (8, 9))
 def test_quad_route_with_full_regions_counts_directly(route_engine, k):
     """Quads of which only some windows count (a read's first and last, the neighbours of an N) travel through a region

@@ -36,6 +36,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -87,7 +88,7 @@ struct vk_ctx {
     size_t scratch_cap = 0;
     uint32_t* d_spill = nullptr;  // k >= 8: bucket cursors + bucket streams
     size_t spill_cap = 0;
-    size_t spill_budget = 96ull << 30;  // bytes of HBM the spill path may use at a time
+    size_t spill_budget = 96ull << 30;  // bytes of HBM the spill path may use at a time (VKIMG_SPILL_BUDGET=n: tests force several sub-batches)
     // host-call staging
     uint64_t* d_sub = nullptr;    // subsampling launches: seeds | thresholds
     uint8_t* d_gzjobs = nullptr;  // vk_inflate_device: jobs | text lengths | status words
@@ -132,6 +133,7 @@ struct vk_ctx {
     uint8_t* d_cldetect = nullptr; // vk_clean_detect_device: a slice's seed occurrences and their states
     size_t cldetect_cap = 0;
     uint32_t clean_hash_bits = 64; // VKIMG_CLEAN_HASH_BITS=n: vk_clean_device's dedup keeps n bits of its 64-bit hash (tests: collisions on purpose)
+    bool no_read_index = false;    // VKIMG_NO_READ_INDEX=1: subsampled counts always stream the text, whatever index the context holds (tests, A/B timing)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -155,6 +157,53 @@ int ensure(vk_ctx* ctx, void** p, size_t* cap, size_t need) {
     VK_HIP(ctx, hipMalloc(p, n));
     *cap = n;
     return VK_OK;
+}
+
+size_t ws_align(size_t x) { return (x + 255) / 256 * 256; }
+// Hands out the pieces of a workspace one after another, each at a multiple of 256 bytes.  A piece is stated once: the
+// typed pointer it fills and its element count.  Without a base only the sizes add up (the *_workspace_size calls).
+struct WsTake {
+    uint8_t* base;
+    size_t at;
+    template <class T> void operator()(T*& piece, size_t count) {
+        piece = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += ws_align(count * sizeof(T));
+    }
+};
+
+// A workspace of the context (*p, *cap: grown on demand) in the pieces `pieces(take)` states: once for the size, once for the pointers.
+template <class P, class F>
+int ws_carve(vk_ctx* ctx, P** p, size_t* cap, F&& pieces) {
+    WsTake size{nullptr, 0};
+    pieces(size);
+    int rc = ensure(ctx, reinterpret_cast<void**>(p), cap, size.at);
+    if (rc) return rc;
+    WsTake take{reinterpret_cast<uint8_t*>(*p), 0};
+    pieces(take);
+    return VK_OK;
+}
+
+// environment switches, read when a context is made: NAME=1, NAME=<number>
+bool env_flag(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '1';
+}
+template <class T>
+void env_uint(const char* name, T* dst) {
+    const char* e = getenv(name);
+    if (e && e[0]) *dst = static_cast<T>(strtoull(e, nullptr, 10));
+}
+
+// The runtime k (5..9, checked by the caller) as the template argument of f: f(std::integral_constant<int, K>{}).
+template <class F>
+int with_k(int k, F&& f) {
+    switch (k) {
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: return f(std::integral_constant<int, 9>{});
+    }
 }
 
 // Sample descriptors go through a pinned host mirror; an unchanged batch (the
@@ -202,11 +251,76 @@ uint32_t npad_of(uint32_t npix) {
     return p;
 }
 
+// The samples of a count / index call and how its launches split them.
+struct CtPlan {
+    const uint8_t* fq;
+    uint32_t nsamples, parts;    // workgroups per sample
+    uint64_t maxlen;             // the longest sample
+    size_t nwaves;               // nsamples * parts * kWaves: a slot each in d_wavephase
+    const uint64_t *d_offs, *d_lens;   // the descriptors on the device
+};
+
+// The arguments every such call checks alike (nsamples > 0), and the longest sample.
+int ct_check(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples, CtPlan* p) {
+    if (!d_fastq || (reinterpret_cast<uintptr_t>(d_fastq) & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    *p = CtPlan{static_cast<const uint8_t*>(d_fastq), nsamples, 0, 0, 0, nullptr, nullptr};
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+        if (lengths[i] > p->maxlen) p->maxlen = lengths[i];
+    }
+    return VK_OK;
+}
+
+// The split is settled (at least `parts` workgroups per sample): the descriptors and a phase word per wave on the device.
+int ct_split(vk_ctx* ctx, const uint64_t* offsets, const uint64_t* lengths, uint32_t parts, CtPlan* p) {
+    // a wavefront addresses its byte range through a 32-bit buffer descriptor (vk_count.h, wave_stream):
+    // keep every range below 2 GiB, whatever the caller asked for
+    while (p->maxlen / (static_cast<uint64_t>(parts) * kWaves) >= (1ull << 31)) parts *= 2;
+    if (static_cast<uint64_t>(p->nsamples) * parts > (1u << 24)) return VK_EINVAL;
+    p->parts = parts;
+    p->nwaves = static_cast<size_t>(p->nsamples) * parts * kWaves;
+    if (ctx->desc_cap < 2ull * p->nsamples * sizeof(uint64_t)) ctx->desc_n = 0;  // realloc drops the cached copy
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->desc_cap, 2ull * p->nsamples * sizeof(uint64_t));
+    if (rc) return rc;
+    rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_wavephase), &ctx->wavephase_cap, p->nwaves * sizeof(uint32_t));
+    if (rc) return rc;
+    p->d_offs = ctx->d_desc;
+    p->d_lens = ctx->d_desc + p->nsamples;
+    return upload_desc(ctx, offsets, lengths, p->nsamples);
+}
+
+// What a launch over the plan's samples ends with: the line-phase check of the byte ranges into d_status.  With `lengths`
+// (a count) the figures vk_last_count_general reads are kept.
+int ct_finish(vk_ctx* ctx, const CtPlan& p, const uint64_t* lengths, uint32_t* d_status) {
+    if (lengths) {
+        ctx->last_waves = p.nwaves;
+        ctx->last_bytes = 0;
+        for (uint32_t i = 0; i < p.nsamples; ++i) ctx->last_bytes += lengths[i];
+    }
+    hipLaunchKernelGGL(vk_check_kernel, dim3((p.nsamples + 255) / 256), dim3(256), 0, ctx->stream, p.fq, p.d_offs, p.d_lens,
+                       p.nsamples, p.parts, ctx->d_wavephase, d_status);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// The waves' lists of lanes set aside (vk_count.h): room for one lane per piece of the longest range (fastp-shaped
+// reads need 0.45), at least 64 entries; a wave whose list is full sends its pieces down the general path instead.
+// ctx->d_aside holds the lists of `nwaves` waves, *d_aside_n their lengths.
+int aside_lists(vk_ctx* ctx, const CtPlan& p, size_t nwaves, uint32_t* cap_out, uint32_t** d_aside_n) {
+    const uint64_t wave_bytes = p.maxlen / (static_cast<uint64_t>(p.parts) * kWaves) + 64;
+    uint64_t cap = wave_bytes / kPiece + 64;
+    if (cap > (1u << 20)) cap = 1u << 20;
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_aside), &ctx->aside_cap, nwaves * (cap + 1) * sizeof(uint32_t));   // lists, then their lengths
+    if (rc) return rc;
+    *cap_out = static_cast<uint32_t>(cap);
+    *d_aside_n = ctx->d_aside + nwaves * cap;
+    return VK_OK;
+}
+
 template <int K>
-int launch_count(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, const uint64_t* d_lens,
-                 uint32_t nsamples, uint32_t parts, uint64_t maxlen, uint32_t* d_hist, const SubParams* sub,
-                 const IndexParams* index = nullptr) {
-    const uint32_t grid = nsamples * parts;
+int launch_count(vk_ctx* ctx, const CtPlan& p, uint32_t* d_hist, const SubParams* sub, const IndexParams* index = nullptr) {
+    const uint32_t nsamples = p.nsamples, parts = p.parts, grid = nsamples * parts;
     const int atomic_flush = parts > 1 ? 1 : 0;
     if (atomic_flush)
         VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(nsamples) * (1u << (2 * K)) * sizeof(uint32_t),
@@ -215,42 +329,35 @@ int launch_count(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, co
     ctx->last_block = kCountThreads;
     ctx->last_lds = (1u << (2 * K)) * 4u + kWaves * 64 + 2 * 66 * 16;
     if (sub)
-        hipLaunchKernelGGL((vk_count_kernel<K, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                           d_offs, d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, *sub);
+        hipLaunchKernelGGL((vk_count_kernel<K, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                           p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, *sub);
     else if (ctx->k1_classic && !index)
-        hipLaunchKernelGGL((vk_count_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                           d_offs, d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, SubParams{});
+        hipLaunchKernelGGL((vk_count_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                           p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, SubParams{});
     else {
         ctx->last_lds = (1u << (2 * K)) * 4u + kWaves * 1024;
-        // the waves' lists of lanes set aside (vk_count.h): room for one lane per piece of the longest range (fastp-shaped
-        // reads need 0.45), at least 64 entries; a wave whose list is full sends its pieces down the general path instead
-        const uint64_t wave_bytes = maxlen / (static_cast<uint64_t>(parts) * kWaves) + 64;
-        uint64_t cap = wave_bytes / kPiece + 64;
-        if (cap > (1u << 20)) cap = 1u << 20;
-        const size_t nwaves = static_cast<size_t>(grid) * kWaves;
-        const size_t need = nwaves * (cap + 1) * sizeof(uint32_t);   // lists, then their lengths
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_aside), &ctx->aside_cap, need);
+        uint32_t cap = 0, *d_aside_n = nullptr;
+        int rc = aside_lists(ctx, p, p.nwaves, &cap, &d_aside_n);
         if (rc) return rc;
-        uint32_t* const d_aside_n = ctx->d_aside + nwaves * cap;
         // vk_aside_kernel: about a thousand workgroups, each serving `upb` workgroups of the count launch (of one sample)
         const uint32_t awant = nsamples >= 1024u ? 1u : (1024u + nsamples - 1u) / nsamples;
         const uint32_t upb = (parts + (awant < parts ? awant : parts) - 1u) / (awant < parts ? awant : parts);
         const uint32_t ablocks = (parts + upb - 1u) / upb;
         if (index) {   // the count and the read index of the samples in one pass (vk_count_index_device)
-            hipLaunchKernelGGL((vk_count_dense_kernel<K, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                               d_offs, d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
-                               static_cast<uint32_t>(cap), d_aside_n, *index);
+            hipLaunchKernelGGL((vk_count_dense_kernel<K, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                               p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
+                               cap, d_aside_n, *index);
             VK_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL((vk_aside_kernel<K, true>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                               d_offs, d_lens, nsamples, parts, d_hist, ctx->d_aside, static_cast<uint32_t>(cap), d_aside_n, *index, upb);
+            hipLaunchKernelGGL((vk_aside_kernel<K, true>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                               p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_aside, cap, d_aside_n, *index, upb);
         } else {
-            hipLaunchKernelGGL((vk_count_dense_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                               d_offs, d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
-                               static_cast<uint32_t>(cap), d_aside_n, IndexParams{});
+            hipLaunchKernelGGL((vk_count_dense_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                               p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
+                               cap, d_aside_n, IndexParams{});
             VK_HIP(ctx, hipGetLastError());
 #ifndef VK_DIAG_ASIDE_INLINE   // (diagnostic: the count kernel counts its own lists, vk_count.h)
-            hipLaunchKernelGGL((vk_aside_kernel<K, false>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                               d_offs, d_lens, nsamples, parts, d_hist, ctx->d_aside, static_cast<uint32_t>(cap), d_aside_n, IndexParams{}, upb);
+            hipLaunchKernelGGL((vk_aside_kernel<K, false>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                               p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_aside, cap, d_aside_n, IndexParams{}, upb);
 #endif
         }
     }
@@ -258,106 +365,12 @@ int launch_count(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, co
     return VK_OK;
 }
 
-// k = 8, 9, the quad route (vk_count.h: vk_bucket_kernel<K, 3>, vk_quad_list / _count / _merge_kernel),
-// in sub-batches that fit the spill budget.
-template <int K>
-int launch_spill_quad(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, const uint64_t* d_lens,
-                      uint32_t nsamples, uint32_t parts, uint64_t maxlen, uint32_t* d_hist) {
-    constexpr uint32_t NCODE = 1u << (2 * K);
-    constexpr size_t kOutWords = 4u << (2 * K - 8);   // what a pass B job stores: four window arrays of 4^(K-4) counters
-    // Arena of one sample, in 4 KiB runs: a quad entry is 2 bytes and a FASTQ holds at most len / 8 quads (sequence
-    // lines are less than half of the text), so len / 4 bytes however they spread over the 256 buckets; plus the
-    // blocks a drain may leave unused at the end of a run, one open run per (workgroup, queue), one reserve per wave.
-    uint64_t runs = (maxlen / 4 + maxlen / 32) / kRunBytes + 16 + static_cast<uint64_t>(parts) * (kQuadBuckets + kWaves * kPoolRuns);
-    if (ctx->spill_runs_cap) runs = ctx->spill_runs_cap;  // VKIMG_SPILL_RUNS_CAP: tests force the arena-full fallback
-    if (runs >= (1u << 24)) return VK_EINVAL;
-    // the regions of quads of which only some windows count, one per (workgroup of pass A, bucket): ~1 per 215 bytes of
-    // 150-base reads over 256 buckets; room for four times that (uniform bases), at least 64
-    const uint64_t wg_bytes = maxlen / parts + 64 * kWaves;
-    uint32_t pshift = 6;                                   // (a power of two: the place is a shift and an or)
-    while (pshift < 21 && (1ull << pshift) < wg_bytes / 16384 + 64) ++pshift;   // (at most 2^21: a workgroup's 256 regions stay below 2^31 bytes, the size a buffer descriptor takes as an int; what does not fit is counted directly)
-    if (ctx->spill_misc_cap) pshift = ctx->spill_misc_cap < 21 ? ctx->spill_misc_cap : 21;   // VKIMG_SPILL_MISC_CAP (log2): tests force the region-full fallback
-    const uint64_t pcap = 1ull << pshift;
-    const size_t preg_words = static_cast<size_t>(parts) * kQuadBuckets * (pcap + 1);   // per sample: regions, populations
-    const size_t per_sample = static_cast<size_t>(runs) * (kRunBytes + 2 * sizeof(uint32_t)) + (3 * kQuadBuckets + 2) * sizeof(uint32_t) +
-                              kQuadBuckets * kOutWords * sizeof(uint32_t) + preg_words * sizeof(uint32_t) + 64;
-    size_t free_b = 0, total_b = 0;
-    VK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    size_t budget = ctx->spill_budget;
-    const size_t avail = free_b / 4 * 3 + ctx->spill_cap;
-    if (budget > avail) budget = avail;
-    uint32_t batch = static_cast<uint32_t>(budget / per_sample);
-    if (batch == 0) batch = 1;
-    if (batch > nsamples) batch = nsamples;
-    // workspace: [zeroed per sub-batch: cursors[batch] | hdrs[batch][runs]] | qfirst[batch][257] | qlist[batch][runs] |
-    //            preg_n[batch * parts][256] | preg[batch * parts][256][pcap] | window arrays[batch][256][4][4^(K-4)] | arena[batch][runs][4 KiB]
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t head_bytes = up(static_cast<size_t>(batch) * (1 + runs) * sizeof(uint32_t));
-    const size_t list_bytes = up(static_cast<size_t>(batch) * (3 * kQuadBuckets + 1 + runs) * sizeof(uint32_t));   // qfirst | qlist | job sizes | job order
-    const size_t misc_bytes = up(static_cast<size_t>(batch) * preg_words * sizeof(uint32_t));
-    const size_t bh_bytes = static_cast<size_t>(batch) * kQuadBuckets * kOutWords * sizeof(uint32_t);
-    const size_t arena_bytes = static_cast<size_t>(batch) * runs * kRunBytes;
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_spill), &ctx->spill_cap, head_bytes + list_bytes + misc_bytes + bh_bytes + arena_bytes);
-    if (rc) return rc;
-    uint8_t* const base = reinterpret_cast<uint8_t*>(ctx->d_spill);
-    BucketParams bp{};
-    bp.cursors = ctx->d_spill;
-    bp.hdrs = ctx->d_spill + batch;
-    bp.qfirst = reinterpret_cast<uint32_t*>(base + head_bytes);
-    bp.qlist = bp.qfirst + static_cast<size_t>(batch) * (kQuadBuckets + 1);
-    bp.bsize = bp.qlist + static_cast<size_t>(batch) * runs;
-    bp.order = bp.bsize + static_cast<size_t>(batch) * kQuadBuckets;
-    bp.preg_n = reinterpret_cast<uint32_t*>(base + head_bytes + list_bytes);
-    bp.preg = bp.preg_n + static_cast<size_t>(batch) * parts * kQuadBuckets;
-    bp.preg_shift = pshift;
-    bp.parts = parts;
-    bp.bucket_hist = reinterpret_cast<uint32_t*>(base + head_bytes + list_bytes + misc_bytes);
-    bp.arena = base + head_bytes + list_bytes + misc_bytes + bh_bytes;
-    bp.runs_cap = static_cast<uint32_t>(runs);
-    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(nsamples) * NCODE * sizeof(uint32_t), ctx->stream));
-    ctx->last_block = kCountThreads;
-    ctx->last_lds = kLdsBucketBytes;
-    for (uint32_t s0 = 0; s0 < nsamples; s0 += batch) {
-        const uint32_t n = nsamples - s0 < batch ? nsamples - s0 : batch;
-        VK_HIP(ctx, hipMemsetAsync(ctx->d_spill, 0, head_bytes, ctx->stream));  // cursors and run headers
-        ctx->last_grid = n * parts;
-        uint32_t* const hist0 = d_hist + static_cast<size_t>(s0) * NCODE;
-        uint32_t* const wph0 = ctx->d_wavephase + static_cast<size_t>(s0) * parts * kWaves;
-        hipLaunchKernelGGL((vk_bucket_kernel<K, 3>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream,
-                           d_fastq, d_offs + s0, d_lens + s0, n, parts, hist0, wph0, bp, SubParams{}, PackParams{});
-        VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(vk_quad_list_kernel, dim3(n), dim3(1024), 0, ctx->stream, bp);
-        VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(vk_bucket_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, bp, n * kQuadBuckets);
-        VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL((vk_quad_count_kernel<K>), dim3(n * kQuadBuckets), dim3(512), 0, ctx->stream, bp);
-        VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL((vk_quad_merge_kernel<K>), dim3(n * (NCODE / kMergeTile)), dim3(256), 0, ctx->stream, bp, hist0);
-        VK_HIP(ctx, hipGetLastError());
-    }
-    return VK_OK;
-}
-
-// k = 8, 9: bucket pass + replay pass, in sub-batches that fit the spill budget.
-template <int K>
-int launch_spill(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, const uint64_t* d_lens,
-                 uint32_t nsamples, uint32_t parts, uint64_t maxlen, uint32_t* d_hist, const SubParams* sub) {
-    constexpr uint32_t NCODE = 1u << (2 * K);
-    if (sub == nullptr && !ctx->spill_packed && !ctx->spill_pairs)
-        return launch_spill_quad<K>(ctx, d_fastq, d_offs, d_lens, nsamples, parts, maxlen, d_hist);
-    // Arena of one sample, in 4 KiB runs: a pair entry is 2 bytes and a FASTQ holds at most len / 4
-    // pairs (sequence lines are less than half of the text), so len / 2 bytes however the pairs spread
-    // over the 16 buckets; plus the blocks a drain may leave unused at the end of a run (at most 3 of
-    // 64), plus one open run per (workgroup, wave, queue).
-    uint64_t runs = (maxlen / 2 + maxlen / 16) / kRunBytes + 16 + static_cast<uint64_t>(parts) * kWaves * (kQueues + kPoolRuns);   // (+ one open run per queue and one reserve per wave)
-    if (ctx->spill_runs_cap) runs = ctx->spill_runs_cap;  // VKIMG_SPILL_RUNS_CAP: tests force the arena-full fallback
-    if (runs >= (1u << 24)) return VK_EINVAL;             // a run number travels in 24 bits (64 GiB of entries per sample)
-    constexpr size_t kBucketHistBytes = static_cast<size_t>(kQueues) * (2u << (2 * K - 4)) * sizeof(uint32_t);  // pass B -> merge
-    // the packed stream of a sample (vk_pack.h): a record per 16 bytes of text at most, a few per wavefront on top
-    const bool packed = sub == nullptr && ctx->spill_packed;
-    const uint64_t pack_recs = packed ? ((maxlen + 15) / 16 + 8ull * parts * kWaves + 16 + 3) / 4 * 4 : 0;
-    const size_t per_sample = static_cast<size_t>(runs) * (kRunBytes + sizeof(uint32_t)) + sizeof(uint32_t) + 3 * kQueues * sizeof(uint32_t) + kBucketHistBytes +
-                              pack_recs * 8 + 64;
+// k = 8, 9: how many 4 KiB runs a sample's arena gets (*runs: in, what the route wants for its entries and open runs) and
+// how many samples a sub-batch holds.  `run_bytes`: a run with its header words, `fixed_bytes`: the rest of a sample's share.
+int spill_plan(vk_ctx* ctx, uint32_t nsamples, size_t run_bytes, size_t fixed_bytes, size_t* runs, size_t* batch_out) {
+    if (ctx->spill_runs_cap) *runs = ctx->spill_runs_cap;  // VKIMG_SPILL_RUNS_CAP: tests force the arena-full fallback
+    if (*runs >= (1u << 24)) return VK_EINVAL;             // a run number travels in 24 bits (64 GiB of entries per sample)
+    const size_t per_sample = *runs * run_bytes + fixed_bytes + 64;
     // never plan for more than three quarters of what is free (plus what this context already holds)
     size_t free_b = 0, total_b = 0;
     VK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -367,80 +380,160 @@ int launch_spill(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, co
     uint32_t batch = static_cast<uint32_t>(budget / per_sample);
     if (batch == 0) batch = 1;
     if (batch > nsamples) batch = nsamples;
-    // workspace: cursors[batch] | hdrs[batch][runs] | bucket sizes[batch][16] | job order[batch * 16] | wide flags[batch * 16] |
-    //            bucket histograms[batch][16][2 * 4^K / 16] | arena[batch][runs][4 KiB]
-    const size_t head_bytes = ((static_cast<size_t>(batch) * (1 + runs + 3 * kQueues)) * sizeof(uint32_t) + 255) / 256 * 256;
-    const size_t bh_bytes = static_cast<size_t>(batch) * kBucketHistBytes;
-    const size_t arena_bytes = static_cast<size_t>(batch) * runs * kRunBytes;
-    // packed stream: codes | masks (+ a block of slack: the last wavefront's loads run to the end of its last block) | sample bases | counts
-    const size_t pack_arr = packed ? (static_cast<size_t>(batch) * pack_recs + kPackBlock) * sizeof(uint32_t) : 0;
-    const size_t pack_meta = packed ? (static_cast<size_t>(batch) * sizeof(uint64_t) + static_cast<size_t>(batch) * parts * kWaves * sizeof(uint32_t) + 255) / 256 * 256 : 0;
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_spill), &ctx->spill_cap,
-                    head_bytes + bh_bytes + arena_bytes + 2 * pack_arr + pack_meta);
+    *batch_out = batch;
+    return VK_OK;
+}
+
+// The sub-batches of a k = 8, 9 count, `batch` samples at a time: the head of the workspace (cursors and run headers)
+// zeroed, then body(s0, n, hist0, wph0) for samples s0 .. s0 + n with their rows of d_hist and d_wavephase.
+template <int K, class F>
+int spill_batches(vk_ctx* ctx, const CtPlan& p, size_t batch, size_t head_bytes, uint32_t* d_hist, F&& body) {
+    constexpr uint32_t NCODE = 1u << (2 * K);
+    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(p.nsamples) * NCODE * sizeof(uint32_t), ctx->stream));
+    ctx->last_block = kCountThreads;
+    ctx->last_lds = kLdsBucketBytes;
+    for (uint32_t s0 = 0; s0 < p.nsamples; s0 += batch) {
+        const uint32_t n = p.nsamples - s0 < batch ? p.nsamples - s0 : static_cast<uint32_t>(batch);
+        VK_HIP(ctx, hipMemsetAsync(ctx->d_spill, 0, head_bytes, ctx->stream));
+        ctx->last_grid = n * p.parts;
+        const int rc = body(s0, n, d_hist + static_cast<size_t>(s0) * NCODE, ctx->d_wavephase + static_cast<size_t>(s0) * p.parts * kWaves);
+        if (rc) return rc;
+    }
+    return VK_OK;
+}
+
+// k = 8, 9, the quad route (vk_count.h: vk_bucket_kernel<K, 3>, vk_quad_list / _count / _merge_kernel),
+// in sub-batches that fit the spill budget.
+template <int K>
+int launch_spill_quad(vk_ctx* ctx, const CtPlan& p, uint32_t* d_hist) {
+    constexpr uint32_t NCODE = 1u << (2 * K);
+    constexpr size_t kOutWords = 4u << (2 * K - 8);   // what a pass B job stores: four window arrays of 4^(K-4) counters
+    const uint32_t parts = p.parts;
+    // the regions of quads of which only some windows count, one per (workgroup of pass A, bucket): ~1 per 215 bytes of
+    // 150-base reads over 256 buckets; room for four times that (uniform bases), at least 64
+    const uint64_t wg_bytes = p.maxlen / parts + 64 * kWaves;
+    uint32_t pshift = 6;                                   // (a power of two: the place is a shift and an or)
+    while (pshift < 21 && (1ull << pshift) < wg_bytes / 16384 + 64) ++pshift;   // (at most 2^21: a workgroup's 256 regions stay below 2^31 bytes, the size a buffer descriptor takes as an int; what does not fit is counted directly)
+    if (ctx->spill_misc_cap) pshift = ctx->spill_misc_cap < 21 ? ctx->spill_misc_cap : 21;   // VKIMG_SPILL_MISC_CAP (log2): tests force the region-full fallback
+    const uint64_t pcap = 1ull << pshift;
+    const size_t preg_words = static_cast<size_t>(parts) * kQuadBuckets * (pcap + 1);   // per sample: regions, populations
+    // Arena of one sample, in 4 KiB runs: a quad entry is 2 bytes and a FASTQ holds at most len / 8 quads (sequence
+    // lines are less than half of the text), so len / 4 bytes however they spread over the 256 buckets; plus the
+    // blocks a drain may leave unused at the end of a run, one open run per (workgroup, queue), one reserve per wave.
+    // A run has a header and a place in qlist; per sample on top: qfirst, job sizes and order, a cursor, pass B's tables, the regions.
+    size_t runs = (p.maxlen / 4 + p.maxlen / 32) / kRunBytes + 16 + static_cast<uint64_t>(parts) * (kQuadBuckets + kWaves * kPoolRuns), batch = 0;
+    int rc = spill_plan(ctx, p.nsamples, kRunBytes + 2 * sizeof(uint32_t),
+                        (3 * kQuadBuckets + 2) * sizeof(uint32_t) + kQuadBuckets * kOutWords * sizeof(uint32_t) + preg_words * sizeof(uint32_t), &runs, &batch);
     if (rc) return rc;
-    BucketParams bp;
-    bp.cursors = ctx->d_spill;
-    bp.hdrs = ctx->d_spill + batch;
-    bp.bsize = bp.hdrs + static_cast<size_t>(batch) * runs;
-    bp.order = bp.bsize + static_cast<size_t>(batch) * kQueues;
-    bp.wide = bp.order + static_cast<size_t>(batch) * kQueues;
-    bp.force_wide = ctx->spill_force_wide ? 1u : 0u;
-    bp.bucket_hist = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ctx->d_spill) + head_bytes);
-    bp.arena = reinterpret_cast<uint8_t*>(ctx->d_spill) + head_bytes + bh_bytes;
+    BucketParams bp{};
+    size_t head_bytes = 0;
+    rc = ws_carve(ctx, &ctx->d_spill, &ctx->spill_cap, [&](WsTake& take) {
+        take(bp.cursors, batch);
+        take(bp.hdrs, batch * runs);
+        head_bytes = take.at;   // zeroed per sub-batch: the cursors and run headers
+        take(bp.qfirst, batch * (kQuadBuckets + 1));
+        take(bp.qlist, batch * runs);
+        take(bp.bsize, batch * kQuadBuckets);   // job sizes
+        take(bp.order, batch * kQuadBuckets);   // job order
+        take(bp.preg_n, batch * parts * kQuadBuckets);
+        take(bp.preg, batch * parts * kQuadBuckets * pcap);
+        take(bp.bucket_hist, batch * kQuadBuckets * kOutWords);   // window arrays [batch][256][4][4^(K-4)]
+        take(bp.arena, batch * runs * kRunBytes);
+    });
+    if (rc) return rc;
+    bp.preg_shift = pshift;
+    bp.parts = parts;
     bp.runs_cap = static_cast<uint32_t>(runs);
+    return spill_batches<K>(ctx, p, batch, head_bytes, d_hist, [&](uint32_t s0, uint32_t n, uint32_t* hist0, uint32_t* wph0) {
+        hipLaunchKernelGGL((vk_bucket_kernel<K, 3>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream,
+                           p.fq, p.d_offs + s0, p.d_lens + s0, n, parts, hist0, wph0, bp, SubParams{}, PackParams{});
+        VK_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(vk_quad_list_kernel, dim3(n), dim3(1024), 0, ctx->stream, bp);
+        VK_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(vk_bucket_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, bp, n * kQuadBuckets);
+        VK_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL((vk_quad_count_kernel<K>), dim3(n * kQuadBuckets), dim3(512), 0, ctx->stream, bp);
+        VK_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL((vk_quad_merge_kernel<K>), dim3(n * (NCODE / kMergeTile)), dim3(256), 0, ctx->stream, bp, hist0);
+        VK_HIP(ctx, hipGetLastError());
+        return VK_OK;
+    });
+}
+
+// k = 8, 9: bucket pass + replay pass, in sub-batches that fit the spill budget.
+template <int K>
+int launch_spill(vk_ctx* ctx, const CtPlan& p, uint32_t* d_hist, const SubParams* sub) {
+    constexpr uint32_t NCODE = 1u << (2 * K);
+    if (sub == nullptr && !ctx->spill_packed && !ctx->spill_pairs) return launch_spill_quad<K>(ctx, p, d_hist);
+    const uint32_t parts = p.parts;
+    constexpr size_t kBucketHistWords = static_cast<size_t>(kQueues) * (2u << (2 * K - 4));  // pass B -> merge
+    // the packed stream of a sample (vk_pack.h): a record per 16 bytes of text at most, a few per wavefront on top
+    const bool packed = sub == nullptr && ctx->spill_packed;
+    const uint64_t pack_recs = packed ? ((p.maxlen + 15) / 16 + 8ull * parts * kWaves + 16 + 3) / 4 * 4 : 0;
+    // Arena of one sample, in 4 KiB runs: a pair entry is 2 bytes and a FASTQ holds at most len / 4
+    // pairs (sequence lines are less than half of the text), so len / 2 bytes however the pairs spread
+    // over the 16 buckets; plus the blocks a drain may leave unused at the end of a run (at most 3 of
+    // 64), plus one open run per (workgroup, wave, queue) and one reserve per wave.
+    // A run has a header; per sample on top: a cursor, job sizes, order and wide flags, pass B's tables, the packed stream.
+    size_t runs = (p.maxlen / 2 + p.maxlen / 16) / kRunBytes + 16 + static_cast<uint64_t>(parts) * kWaves * (kQueues + kPoolRuns), batch = 0;
+    int rc = spill_plan(ctx, p.nsamples, kRunBytes + sizeof(uint32_t),
+                        sizeof(uint32_t) + 3 * kQueues * sizeof(uint32_t) + kBucketHistWords * sizeof(uint32_t) + pack_recs * 8, &runs, &batch);
+    if (rc) return rc;
+    BucketParams bp{};
     PackParams pk{};
-    uint32_t aside_cap = 0;
-    uint32_t* d_aside_n = nullptr;
+    uint64_t* d_base = nullptr;
+    size_t head_bytes = 0;
+    rc = ws_carve(ctx, &ctx->d_spill, &ctx->spill_cap, [&](WsTake& take) {
+        take(bp.cursors, batch);
+        take(bp.hdrs, batch * runs);
+        take(bp.bsize, batch * kQueues);   // bucket sizes
+        take(bp.order, batch * kQueues);   // job order
+        take(bp.wide, batch * kQueues);    // wide flags
+        head_bytes = take.at;   // zeroed per sub-batch: all of the above
+        take(bp.bucket_hist, batch * kBucketHistWords);   // [batch][16][2 * 4^K / 16]
+        take(bp.arena, batch * runs * kRunBytes);
+        if (!packed) return;
+        // packed stream: codes | masks (+ a block of slack: the last wavefront's loads run to the end of its last block) | sample bases | counts
+        take(pk.c, batch * pack_recs + kPackBlock);
+        take(pk.m, batch * pack_recs + kPackBlock);
+        take(d_base, batch);
+        take(pk.count, batch * parts * kWaves);
+    });
+    if (rc) return rc;
+    bp.force_wide = ctx->spill_force_wide ? 1u : 0u;
+    bp.runs_cap = static_cast<uint32_t>(runs);
+    uint32_t aside_cap = 0, *d_aside_n = nullptr;
     if (packed) {
-        uint8_t* at = reinterpret_cast<uint8_t*>(ctx->d_spill) + head_bytes + bh_bytes + arena_bytes;
-        pk.c = reinterpret_cast<uint32_t*>(at);
-        pk.m = reinterpret_cast<uint32_t*>(at + pack_arr);
-        uint64_t* d_base = reinterpret_cast<uint64_t*>(at + 2 * pack_arr);
         pk.base = d_base;
-        pk.count = reinterpret_cast<uint32_t*>(d_base + batch);
         std::vector<uint64_t> base(batch);
         for (uint32_t i = 0; i < batch; ++i) base[i] = static_cast<uint64_t>(i) * pack_recs;
         VK_HIP(ctx, hipMemcpyAsync(d_base, base.data(), batch * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
         VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (base is a temporary; once per call)
-        // the waves' lists of lanes set aside, as for the k <= 7 kernel
-        const uint64_t wave_bytes = maxlen / (static_cast<uint64_t>(parts) * kWaves) + 64;
-        uint64_t cap = wave_bytes / kPiece + 64;
-        if (cap > (1u << 20)) cap = 1u << 20;
-        aside_cap = static_cast<uint32_t>(cap);
-        const size_t nwaves = static_cast<size_t>(batch) * parts * kWaves;
-        rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_aside), &ctx->aside_cap, nwaves * (cap + 1) * sizeof(uint32_t));
+        rc = aside_lists(ctx, p, batch * parts * kWaves, &aside_cap, &d_aside_n);   // as for the k <= 7 kernel
         if (rc) return rc;
-        d_aside_n = ctx->d_aside + nwaves * cap;
     }
-    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(nsamples) * NCODE * sizeof(uint32_t), ctx->stream));
-    ctx->last_block = kCountThreads;
-    ctx->last_lds = kLdsBucketBytes;
-    for (uint32_t s0 = 0; s0 < nsamples; s0 += batch) {
-        const uint32_t n = nsamples - s0 < batch ? nsamples - s0 : batch;
-        VK_HIP(ctx, hipMemsetAsync(ctx->d_spill, 0, head_bytes, ctx->stream));  // cursors and run headers
-        ctx->last_grid = n * parts;
-        uint32_t* const hist0 = d_hist + static_cast<size_t>(s0) * NCODE;
-        uint32_t* const wph0 = ctx->d_wavephase + static_cast<size_t>(s0) * parts * kWaves;
+    return spill_batches<K>(ctx, p, batch, head_bytes, d_hist, [&](uint32_t s0, uint32_t n, uint32_t* hist0, uint32_t* wph0) {
+        const uint64_t *const d_offs = p.d_offs + s0, *const d_lens = p.d_lens + s0;
         if (sub) {
-            SubParams sp = *sub;  // this sub-batch's slice of the per-sample arrays
-            sp.seeds += s0;
-            sp.thresholds += s0;
-            if (sp.sites) sp.sites += 2ull * s0;
+            SubParams ss = *sub;  // this sub-batch's slice of the per-sample arrays
+            ss.seeds += s0;
+            ss.thresholds += s0;
+            if (ss.sites) ss.sites += 2ull * s0;
             hipLaunchKernelGGL((vk_bucket_kernel<K, 1>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream,
-                               d_fastq, d_offs + s0, d_lens + s0, n, parts, hist0, wph0, bp, sp, PackParams{});
+                               p.fq, d_offs, d_lens, n, parts, hist0, wph0, bp, ss, PackParams{});
         } else if (packed) {
             // pass A in two kernels: the text packed once (the k <= 7 kernel's front end), the stream partitioned
-            hipLaunchKernelGGL(vk_pack_kernel, dim3(n * parts), dim3(kCountThreads), 0, ctx->stream, d_fastq, d_offs + s0,
-                               d_lens + s0, n, parts, pk, wph0, ctx->d_aside, aside_cap, d_aside_n);
+            hipLaunchKernelGGL(vk_pack_kernel, dim3(n * parts), dim3(kCountThreads), 0, ctx->stream, p.fq, d_offs,
+                               d_lens, n, parts, pk, wph0, ctx->d_aside, aside_cap, d_aside_n);
             VK_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL((vk_aside_kernel<K, false>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream, d_fastq,
-                               d_offs + s0, d_lens + s0, n, parts, hist0, ctx->d_aside, aside_cap, d_aside_n, IndexParams{}, 1u);
+            hipLaunchKernelGGL((vk_aside_kernel<K, false>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                               d_offs, d_lens, n, parts, hist0, ctx->d_aside, aside_cap, d_aside_n, IndexParams{}, 1u);
             VK_HIP(ctx, hipGetLastError());
             hipLaunchKernelGGL((vk_bucket_kernel<K, 2>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream,
-                               d_fastq, d_offs + s0, d_lens + s0, n, parts, hist0, wph0, bp, SubParams{}, pk);
+                               p.fq, d_offs, d_lens, n, parts, hist0, wph0, bp, SubParams{}, pk);
         } else {
             hipLaunchKernelGGL((vk_bucket_kernel<K, 0>), dim3(n * parts), dim3(kCountThreads), 0, ctx->stream,
-                               d_fastq, d_offs + s0, d_lens + s0, n, parts, hist0, wph0, bp, SubParams{}, PackParams{});
+                               p.fq, d_offs, d_lens, n, parts, hist0, wph0, bp, SubParams{}, PackParams{});
         }
         VK_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(vk_bucket_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, bp, n * kQueues);
@@ -450,11 +543,10 @@ int launch_spill(vk_ctx* ctx, const uint8_t* d_fastq, const uint64_t* d_offs, co
         // (jobs whose u16 pair counters wrapped: replayed into u32 window counters; every other workgroup leaves at once)
         hipLaunchKernelGGL((vk_bucket_count_wide_kernel<K>), dim3(n * kQueues), dim3(kCountThreads), 0, ctx->stream, bp);
         VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL((vk_bucket_merge_kernel<K>), dim3(n * (NCODE / 256)), dim3(256), 0, ctx->stream, bp,
-                           d_hist + static_cast<size_t>(s0) * NCODE);
+        hipLaunchKernelGGL((vk_bucket_merge_kernel<K>), dim3(n * (NCODE / 256)), dim3(256), 0, ctx->stream, bp, hist0);
         VK_HIP(ctx, hipGetLastError());
-    }
-    return VK_OK;
+        return VK_OK;
+    });
 }
 
 uint32_t choose_parts(uint32_t nsamples, uint64_t maxlen, int k) {
@@ -528,37 +620,23 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     vk_ctx* ctx = new (std::nothrow) vk_ctx();
     if (!ctx) return VK_ENOMEM;
     ctx->device = device;
-    {
-        const char* e = getenv("VKIMG_IMAGE_SORT_ONLY");
-        ctx->image_sort_only = e && e[0] == '1';
-        const char* g = getenv("VKIMG_GZ_NO_CHUNKS");
-        ctx->gz_no_chunks = g && g[0] == '1';
-        const char* cb = getenv("VKIMG_GZ_CHUNK_BYTES");
-        if (cb && cb[0]) ctx->gz_chunk_bytes = static_cast<uint32_t>(strtoul(cb, nullptr, 10));
-        const char* sf = getenv("VKIMG_GZ_SPLIT_FIND");
-        ctx->gz_split_find = sf && sf[0] == '1';
-        const char* fp = getenv("VKIMG_GZ_FILL");
-        if (fp && fp[0]) ctx->gz_fill_pct = static_cast<uint32_t>(strtoul(fp, nullptr, 10));
-        const char* lp = getenv("VKIMG_GZ_LDS_PAD");
-        if (lp && lp[0]) ctx->gz_lds_pad = static_cast<uint32_t>(strtoul(lp, nullptr, 10));
-        const char* r = getenv("VKIMG_SPILL_RUNS_CAP");
-        if (r && r[0]) ctx->spill_runs_cap = static_cast<uint32_t>(strtoul(r, nullptr, 10));
-        const char* tf = getenv("VKIMG_SPILL_PACKED");
-        ctx->spill_packed = tf && tf[0] == '1';
-        const char* mc = getenv("VKIMG_SPILL_MISC_CAP");
-        if (mc && mc[0]) ctx->spill_misc_cap = static_cast<uint32_t>(strtoul(mc, nullptr, 10));
-        const char* sq = getenv("VKIMG_SPILL_PAIRS");
-        ctx->spill_pairs = sq && sq[0] == '1';
-        const char* fw = getenv("VKIMG_SPILL_FORCE_WIDE");
-        ctx->spill_force_wide = fw && fw[0] == '1';
-        const char* hb = getenv("VKIMG_CLEAN_HASH_BITS");
-        if (hb && hb[0]) {
-            const unsigned long v = strtoul(hb, nullptr, 10);
-            ctx->clean_hash_bits = v >= 1 && v <= 64 ? static_cast<uint32_t>(v) : 64u;
-        }
-        const char* kc = getenv("VKIMG_K1_CLASSIC");
-        ctx->k1_classic = kc && kc[0] == '1';
-    }
+    ctx->image_sort_only = env_flag("VKIMG_IMAGE_SORT_ONLY");
+    ctx->gz_no_chunks = env_flag("VKIMG_GZ_NO_CHUNKS");
+    env_uint("VKIMG_GZ_CHUNK_BYTES", &ctx->gz_chunk_bytes);
+    ctx->gz_split_find = env_flag("VKIMG_GZ_SPLIT_FIND");
+    env_uint("VKIMG_GZ_FILL", &ctx->gz_fill_pct);
+    env_uint("VKIMG_GZ_LDS_PAD", &ctx->gz_lds_pad);
+    env_uint("VKIMG_SPILL_RUNS_CAP", &ctx->spill_runs_cap);
+    env_uint("VKIMG_SPILL_BUDGET", &ctx->spill_budget);
+    ctx->spill_packed = env_flag("VKIMG_SPILL_PACKED");
+    env_uint("VKIMG_SPILL_MISC_CAP", &ctx->spill_misc_cap);
+    ctx->spill_pairs = env_flag("VKIMG_SPILL_PAIRS");
+    ctx->spill_force_wide = env_flag("VKIMG_SPILL_FORCE_WIDE");
+    uint64_t hash_bits = 64;
+    env_uint("VKIMG_CLEAN_HASH_BITS", &hash_bits);
+    ctx->clean_hash_bits = hash_bits >= 1 && hash_bits <= 64 ? static_cast<uint32_t>(hash_bits) : 64u;
+    ctx->k1_classic = env_flag("VKIMG_K1_CLASSIC");
+    ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return VK_EHIP; }
     {
         int cus = 0;
@@ -687,18 +765,11 @@ int vk_set_mapping(vk_ctx* ctx, int k, const uint32_t* pix, uint32_t npix) {
 // holds an index of.  Returns VK_OK with *done = true when the walker ran.
 constexpr uint64_t kWalkMaxThresholdSpill = (1ull << 32) / 32;   // k = 8, 9: largest fraction of the reads (as a threshold) the walker takes
 
-template <int K>
-static void launch_walk(vk_ctx* ctx, const uint8_t* fq, const uint64_t* d_offs, const uint64_t* d_lens, uint32_t npairs,
-                        const WalkParams& wp, uint32_t* d_hist, int atomic_flush) {
-    hipLaunchKernelGGL((vk_walk_kernel<K>), dim3(npairs * wp.iparts), dim3(kCountThreads), 0, ctx->stream, fq, d_offs, d_lens, npairs,
-                       ctx->ix, wp, d_hist, atomic_flush);
-}
-
 static int count_walk(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples, int k,
                       uint32_t* d_hist, uint32_t* d_status, const uint64_t* seeds, const uint64_t* thresholds, uint64_t* d_sites,
                       bool* done) {
     *done = false;
-    if (ctx->ix_fastq != d_fastq || ctx->ix_sample.empty() || getenv("VKIMG_NO_READ_INDEX")) return VK_OK;
+    if (ctx->ix_fastq != d_fastq || ctx->ix_sample.empty() || ctx->no_read_index) return VK_OK;
     std::vector<uint32_t> isample(nsamples), status(nsamples);
     for (uint32_t i = 0; i < nsamples; ++i) {
         // k = 8, 9: the walker counts into the subsample's row in HBM, one atomic per window (~28 G/s measured): it beats a
@@ -712,16 +783,21 @@ static int count_walk(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets,
     }
     const uint32_t parts = ctx->ix_parts;
     if (static_cast<uint64_t>(nsamples) * parts > (1u << 24)) return VK_OK;
-    // per-pair arrays: offsets | lengths | seeds | thresholds (u64 each) | isample (u32)
-    const size_t need = static_cast<size_t>(nsamples) * (4 * sizeof(uint64_t) + sizeof(uint32_t)) + 64;
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_walk), &ctx->walk_cap, need);
+    // per-pair arrays
+    uint64_t *d_offs = nullptr, *d_lens = nullptr, *d_seeds = nullptr, *d_thr = nullptr;
+    uint32_t* d_is = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_walk, &ctx->walk_cap, [&](WsTake& take) {
+        take(d_offs, nsamples);
+        take(d_lens, nsamples);
+        take(d_seeds, nsamples);
+        take(d_thr, nsamples);
+        take(d_is, nsamples);
+    });
     if (rc) return rc;
-    uint64_t* d64 = reinterpret_cast<uint64_t*>(ctx->d_walk);
-    uint32_t* d_is = reinterpret_cast<uint32_t*>(d64 + 4ull * nsamples);
-    VK_HIP(ctx, hipMemcpyAsync(d64, offsets, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(d64 + nsamples, lengths, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(d64 + 2ull * nsamples, seeds, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(d64 + 3ull * nsamples, thresholds, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_offs, offsets, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_lens, lengths, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_seeds, seeds, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_thr, thresholds, nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipMemcpyAsync(d_is, isample.data(), nsamples * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipMemcpyAsync(d_status, status.data(), nsamples * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the host vectors are temporaries)
@@ -729,23 +805,15 @@ static int count_walk(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets,
     const int atomic_flush = (parts > 1 || k > 7) ? 1 : 0;
     if (atomic_flush)
         VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(nsamples) * (1ull << (2 * k)) * sizeof(uint32_t), ctx->stream));
-    WalkParams wp;
-    wp.isample = d_is;
-    wp.seeds = d64 + 2ull * nsamples;
-    wp.thresholds = d64 + 3ull * nsamples;
-    wp.sites = reinterpret_cast<unsigned long long*>(d_sites);
-    wp.iparts = parts;
-    const uint8_t* fq = static_cast<const uint8_t*>(d_fastq);
+    const WalkParams wp{d_is, d_seeds, d_thr, reinterpret_cast<unsigned long long*>(d_sites), parts};
     ctx->last_grid = nsamples * parts;
     ctx->last_block = kCountThreads;
     ctx->last_lds = (k <= 7 ? (1u << (2 * k)) * 4u : 4u) + kWaves * kWalkQueue * 4u;
-    switch (k) {
-        case 5: launch_walk<5>(ctx, fq, d64, d64 + nsamples, nsamples, wp, d_hist, atomic_flush); break;
-        case 6: launch_walk<6>(ctx, fq, d64, d64 + nsamples, nsamples, wp, d_hist, atomic_flush); break;
-        case 7: launch_walk<7>(ctx, fq, d64, d64 + nsamples, nsamples, wp, d_hist, atomic_flush); break;
-        case 8: launch_walk<8>(ctx, fq, d64, d64 + nsamples, nsamples, wp, d_hist, atomic_flush); break;
-        default: launch_walk<9>(ctx, fq, d64, d64 + nsamples, nsamples, wp, d_hist, atomic_flush); break;
-    }
+    with_k(k, [&](auto kc) {
+        hipLaunchKernelGGL((vk_walk_kernel<decltype(kc)::value>), dim3(nsamples * parts), dim3(kCountThreads), 0, ctx->stream,
+                           static_cast<const uint8_t*>(d_fastq), d_offs, d_lens, nsamples, ctx->ix, wp, d_hist, atomic_flush);
+        return VK_OK;
+    });
     VK_HIP(ctx, hipGetLastError());
     *done = true;
     return VK_OK;
@@ -758,44 +826,25 @@ static int count_impl(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets,
                       const uint64_t* seeds, const uint64_t* thresholds, uint64_t* d_sites) {
     if (!ctx || !offsets || !lengths || !d_hist || !d_status || k < 5 || k > 9) return VK_EINVAL;
     if (nsamples == 0) return VK_OK;
-    if (!d_fastq) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t maxlen = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
-        if (lengths[i] > maxlen) maxlen = lengths[i];
-    }
-    if ((reinterpret_cast<uintptr_t>(d_fastq) & 15u) != 0) return VK_EINVAL;
+    CtPlan p;
+    int rc = ct_check(ctx, d_fastq, offsets, lengths, nsamples, &p);
+    if (rc) return rc;
     if (seeds) {   // subsamples of samples the context holds a read index of: the walker (vk_ladder.h)
         bool done = false;
         const int rcw = count_walk(ctx, d_fastq, offsets, lengths, nsamples, k, d_hist, d_status, seeds, thresholds, d_sites, &done);
         if (rcw || done) return rcw;
     }
-    uint32_t parts = parts_per_sample ? parts_per_sample : choose_parts(nsamples, maxlen, k);
+    uint32_t parts = parts_per_sample ? parts_per_sample : choose_parts(nsamples, p.maxlen, k);
     if (!parts_per_sample && k >= 8 && seeds == nullptr && !ctx->spill_pairs && !ctx->spill_packed) {
         // The quad route's workgroups meet at barriers: twice as many, half as long, when that fills the chip's 512 slots as
         // well (100 samples: 5 -> 10 parts, 500 -> 1000 workgroups), ends a launch with less of a tail: 13.09 against 13.18 ms.
         const uint64_t g1 = static_cast<uint64_t>(nsamples) * parts, g2 = 2 * g1;
         const double e1 = static_cast<double>(g1) / static_cast<double>((g1 + 511) / 512 * 512);
         const double e2 = static_cast<double>(g2) / static_cast<double>((g2 + 511) / 512 * 512);
-        if (g2 <= 2048 && e2 >= e1 - 0.005 && maxlen / (2ull * parts) >= (1u << 20)) parts *= 2;
+        if (g2 <= 2048 && e2 >= e1 - 0.005 && p.maxlen / (2ull * parts) >= (1u << 20)) parts *= 2;
     }
-    // a wavefront addresses its byte range through a 32-bit buffer descriptor (vk_count.h, wave_stream):
-    // keep every range below 2 GiB, whatever the caller asked for
-    while (maxlen / (static_cast<uint64_t>(parts) * kWaves) >= (1ull << 31)) parts *= 2;
-    if (static_cast<uint64_t>(nsamples) * parts > (1u << 24)) return VK_EINVAL;
-
-    if (ctx->desc_cap < 2ull * nsamples * sizeof(uint64_t)) ctx->desc_n = 0;  // realloc drops the cached copy
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->desc_cap, 2ull * nsamples * sizeof(uint64_t));
+    rc = ct_split(ctx, offsets, lengths, parts, &p);
     if (rc) return rc;
-    rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_wavephase), &ctx->wavephase_cap,
-                static_cast<size_t>(nsamples) * parts * kWaves * sizeof(uint32_t));
-    if (rc) return rc;
-    uint64_t* d_offs = ctx->d_desc;
-    uint64_t* d_lens = ctx->d_desc + nsamples;
-    rc = upload_desc(ctx, offsets, lengths, nsamples);
-    if (rc) return rc;
-    const uint8_t* fq = static_cast<const uint8_t*>(d_fastq);
     SubParams sp{};
     const SubParams* sub = nullptr;
     if (seeds) {
@@ -811,21 +860,12 @@ static int count_impl(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets,
         sp.sites = reinterpret_cast<unsigned long long*>(d_sites);
         sub = &sp;
     }
-    switch (k) {
-        case 5: rc = launch_count<5>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, sub); break;
-        case 6: rc = launch_count<6>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, sub); break;
-        case 7: rc = launch_count<7>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, sub); break;
-        case 8: rc = launch_spill<8>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, sub); break;
-        default: rc = launch_spill<9>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, sub); break;
-    }
-    if (rc) return rc;
-    ctx->last_waves = static_cast<uint64_t>(nsamples) * parts * kWaves;
-    ctx->last_bytes = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) ctx->last_bytes += lengths[i];
-    hipLaunchKernelGGL(vk_check_kernel, dim3((nsamples + 255) / 256), dim3(256), 0, ctx->stream, fq, d_offs, d_lens,
-                       nsamples, parts, ctx->d_wavephase, d_status);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
+    rc = with_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if constexpr (K <= 7) return launch_count<K>(ctx, p, d_hist, sub);
+        else return launch_spill<K>(ctx, p, d_hist, sub);
+    });
+    return rc ? rc : ct_finish(ctx, p, lengths, d_status);
 }
 
 int vk_count_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths,
@@ -848,54 +888,40 @@ int vk_count_sampled_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* of
 
 namespace {
 
-// Workspace and descriptors of a read index over the samples of a call (vk_ladder.h): *ip describes it, *parts_out is the
-// split the index is laid out for.  The samples' descriptors are on the device (ctx->d_desc) on return.
+// Workspace and descriptors of a read index over the samples of a call (vk_ladder.h): *ip describes it, *p is the split
+// the index is laid out for.  The samples' descriptors are on the device (ctx->d_desc) on return.
 int index_prepare(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
-                  uint32_t parts_per_sample, IndexParams* ip, uint32_t* parts_out, uint64_t* maxlen_out) {
+                  uint32_t parts_per_sample, IndexParams* ip, CtPlan* p) {
     ctx->ix_fastq = nullptr;
     ctx->ix_sample.clear();
-    if (!d_fastq || (reinterpret_cast<uintptr_t>(d_fastq) & 15u) != 0) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t maxlen = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
-        if (lengths[i] > maxlen) maxlen = lengths[i];
-    }
+    int rc = ct_check(ctx, d_fastq, offsets, lengths, nsamples, p);
+    if (rc) return rc;
     // (the walker runs a workgroup per (subsample, part) of this split: the rule of rounds 2-5, one round of the chip)
-    uint32_t parts = parts_per_sample ? parts_per_sample : choose_parts(nsamples, maxlen, 9);
-    while (maxlen / (static_cast<uint64_t>(parts) * kWaves) >= (1ull << 31)) parts *= 2;
-    if (static_cast<uint64_t>(nsamples) * parts > (1u << 24)) return VK_EINVAL;
-    const size_t nwaves = static_cast<size_t>(nsamples) * parts * kWaves;
+    rc = ct_split(ctx, offsets, lengths, parts_per_sample ? parts_per_sample : choose_parts(nsamples, p->maxlen, 9), p);
+    if (rc) return rc;
     // anchors: a sample's region holds one per 32 bytes of text, and eight per wavefront on top
     std::vector<uint64_t> base(nsamples);
     uint64_t total = 0;
     for (uint32_t i = 0; i < nsamples; ++i) {
         base[i] = total;
-        total += lengths[i] / 32 + 8ull * parts * kWaves + 16;
+        total += lengths[i] / 32 + 8ull * p->parts * kWaves + 16;
     }
-    const size_t o_base = (total * sizeof(uint32_t) + 255) / 256 * 256, o_count = o_base + nsamples * sizeof(uint64_t),
-                 o_sites = (o_count + nwaves * sizeof(uint32_t) + 7) / 8 * 8, o_over = o_sites + nsamples * sizeof(uint64_t),
-                 bytes = o_over + nsamples * sizeof(uint32_t);
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_index), &ctx->index_cap, bytes + 256);
+    uint64_t* d_base = nullptr;
+    size_t zeroed = 0, end = 0;
+    rc = ws_carve(ctx, &ctx->d_index, &ctx->index_cap, [&](WsTake& take) {
+        take(ip->anchors, total);
+        take(d_base, nsamples);
+        take(ip->count, p->nwaves);
+        zeroed = take.at;   // cleared per call: the site counters and overflow flags
+        take(ip->sites, nsamples);
+        take(ip->overflow, nsamples);
+        end = take.at;
+    });
     if (rc) return rc;
-    if (ctx->desc_cap < 2ull * nsamples * sizeof(uint64_t)) ctx->desc_n = 0;
-    rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_desc), &ctx->desc_cap, 2ull * nsamples * sizeof(uint64_t));
-    if (rc) return rc;
-    rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_wavephase), &ctx->wavephase_cap, nwaves * sizeof(uint32_t));
-    if (rc) return rc;
-    rc = upload_desc(ctx, offsets, lengths, nsamples);
-    if (rc) return rc;
-    uint8_t* m = ctx->d_index;
-    ip->anchors = reinterpret_cast<uint32_t*>(m);
-    ip->base = reinterpret_cast<const uint64_t*>(m + o_base);
-    ip->count = reinterpret_cast<uint32_t*>(m + o_count);
-    ip->sites = reinterpret_cast<unsigned long long*>(m + o_sites);
-    ip->overflow = reinterpret_cast<uint32_t*>(m + o_over);
-    VK_HIP(ctx, hipMemcpyAsync(m + o_base, base.data(), nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    ip->base = d_base;
+    VK_HIP(ctx, hipMemcpyAsync(d_base, base.data(), nsamples * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (base is a temporary)
-    VK_HIP(ctx, hipMemsetAsync(m + o_sites, 0, bytes - o_sites, ctx->stream));
-    *parts_out = parts;
-    *maxlen_out = maxlen;
+    VK_HIP(ctx, hipMemsetAsync(ctx->d_index + zeroed, 0, end - zeroed, ctx->stream));
     return VK_OK;
 }
 
@@ -930,20 +956,17 @@ int vk_read_index_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offse
     ctx->ix_sample.clear();
     if (nsamples == 0) return VK_OK;
     IndexParams ip;
-    uint32_t parts = 0;
-    uint64_t maxlen = 0;
-    int rc = index_prepare(ctx, d_fastq, offsets, lengths, nsamples, parts_per_sample, &ip, &parts, &maxlen);
+    CtPlan p;
+    int rc = index_prepare(ctx, d_fastq, offsets, lengths, nsamples, parts_per_sample, &ip, &p);
     if (rc) return rc;
     rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_status1), &ctx->status1_cap, nsamples * sizeof(uint32_t) + 64);
     if (rc) return rc;
-    const uint8_t* fq = static_cast<const uint8_t*>(d_fastq);
-    hipLaunchKernelGGL(vk_index_kernel, dim3(nsamples * parts), dim3(kCountThreads), 0, ctx->stream, fq, ctx->d_desc, ctx->d_desc + nsamples,
-                       nsamples, parts, ip, ctx->d_wavephase);
+    hipLaunchKernelGGL(vk_index_kernel, dim3(nsamples * p.parts), dim3(kCountThreads), 0, ctx->stream, p.fq, p.d_offs, p.d_lens,
+                       nsamples, p.parts, ip, ctx->d_wavephase);
     VK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(vk_check_kernel, dim3((nsamples + 255) / 256), dim3(256), 0, ctx->stream, fq, ctx->d_desc, ctx->d_desc + nsamples,
-                       nsamples, parts, ctx->d_wavephase, ctx->d_status1);
-    VK_HIP(ctx, hipGetLastError());
-    return index_finish(ctx, d_fastq, offsets, lengths, nsamples, ip, parts, ctx->d_status1, sites, status);
+    rc = ct_finish(ctx, p, nullptr, ctx->d_status1);
+    if (rc) return rc;
+    return index_finish(ctx, d_fastq, offsets, lengths, nsamples, ip, p.parts, ctx->d_status1, sites, status);
 }
 
 int vk_count_index_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples, int k,
@@ -958,26 +981,18 @@ int vk_count_index_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offs
         return vk_count_device(ctx, d_fastq, offsets, lengths, nsamples, k, parts_per_sample, d_hist, d_status);
     }
     IndexParams ip;
-    uint32_t parts = 0;
-    uint64_t maxlen = 0;
-    int rc = index_prepare(ctx, d_fastq, offsets, lengths, nsamples, parts_per_sample, &ip, &parts, &maxlen);
+    CtPlan p;
+    int rc = index_prepare(ctx, d_fastq, offsets, lengths, nsamples, parts_per_sample, &ip, &p);
     if (rc) return rc;
-    const uint8_t* fq = static_cast<const uint8_t*>(d_fastq);
-    uint64_t* d_offs = ctx->d_desc;
-    uint64_t* d_lens = ctx->d_desc + nsamples;
-    switch (k) {
-        case 5: rc = launch_count<5>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, nullptr, &ip); break;
-        case 6: rc = launch_count<6>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, nullptr, &ip); break;
-        default: rc = launch_count<7>(ctx, fq, d_offs, d_lens, nsamples, parts, maxlen, d_hist, nullptr, &ip); break;
-    }
+    rc = with_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if constexpr (K <= 7) return launch_count<K>(ctx, p, d_hist, nullptr, &ip);
+        else return VK_EINVAL;   // (handled above)
+    });
     if (rc) return rc;
-    ctx->last_waves = static_cast<uint64_t>(nsamples) * parts * kWaves;
-    ctx->last_bytes = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) ctx->last_bytes += lengths[i];
-    hipLaunchKernelGGL(vk_check_kernel, dim3((nsamples + 255) / 256), dim3(256), 0, ctx->stream, fq, d_offs, d_lens,
-                       nsamples, parts, ctx->d_wavephase, d_status);
-    VK_HIP(ctx, hipGetLastError());
-    return index_finish(ctx, d_fastq, offsets, lengths, nsamples, ip, parts, d_status, sites, status);
+    rc = ct_finish(ctx, p, lengths, d_status);
+    if (rc) return rc;
+    return index_finish(ctx, d_fastq, offsets, lengths, nsamples, ip, p.parts, d_status, sites, status);
 }
 
 int vk_image_device(vk_ctx* ctx, const uint32_t* d_hist, uint32_t nsamples, int k, uint8_t* d_img) {
@@ -1610,19 +1625,6 @@ int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uin
 
 namespace {
 
-size_t cl_align(size_t x) { return (x + 255) / 256 * 256; }
-
-// Hands out the pieces of a workspace one after another, each at a multiple of 256 bytes.  A piece is stated once: the
-// typed pointer it fills and its element count.  Without a base only the sizes add up (the *_workspace_size calls).
-struct ClTake {
-    uint8_t* base;
-    size_t at;
-    template <class T> void operator()(T*& piece, size_t count) {
-        piece = base ? reinterpret_cast<T*>(base + at) : nullptr;
-        at += cl_align(count * sizeof(T));
-    }
-};
-
 // the pieces of a vk_clean_device workspace
 struct ClLayout {
     ClFile* files;
@@ -1644,7 +1646,7 @@ ClLayout cl_layout(void* d_ws, const uint64_t* lengths, const uint64_t* records,
     L.nslots = 1024;
     while (L.nslots < 2 * L.nrec) L.nslots <<= 1;
     const uint64_t nb = std::max((L.nchunks + kClScanBlock - 1) / kClScanBlock, (L.nrec + kClScanBlock - 1) / kClScanBlock);
-    ClTake take{static_cast<uint8_t*>(d_ws), 0};
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
     take(L.files, nfiles);
     take(L.fchunk, nfiles);
     take(L.samples, nsamples);
@@ -1679,7 +1681,7 @@ AdLayout ad_layout(void* d_ws, const uint64_t* lengths, const uint64_t* records,
     AdLayout L{};
     L.c = cl_layout(d_ws, lengths, records, nfiles, nsamples);
     L.slice = static_cast<uint32_t>(std::min<uint64_t>(kAdSlice, 3ull * nsamples));
-    ClTake take{static_cast<uint8_t*>(d_ws), L.c.total};
+    WsTake take{static_cast<uint8_t*>(d_ws), L.c.total};
     take(L.hist, static_cast<size_t>(L.slice) * kAdKeys);
     take(L.groups, L.slice);
     take(L.gbase, L.slice + 1ull);
@@ -1938,7 +1940,7 @@ int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
         if (offsets[i] % 16) return VK_EINVAL;
     const ClIndex ix = cl_index(offsets, lengths, nullptr, nullptr, nullptr, nfiles, 0, 0);
     VK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_chunk = cl_align(nfiles * sizeof(ClFile)), o_lines = o_chunk + cl_align(nfiles * 8ull);
+    const size_t o_chunk = ws_align(nfiles * sizeof(ClFile)), o_lines = o_chunk + ws_align(nfiles * 8ull);
     int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, o_lines + nfiles * 8ull);
     if (rc) return rc;
     uint8_t* m = ctx->d_clines;
@@ -2039,10 +2041,10 @@ int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offs
         const uint64_t nocc = ad_candidates(rk, tot, cand);
         if (nocc == 0) continue;
         rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_cldetect), &ctx->cldetect_cap,
-                    cl_align(nocc * sizeof(AdOcc)) + nocc * sizeof(uint16_t));
+                    ws_align(nocc * sizeof(AdOcc)) + nocc * sizeof(uint16_t));
         if (rc) return rc;
         auto* occ = reinterpret_cast<AdOcc*>(ctx->d_cldetect);
-        auto* state = reinterpret_cast<uint16_t*>(ctx->d_cldetect + cl_align(nocc * sizeof(AdOcc)));
+        auto* state = reinterpret_cast<uint16_t*>(ctx->d_cldetect + ws_align(nocc * sizeof(AdOcc)));
         VK_HIP(ctx, hipMemcpyAsync(L.cands, cand.data(), cand.size() * sizeof(AdCand), hipMemcpyHostToDevice, ctx->stream));
         VK_HIP(ctx, hipMemsetAsync(L.counts, 0, cand.size() * 4, ctx->stream));
         hipLaunchKernelGGL(vk_ad_collect_kernel, dim3((nrec + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
