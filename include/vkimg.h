@@ -229,6 +229,12 @@ int vk_host_unregister(vk_ctx* ctx, const void* p);
  * vk_clean_lines_device: lines[i] (host) = the '\n' bytes of file i, d_text[offsets[i] .. +lengths[i]) -- `wc -l`
  * of count_total_reads (:117-160), whose // 4 is the file's read count.  Synchronises.
  *
+ * vk_clean_heads_device: replaces estimate_read_lengths (:90-115) reading each file's first sample_size records on
+ * the host.  totals[i] and counted[i] (host) = the sum of the lengths and the number of the sequence lines that it
+ * samples in file i: of the pieces between '\n' bytes (the last one ends with the file), pieces 1, 5, 9, ... up to
+ * sample_size (>= 1) of them, each without the space, \t, \n, \v, \f and \r bytes at its ends.  The mean read length
+ * is totals[i] / counted[i].  A file is read from its start only as far as its last sampled line.  Synchronises once.
+ *
  * vk_clean_device: file i belongs to sample samples[i] as roles[i] (VK_CL_ROLE_*) and gives its first records[i]
  * records (the read budget of calculate_reads_needed, :164-221; the caller computes it).  A sample's R1 records,
  * in the order its R1 files are listed, pair up with its R2 records in the order of its R2 files.  flags:
@@ -251,6 +257,8 @@ int vk_host_unregister(vk_ctx* ctx, const void* p);
 #define VK_CL_NSTAT 202
 int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
                           uint32_t nfiles, uint64_t* lines);
+int vk_clean_heads_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                          uint32_t nfiles, uint32_t sample_size, uint64_t* totals, uint64_t* counted);
 int vk_clean_workspace_size(const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples,
                             uint64_t* bytes);
 int vk_clean_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,

@@ -22,7 +22,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_last_count_launch", "vk_count_sampled_device", "vk_inflate_device", "vk_upload_mapped", "vk_host_register", "vk_host_unregister",
            "vk_synth_shaped_lengths", "vk_synth_shaped_device", "vk_last_count_general", "vk_read_index_device", "vk_count_index_device",
            "vk_clean_lines_device", "vk_clean_workspace_size", "vk_clean_device", "vk_clean_detect_workspace_size",
-           "vk_clean_detect_device", "vk_clean_adapters_device")
+           "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device")
 
 _lib = None
 
@@ -71,6 +71,7 @@ def lib():
     L.vk_read_index_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_uint32, u64p, u32p]
     L.vk_count_index_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, vp, vp, u64p, u32p]
     L.vk_clean_lines_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, u64p]
+    L.vk_clean_heads_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_uint32, u64p, u64p]
     L.vk_clean_workspace_size.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, u64p]
     L.vk_clean_device.argtypes = [vp, vp, u64p, u64p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint32, vp, C.c_uint64, vp, u64p, C.c_uint64, vp, vp, vp]

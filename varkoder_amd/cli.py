@@ -11,6 +11,9 @@ the GPU (rules: INTEGRATION.md, "Step B"; -a/-D/-r/-T take effect, -M sets the r
 without leaving the device; with `-i INT` the cleaned reads and their base-content report are also written to
 `INT/clean_reads/` (and reused there by a later run unless -x).  `stats.csv` (and `labels.csv` with -t) are written
 like process_stats does (commands/image.py:1144-1185).  With torchrun, ranks shard the files (samples).
+
+`python -m varkoder_amd query ...`: `varKoder query` (run_query); with `--from-raw` from raw reads, cleaned on the GPU
+like `image --from-raw`.
 """
 import argparse
 import math
@@ -24,6 +27,18 @@ from . import __version__
 from .config import (DEFAULT_KMER_MAPPING, DEFAULT_KMER_SIZE, KMER_MAX, KMER_MIN, LABELS_SEP, MAPPING_CHOICES,
                      QUAL_THRESH, SAMPLE_BP_SEP)
 from .image import eprint
+
+
+def add_adapter_flags(p):
+    """The adapters-by-sequence flags of `image` and `query` (parse_args refuses them without --from-raw or with -a)."""
+    # (SUPPRESS: a namespace without these flags is the one from before they existed; read them with getattr)
+    p.add_argument("--detect-adapters", action="store_true", default=argparse.SUPPRESS,
+                   help="with --from-raw: also detect each read group's adapter from its first reads and trim it by "
+                        "sequence (fastp's adapter detection, as INTEGRATION.md restates it)")
+    p.add_argument("--adapter-sequence", default=argparse.SUPPRESS, metavar="SEQ",
+                   help="with --from-raw: trim R1 and single reads by this adapter (4-64 bases of ACGT)")
+    p.add_argument("--adapter-sequence-r2", default=argparse.SUPPRESS, metavar="SEQ",
+                   help="with --from-raw: trim R2 by this adapter (default: --adapter-sequence)")
 
 
 def setup_parser():
@@ -66,18 +81,12 @@ def setup_parser():
     entry.add_argument("--from-raw", action="store_true",
                        help="input holds RAW reads (`<taxon>/<sample>/*.fq[.gz]` or a CSV labels,sample,files): clean them "
                             "on the GPU (step B, the reference's fastp pass) and go on with the ladder")
-    # (SUPPRESS: a namespace without these flags is the one from before they existed; read them with getattr)
-    p.add_argument("--detect-adapters", action="store_true", default=argparse.SUPPRESS,
-                   help="with --from-raw: also detect each read group's adapter from its first reads and trim it by "
-                        "sequence (fastp's adapter detection, as INTEGRATION.md restates it)")
-    p.add_argument("--adapter-sequence", default=argparse.SUPPRESS, metavar="SEQ",
-                   help="with --from-raw: trim R1 and single reads by this adapter (4-64 bases of ACGT)")
-    p.add_argument("--adapter-sequence-r2", default=argparse.SUPPRESS, metavar="SEQ",
-                   help="with --from-raw: trim R2 by this adapter (default: --adapter-sequence)")
+    add_adapter_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
-                       help="Query cleaned reads or images against a trained network (cli.py:327-446).")
-    q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads) or, with "
-                                 "--images, with varKode / rfCGR png files")
+                       help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
+    q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads); with --from-raw, "
+                                 "with raw reads (one file per sample, or one sub-folder per sample); with --images, "
+                                 "with varKode / rfCGR png files")
     q.add_argument("outdir", help="path to the folder where results will be saved.")
     q.add_argument("-R", "--seed", type=int, help="random seed.")
     q.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
@@ -88,7 +97,8 @@ def setup_parser():
     q.add_argument("--single-label", action="store_true", help="softmax + best label instead of sigmoid >= threshold")
     q.add_argument("--input-size", type=int, default=224, help="side of the model's input (squish, BOX filter)")
     q.add_argument("--half", action="store_true", help="run the model under fp16 autocast")
-    q.add_argument("-1", "--no-pairs", action="store_true", help="accepted for parity")
+    q.add_argument("-1", "--no-pairs", action="store_true",
+                   help="accepted for parity and inert: the reference's input listing never reads it either")
     q.add_argument("-I", "--images", action="store_true", help="input folder contains processed images instead of reads.")
     q.add_argument("-k", "--kmer-size", type=int, default=DEFAULT_KMER_SIZE, help="size of kmers to count (5-9)")
     q.add_argument("-p", "--kmer-mapping", type=str, default=DEFAULT_KMER_MAPPING, choices=MAPPING_CHOICES)
@@ -96,17 +106,24 @@ def setup_parser():
     q.add_argument("-c", "--cpus-per-thread", type=int, default=1, help="accepted for parity, unused")
     q.add_argument("-f", "--stats-file", default="stats.csv", help="path to file where sample statistics will be saved.")
     q.add_argument("-d", "--threshold", type=float, default=0.7, help="confidence threshold to make a prediction.")
-    q.add_argument("-i", "--int-folder", help="accepted for parity")
+    q.add_argument("-i", "--int-folder", help="with --from-raw: folder for the cleaned reads (clean_reads/), reused by a "
+                                              "later run unless -x; otherwise accepted for parity")
     q.add_argument("-m", "--keep-images", action="store_true",
                    help="whether barcode images should be saved to a directory named 'query_images'.")
     q.add_argument("-P", "--include-probs", action="store_true",
                    help="whether probabilities for each label should be included in the output.")
-    q.add_argument("-a", "--no-adapter", action="store_true", help="upstream (fastp) option; accepted for parity")
-    q.add_argument("-r", "--no-merge", action="store_true", help="upstream (fastp) option; accepted for parity")
-    q.add_argument("-D", "--no-deduplicate", action="store_true", help="upstream (fastp) option; accepted for parity")
-    q.add_argument("-T", "--trim-bp", default="10,10", help="upstream (fastp) option; accepted for parity")
+    q.add_argument("-a", "--no-adapter", action="store_true", help="with --from-raw: no adapter trimming; otherwise accepted for parity")
+    q.add_argument("-r", "--no-merge", action="store_true", help="with --from-raw: no merging of read pairs; otherwise accepted for parity")
+    q.add_argument("-D", "--no-deduplicate", action="store_true", help="with --from-raw: no deduplication; otherwise accepted for parity")
+    q.add_argument("-T", "--trim-bp", default="10,10",
+                   help="with --from-raw: bases trimmed from the front and the tail of every read; otherwise accepted for parity")
     q.add_argument("-M", "--max-bp", default="200M",
-                   help="number of post-cleaning basepairs to use for making image. Use '0' to use all of the available data.")
+                   help="number of post-cleaning basepairs to use for making image (and, --from-raw, 5x of it the read "
+                        "budget). Use '0' to use all of the available data.")
+    q.add_argument("--from-raw", action="store_true",
+                   help="input holds RAW reads, as the reference's `query` takes them: clean them on the GPU (step B, the "
+                        "reference's fastp pass), subsample, image and predict without leaving the device")
+    add_adapter_flags(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Convert images between different kmer mappings.")          # cli.py:447-482
@@ -133,11 +150,13 @@ ADAPTER_FLAGS = (("detect_adapters", "--detect-adapters"), ("adapter_sequence", 
 
 
 def parse_args(argv=None):
-    """The parsed command line; the adapter flags of `image` are refused (exit 2) without --from-raw or with -a, and
-    their sequences are checked."""
+    """The parsed command line; the adapter flags of `image` and `query` are refused (exit 2) without --from-raw or
+    with -a, and their sequences are checked."""
     parser = setup_parser()
     args = parser.parse_args(argv)
-    if args.command == "image":
+    if args.command == "query" and args.from_raw and args.images:
+        parser.error("--from-raw: not with -I/--images")
+    if args.command in ("image", "query"):
         given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
         if given and not args.from_raw:
             parser.error(f"{', '.join(given)}: only with --from-raw")
@@ -162,7 +181,11 @@ def run_convert(args):
 
 def run_query(args):
     """`varKoder query` from step C on (commands/query.py:188-324): images are made on the GPU and
-    stay there for the model's input transform; predictions.csv has the reference's columns.
+    stay there for the model's input transform; predictions.csv has the reference's columns.  With --from-raw from
+    step B on, like the reference's own default (prepare_images, :97-178): the input is listed by
+    rawinput.process_input(is_query=True), cleaned, subsampled once and counted by pipeline.raw_to_query, and each
+    row carries what its image's text chunks would hold (label `query`, the sample's base-frequency sd).  The
+    reference writes no stats.csv for a query; neither does this.
     Under a launcher (one process per GPU) the inputs are sharded by size over the ranks (shard.shard_by_size) -- every rank
     makes its images and runs the model on its GPU -- and rank 0 writes predictions.csv in input order
     (BASELINE config 5: images + batched inference on 8 GPUs; no data-path collective, one object gather)."""
@@ -179,8 +202,11 @@ def run_query(args):
     outdir = Path(args.outdir)
     if not args.overwrite and (outdir / "predictions.csv").exists():
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
+    from_raw = getattr(args, "from_raw", False)
     if args.images:
         inputs = sorted(Path(args.input).rglob("*.png"))
+    elif from_raw:
+        inputs = RawQueryPlan(args)   # (no collective in it, nothing on the GPU: an input error leaves every rank here)
     else:
         src = Path(args.input)
         if (src / "clean_reads").is_dir():
@@ -196,15 +222,45 @@ def run_query(args):
     # closing barrier; the exception is raised after the process group is gone.
     state = {"eng": None}
     model = vocab = None
-    weights = agreed_weights(inputs)   # (a collective: outside the try block, every rank is still here)
+    # (collectives: outside the try block, every rank is still here)
+    if from_raw:
+        raw_weights, clean_weights = inputs.agree_weights()
+    else:
+        weights = agreed_weights(inputs)
 
     def rank_work():
         nonlocal model, vocab
-        mine = shard_by_size(weights, rank, world)
         model, vocab = Q.load_model(args.model), Q.read_vocab(args.vocab)
         records, images, order = [], None, []   # order: index of each record's input in `inputs`
         eng = None
-        if args.images:
+        mine = [] if from_raw else shard_by_size(weights, rank, world)
+        if from_raw:
+            eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
+            found = inputs.run(eng, raw_weights, clean_weights, rank, world)
+            hists, keep = [], []
+            for i, sample in enumerate(inputs.samples):
+                if sample not in found:
+                    continue
+                bp, hist, sd = found[sample]
+                name = split_name(sample, bp) + f"+{args.kmer_mapping}+k{args.kmer_size}.png"
+                path = str(outdir / "query_images" / name) if args.keep_images else name
+                # what write_png puts into the image's text chunks, read back as a query of that image reads it
+                labels, qual, freq_sd = Q.image_metadata({"varkoderKeywords": LABELS_SEP.join(inputs.labels),
+                                                          "varkoderBaseFreqSd": str(sd),
+                                                          "varkoderLowQualityFlag": str(sd > QUAL_THRESH)})
+                records.append(dict(path=path, sample=sample, bp=int(bp / 1000) * 1000, k=args.kmer_size,
+                                    mapping=args.kmer_mapping, labels=labels, qual=qual, freq_sd=freq_sd))
+                hists.append(hist)
+                keep.append((name, sd))
+                order.append(i)
+            if hists:
+                images = eng.images(torch.stack(hists))
+                if args.keep_images:
+                    (outdir / "query_images").mkdir(parents=True, exist_ok=True)
+                    host = images.cpu().numpy()
+                    for j, (name, sd) in enumerate(keep):
+                        write_png(host[j], outdir / "query_images" / name, inputs.labels, sd, QUAL_THRESH, args.kmer_mapping)
+        elif args.images:
             arrays = []
             for i in mine:
                 p = inputs[i]
@@ -298,6 +354,76 @@ def run_query(args):
         dist.destroy_process_group()
     if failure is not None:
         raise failure
+
+
+class RawQueryPlan:
+    """What `query --from-raw` works on: the input table (rawinput.process_input with is_query), one seed per sample
+    in table order (image.py:1017, drawn for every sample on every rank), the cleaning options, and which samples
+    an earlier run with the same -i has cleaned already.  len() = the samples."""
+    labels = ["query"]
+
+    def __init__(self, args):
+        import numpy as np
+        from .rawinput import process_input
+        src = Path(args.input)
+        if list(src.glob("*.png")):                                           # query.py:111-120
+            eprint("ERROR: Found PNG files in input directory.")
+            eprint("If your input directory contains pre-generated images, use the --images flag:")
+            eprint("    varkoder_amd query --images " + str(src) + " " + str(args.outdir))
+            raise Exception("Input directory contains PNG files. Use --images flag for pre-generated images.")
+        table = process_input(src, is_query=True)
+        self.args = args
+        self.samples = [s for s, _, _ in table]
+        rng = np.random.default_rng(args.seed)
+        self.seeds = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(self.samples)}
+        self.clean_dir = Path(args.int_folder) / "clean_reads" if args.int_folder else None
+        # a cleaned file from an earlier run is used as it is (clean_reads, commands/image.py:350-352)
+        reuse = {s for s in self.samples
+                 if self.clean_dir is not None and not args.overwrite and (self.clean_dir / (s + ".fq.gz")).is_file()}
+        for s in sorted(reuse):
+            eprint("Skipping cleaning for", s + ":", "File exists.")
+        self.raw = [(s, files) for s, _, files in table if s not in reuse]
+        self.reused = sorted(reuse)
+
+    def __len__(self):
+        return len(self.samples)
+
+    def agree_weights(self):
+        """(weight of each raw sample -- the sum of its files' --, weight of each reused cleaned file) as every rank
+        uses them: collectives."""
+        from .shard import agreed_weights
+        every = [f for _, files in self.raw for f in files]
+        fw = agreed_weights(every) if every else []
+        weights, at = [], 0
+        for _, files in self.raw:
+            weights.append(sum(fw[at:at + len(files)]))
+            at += len(files)
+        done = [self.clean_dir / (s + ".fq.gz") for s in self.reused]
+        return weights, (agreed_weights(done) if done else [])
+
+    def run(self, eng, raw_weights, clean_weights, rank, world):
+        """{sample: (bp, histogram on the device, base-frequency sd)} of this rank's share."""
+        from .image import base_sd_table
+        from .pipeline import clean_to_query, raw_to_query
+        from .shard import io_threads_per_rank, shard_by_size
+        args = self.args
+        max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)     # cli.py:496-501
+        front, tail = (int(x) for x in str(args.trim_bp).split(","))
+        a1, a2 = getattr(args, "adapter_sequence", None), getattr(args, "adapter_sequence_r2", None)
+        common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp, seeds=self.seeds, engine=eng,
+                      io_threads=io_threads_per_rank(args.n_threads))
+        found = {}
+        if self.raw:
+            found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, trim=(front, tail),
+                                      adapter=not args.no_adapter, merge=not args.no_merge, dedup=not args.no_deduplicate,
+                                      clean_dir=self.clean_dir, verbose=args.verbose,
+                                      adapters=(a1, a2) if a1 is not None or a2 is not None else None,
+                                      detect_adapters=getattr(args, "detect_adapters", False), **common))
+        mine = [self.reused[i] for i in shard_by_size(clean_weights, rank, world)]
+        if mine:
+            found.update(clean_to_query([(s, self.clean_dir / (s + ".fq.gz")) for s in mine],
+                                        base_sd=base_sd_table(self.clean_dir, mine), **common))
+        return found
 
 
 def read_labels(path):

@@ -193,20 +193,14 @@ __global__ void __launch_bounds__(kClThreads) vk_cl_init_kernel(const ClSample* 
         stats[i] = 0;
 }
 
-// newlines of this lane's 64 bytes of chunk c (bytes at and past `valid` not counted); the bytes are kept in w
-__device__ inline uint32_t cl_chunk_lane(const uint8_t* text, const ClFile* files, const uint64_t* chunk_base,
-                                         uint32_t nfiles, uint64_t c, uint32_t* f_out, uint64_t* pos_out, uint32_t w[16]) {
-    const uint32_t f = cl_find_u64(chunk_base, nfiles, c);
-    const ClFile fd = files[f];
-    const uint64_t cstart = (c - fd.chunk0) * kClChunk;
-    const uint64_t pos = cstart + threadIdx.x * 64ull;
-    *f_out = f;
-    *pos_out = pos;
+// newlines of this lane's 64 bytes at `pos` of a file of `len` bytes (bytes at and past `len` not counted); the bytes
+// are kept in w
+__device__ inline uint32_t cl_lane_newlines(const uint8_t* file, uint64_t len, uint64_t pos, uint32_t w[16]) {
     uint32_t cnt = 0;
     for (uint32_t q = 0; q < 4; ++q) {
         const uint64_t p = pos + q * 16;
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (p < fd.len) v = *reinterpret_cast<const uint4*>(text + fd.off + p);   // (16-byte aligned; readable to the rounded end)
+        if (p < len) v = *reinterpret_cast<const uint4*>(file + p);   // (16-byte aligned; readable to the rounded end)
         w[4 * q] = v.x;
         w[4 * q + 1] = v.y;
         w[4 * q + 2] = v.z;
@@ -214,12 +208,23 @@ __device__ inline uint32_t cl_chunk_lane(const uint8_t* text, const ClFile* file
         for (uint32_t j = 0; j < 4; ++j) {
             const uint64_t pj = p + 4 * j;
             uint32_t m = cl_nl_in(w[4 * q + j]);
-            if (pj >= fd.len) m = 0;
-            else if (fd.len - pj < 4) m &= (1u << (8 * (fd.len - pj))) - 1u;
+            if (pj >= len) m = 0;
+            else if (len - pj < 4) m &= (1u << (8 * (len - pj))) - 1u;
             cnt += __popc(m);
         }
     }
     return cnt;
+}
+
+// the same for chunk c of the launch: its file and the lane's position in it go to f_out / pos_out
+__device__ inline uint32_t cl_chunk_lane(const uint8_t* text, const ClFile* files, const uint64_t* chunk_base,
+                                         uint32_t nfiles, uint64_t c, uint32_t* f_out, uint64_t* pos_out, uint32_t w[16]) {
+    const uint32_t f = cl_find_u64(chunk_base, nfiles, c);
+    const ClFile fd = files[f];
+    const uint64_t pos = (c - fd.chunk0) * kClChunk + threadIdx.x * 64ull;
+    *f_out = f;
+    *pos_out = pos;
+    return cl_lane_newlines(text + fd.off, fd.len, pos, w);
 }
 
 __global__ void __launch_bounds__(kClThreads) vk_cl_nl_count_kernel(const uint8_t* text, const ClFile* files,
@@ -253,6 +258,84 @@ __global__ void __launch_bounds__(kClThreads) vk_cl_lines_kernel(const uint8_t* 
         __syncthreads();
     }
     if (threadIdx.x == 0 && part[0]) atomicAdd(lines + f, static_cast<unsigned long long>(part[0]));
+}
+
+// The read-length head of a file for vk_clean_heads_device: what avg_read_length (rawinput.py) sums over the whole text.
+// Its fragments are what lies between newlines; fragment i has i newlines ahead of it, the last one ends with the
+// file (and is empty when the file ends in a newline).  Fragments 4j + 1 with j < sample_size count, each with its
+// length less the whitespace at both ends.  That length is (end - start) of two positions which different lanes
+// find: the lane that holds newline 4j walks forward from the byte after it to the first byte that is no
+// whitespace (or the fragment's end) and subtracts that position; the lane that holds newline 4j + 1 walks back
+// from it over whitespace and adds where it stops -- or, when the walk reaches the fragment's start, the
+// fragment's end: the forward walk of an all-whitespace fragment stopped there too.  Sums are modulo 2^64.
+__device__ inline bool cl_space(uint8_t b) { return b == ' ' || (b >= '\t' && b <= '\r'); }   // bytes.strip()'s set
+
+__device__ inline uint64_t cl_head_start(const uint8_t* file, uint64_t len, uint64_t q) {
+    while (q < len && file[q] != '\n' && cl_space(file[q])) ++q;
+    return q;
+}
+
+__device__ inline uint64_t cl_head_end(const uint8_t* file, uint64_t e) {
+    uint64_t q = e;
+    while (q > 0 && file[q - 1] != '\n' && cl_space(file[q - 1])) --q;
+    return (q == 0 || file[q - 1] == '\n') ? e : q;
+}
+
+// One workgroup per file, from the file's start in kClChunk pieces until the newline that ends fragment
+// 4 (sample_size - 1) + 1 has been seen or the file ends: a file costs its first sample_size records, whatever its size.
+__global__ void __launch_bounds__(kClThreads) vk_cl_heads_kernel(const uint8_t* text, const uint64_t* offsets,
+                                                                const uint64_t* lengths, uint32_t sample_size,
+                                                                uint64_t* totals, uint64_t* counted) {
+    __shared__ uint32_t wave_sum[kClThreads / 64];
+    __shared__ uint64_t part[kClThreads];
+    const uint32_t f = blockIdx.x, lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+    const uint8_t* file = text + offsets[f];
+    const uint64_t len = lengths[f];
+    const uint64_t want = 4ull * sample_size - 2;   // newlines up to the end of the last fragment that counts
+    uint64_t seen = 0, acc = 0;                     // newlines ahead of this chunk (the same in every lane); this lane's sum
+    for (uint64_t c0 = 0; c0 < len && seen < want; c0 += kClChunk) {
+        const uint64_t pos = c0 + threadIdx.x * 64ull;
+        uint32_t w[16];
+        const uint32_t cnt = cl_lane_newlines(file, len, pos, w);
+        uint32_t incl = cnt;   // newlines of this wavefront's lanes up to this one, then of the waves ahead
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        uint32_t ahead = 0, total = 0;
+        for (uint32_t v = 0; v < kClThreads / 64; ++v) {
+            if (v < wave) ahead += wave_sum[v];
+            total += wave_sum[v];
+        }
+        __syncthreads();   // (wave_sum is written again in the next round)
+        uint64_t line = seen + ahead + incl - cnt;   // index of the fragment that this lane's first newline ends
+        if (cnt && line < want) {
+            for (uint32_t b = 0; b < 64; ++b) {
+                if (((w[b >> 2] >> (8 * (b & 3))) & 0xFFu) != '\n') continue;
+                const uint64_t p = pos + b;
+                if (p >= len || line >= want) break;
+                if ((line & 3) == 0) acc -= cl_head_start(file, len, p + 1);
+                else if ((line & 3) == 1) acc += cl_head_end(file, p);
+                ++line;
+            }
+        }
+        seen += total;
+    }
+    // the fragment that the end of the file ends
+    if (threadIdx.x == 0 && seen < want && (seen & 3) == 1) acc += cl_head_end(file, len);
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t s = kClThreads / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const uint64_t n = (seen + 3) / 4;   // fragments 4j + 1 among 0 .. seen
+        totals[f] = part[0];
+        counted[f] = n < sample_size ? n : sample_size;
+    }
 }
 
 // exclusive scan of u64 items, three phases: block sums, one block over the sums, blocks again

@@ -126,7 +126,7 @@ struct vk_ctx {
     bool spill_packed = false;     // VKIMG_SPILL_PACKED=1: k = 8, 9 pass A in two kernels, vk_pack_kernel + the partition of the packed stream (measured slower than the one kernel that classifies every byte: 21.1 against 16.3 ms per 100 samples; tests, A/B timing)
     bool spill_pairs = false;      // VKIMG_SPILL_PAIRS=1: a plain k = 8, 9 count through the pair route of rounds 1-4 (u16 per two windows, wave-private queues; what subsampled and packed launches still use) instead of the quad route (tests, A/B timing)
     bool spill_force_wide = false; // VKIMG_SPILL_FORCE_WIDE=1: every k = 8, 9 replay job through the u32 window counters (tests)
-    uint8_t* d_clines = nullptr;   // vk_clean_lines_device: files | chunk bases | line counters
+    uint8_t* d_clines = nullptr;   // vk_clean_lines_device: files | chunk bases | line counters (vk_clean_heads_device: see there)
     size_t clines_cap = 0;
     uint8_t* d_cladapt = nullptr;  // vk_clean_adapters_device: the adapter table (ClAdapter per sample and group)
     size_t cladapt_cap = 0;
@@ -1953,6 +1953,30 @@ int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
                            reinterpret_cast<const uint64_t*>(m + o_chunk), nfiles, reinterpret_cast<unsigned long long*>(m + o_lines));
     VK_HIP(ctx, hipGetLastError());
     VK_HIP(ctx, hipMemcpyAsync(lines, m + o_lines, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VK_OK;
+}
+
+int vk_clean_heads_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                          uint32_t nfiles, uint32_t sample_size, uint64_t* totals, uint64_t* counted) {
+    if (!ctx || !offsets || !lengths || !totals || !counted || (nfiles && !d_text)) return VK_EINVAL;
+    if (sample_size == 0 || sample_size > (1u << 30)) return VK_EINVAL;
+    if (nfiles == 0) return VK_OK;
+    for (uint32_t i = 0; i < nfiles; ++i)
+        if (offsets[i] % 16) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    // offsets | lengths | totals | counted, nfiles u64 words each, in the buffer of vk_clean_lines_device
+    const size_t row = nfiles * 8ull;
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, 4 * row);
+    if (rc) return rc;
+    auto* m = reinterpret_cast<uint64_t*>(ctx->d_clines);
+    VK_HIP(ctx, hipMemcpyAsync(m, offsets, row, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(m + nfiles, lengths, row, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(vk_cl_heads_kernel, dim3(nfiles), dim3(kClThreads), 0, ctx->stream, static_cast<const uint8_t*>(d_text),
+                       m, m + nfiles, sample_size, m + 2ull * nfiles, m + 3ull * nfiles);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(totals, m + 2ull * nfiles, row, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(counted, m + 3ull * nfiles, row, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }

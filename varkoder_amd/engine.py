@@ -603,6 +603,17 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_clean_lines_device")
         return lines
 
+    def clean_heads(self, fastq, offsets, lengths, sample_size=10000):
+        """(totals, counted) uint64 per file in HBM: the `total` and `n` of rawinput.avg_read_length over the file's
+        first `sample_size` records (vk_clean_heads_device).  One call and one synchronisation for the batch."""
+        offs, lens = self._desc(offsets, lengths)
+        totals = np.zeros(len(offs), dtype=np.uint64)
+        counted = np.zeros(len(offs), dtype=np.uint64)
+        st = self.L.vk_clean_heads_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), len(offs), int(sample_size),
+                                          _u64(totals), _u64(counted))
+        _capi.check(self.ctx, st, "vk_clean_heads_device")
+        return totals, counted
+
     def _clean_call(self, offsets, lengths, records, roles, samples, nsamples, size_fn):
         """What clean() and detect_adapters() do alike ahead of their call: the files' arrays in the C ABI's types, with
         their count, and a workspace tensor of the size `size_fn` (vk_clean_workspace_size or its detect twin) asks."""

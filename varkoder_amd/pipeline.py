@@ -376,26 +376,136 @@ def _sample_files(files):
             [(f, _capi.VK_CL_ROLE_R2) for f in sorted(p["R2"])])
 
 
-def _budget(eng, dev, offs, lens, lines, sample_files, max_bp):
-    """Records of each file (rawinput.reads_needed) for one sample: sample_files [(path, role)], its files' slots in
-    the batch (offs / lens) and newline counts."""
+def _budget(avgs, lines, sample_files, max_bp):
+    """Records of each file (rawinput.reads_needed) for one sample: sample_files [(path, role)], its files' mean read
+    lengths (0 without a read budget) and newline counts."""
     from . import _capi
-    from .rawinput import avg_read_length, reads_needed
+    from .rawinput import reads_needed
     info = {"unpaired": [], "R1": [], "R2": []}
     key = {_capi.VK_CL_ROLE_UNPAIRED: "unpaired", _capi.VK_CL_ROLE_R1: "R1", _capi.VK_CL_ROLE_R2: "R2"}
     for j, (f, role) in enumerate(sample_files):
-        avg = 0
-        if max_bp is not None:   # (the mean length of the first 10,000 reads: from the head of the text in HBM)
-            o, n, take = int(offs[j]), int(lens[j]), 4 << 20
-            while True:
-                head = dev[o:o + min(n, take)].cpu().numpy().tobytes()
-                if take >= n or head.count(b"\n") >= 4 * 10000 + 1:
-                    break
-                take *= 4
-            avg = round(avg_read_length(head))
-        info[key[role]].append({"file": f, "avg_length": avg, "total_reads": int(lines[j]) // 4})
+        info[key[role]].append({"file": f, "avg_length": avgs[j], "total_reads": int(lines[j]) // 4})
     take = reads_needed(info, max_bp)
     return [int(take.get(f, 0)) for f, _ in sample_files]
+
+
+def _raw_plans(samples, weights, rank, world):
+    """This rank's share of raw samples [(sample, [files])] as [(sample, [(file, role)])], dealt by weight (per sample:
+    the sum of its files' weights; None: agreed on here, a collective when sharded)."""
+    plans = [(s, _sample_files(files)) for s, files in samples]
+    if weights is None:
+        every = [f for _, sf in plans for f, _ in sf]
+        fw = agreed_weights(every) if world > 1 else file_weights(every)
+        weights, at = [], 0
+        for _, sf in plans:
+            weights.append(sum(fw[at:at + len(sf)]))
+            at += len(sf)
+    return [plans[i] for i in shard_by_size(weights, rank, world)]
+
+
+def _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter, merge, dedup, adapters, detect_adapters,
+                   clean_dir, batch_bytes, verbose):
+    """Step B for this rank's raw samples `mine` [(sample, [(file, role)])], as raw_to_images and raw_to_query share
+    it: batch after batch is uploaded (a .gz inflated in HBM), gets its read budget (the files' line counts and mean
+    read lengths, one call each for the batch: ImageEngine.clean_lines / clean_heads), its adapters and is cleaned.
+    Yields (text on the device, offsets, lengths, samples, time the cleaning was done) for the samples of a batch that
+    came through; the others are reported (CLEAN FAIL) and get `failed_step` in stats.  Fills stats (`clean_basepairs`,
+    `cleaning_time`) and base_sd, and with clean_dir queues the writes of `<sample>.fq.gz` and
+    `<sample>_fastp_gpu.json` on the pool (their futures go to `writes`)."""
+    import gzip
+    import json
+    import os
+
+    from .rawinput import content_curves, curves_sd
+    by_sequence = adapters is not None or detect_adapters
+    if by_sequence and not adapter:
+        raise ValueError("adapters by sequence need adapter trimming (not -a)")
+    explicit = [None, None, None]
+    if adapters is not None:
+        a1, a2 = adapters
+        explicit = [a1, a2 if a2 is not None else a1, a1]
+    if clean_dir is not None:
+        Path(clean_dir).mkdir(parents=True, exist_ok=True)
+
+    def text_bytes(f):
+        f = Path(f)
+        return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
+
+    def write_clean(sample, text, curves, cutting=None):
+        with open(Path(clean_dir) / (sample + ".fq.gz"), "wb") as fh:
+            fh.write(gzip.compress(text, compresslevel=1))
+        report = {"read1_after_filtering": {"content_curves": curves}}
+        if cutting is not None:
+            report["adapter_cutting"] = cutting
+        with open(Path(clean_dir) / (sample + "_fastp_gpu.json"), "w") as fh:
+            json.dump(report, fh)
+
+    i = 0
+    while i < len(mine):
+        batch, nbytes = [], 0
+        t0 = time.perf_counter()
+        for s, sf in mine[i:]:
+            sz = sum(text_bytes(f) for f, _ in sf)
+            if batch and nbytes + sz > batch_bytes:
+                break
+            batch.append((s, sf))
+            nbytes += sz
+        i += len(batch)
+        paths = [Path(f) for _, sf in batch for f, _ in sf]
+        dev, offs, lens = eng.upload_files(paths, pool)
+        lines = eng.clean_lines(dev, offs, lens)
+        avgs = [0] * len(paths)
+        if max_bp is not None:   # (the mean length of each file's first 10,000 reads: estimate_read_lengths, commands/image.py:90-115)
+            totals, counted = eng.clean_heads(dev, offs, lens, 10000)
+            avgs = [round(int(t) / int(n)) if n else 0 for t, n in zip(totals, counted)]
+        records, roles, owner, failed = [], [], [], set()
+        at = 0
+        for j, (s, sf) in enumerate(batch):
+            sl = slice(at, at + len(sf))
+            try:
+                records += _budget(avgs[sl], lines[sl], sf, max_bp)
+            except ZeroDivisionError:     # (a file without reads and a read budget: the reference fails here too)
+                records += [0] * len(sf)
+                failed.add(j)
+            roles += [r for _, r in sf]
+            owner += [j] * len(sf)
+            at += len(sf)
+        table = None
+        if by_sequence:
+            found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=trim[1])
+                     if detect_adapters else [[None] * 3 for _ in batch])
+            table = [[e if e is not None else d for e, d in zip(explicit, det)] for det in found]
+        out, ooffs, olens, cst, status, *rest = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
+                                                          adapter=adapter, merge=merge, dedup=dedup, adapters=table)
+        ast = rest[0] if rest else None   # (adapter stats: with a table only)
+        del dev
+        tc = time.perf_counter()
+        ok = []
+        for j, (s, sf) in enumerate(batch):
+            st = stats.setdefault(s, OrderedDict())
+            if status[j] or j in failed:
+                eprint("CLEAN FAIL:", [f for f, _ in sf], "- status", int(status[j]))
+                st["failed_step"] = "clean"
+                continue
+            row = cst[j]
+            curves = content_curves(row[2:2 + 160], row[162:202])
+            base_sd[s] = curves_sd(curves)
+            st["clean_basepairs"] = int(row[0]) if (adapter or merge) else float("nan")
+            st["cleaning_time"] = (tc - t0) / len(batch)
+            if clean_dir is not None:
+                text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
+                cutting = None
+                if by_sequence:
+                    name = [a.decode("latin-1") if a is not None else None for a in table[j]]
+                    cutting = {"read1_adapter_sequence": name[0], "read2_adapter_sequence": name[1],
+                               "single_adapter_sequence": name[2], "adapter_trimmed_reads": int(ast[j][0]),
+                               "adapter_trimmed_bases": int(ast[j][1])}
+                writes.append(pool.submit(write_clean, s, text, curves, cutting))
+            ok.append(j)
+        if verbose:
+            eprint(f"batch of {len(batch)} samples, {nbytes} raw bytes: upload+clean {tc - t0:.3f}s")
+        if ok:
+            yield out, ooffs[ok], olens[ok], [batch[j][0] for j in ok], tc
 
 
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
@@ -415,121 +525,22 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
-    import gzip
-    import json
-    import os
-
-    import numpy as np
-
     from .engine import ImageEngine
-    from .rawinput import content_curves, curves_sd
     labels, seeds = labels or {}, seeds or {}
-    by_sequence = adapters is not None or detect_adapters
-    if by_sequence and not adapter:
-        raise ValueError("adapters by sequence need adapter trimming (not -a)")
-    explicit = [None, None, None]
-    if adapters is not None:
-        a1, a2 = adapters
-        explicit = [a1, a2 if a2 is not None else a1, a1]
-    plans = [(s, _sample_files(files)) for s, files in samples]
-    if weights is None:   # (per sample: the sum of its files' weights; a collective when sharded)
-        every = [f for _, sf in plans for f, _ in sf]
-        fw = agreed_weights(every) if world > 1 else file_weights(every)
-        weights, at = [], 0
-        for _, sf in plans:
-            weights.append(sum(fw[at:at + len(sf)]))
-            at += len(sf)
-    mine = [plans[i] for i in shard_by_size(weights, rank, world)]
+    mine = _raw_plans(samples, weights, rank, world)
     eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
-    if clean_dir is not None:
-        Path(clean_dir).mkdir(parents=True, exist_ok=True)
     stats, base_sd = OrderedDict(), {}
     pool = ThreadPoolExecutor(io_threads)
     pending, writes = [], []
-    if batch_bytes is None:
-        batch_bytes = DEFAULT_BATCH_BYTES
-
-    def text_bytes(f):
-        f = Path(f)
-        return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
-
-    def write_clean(sample, text, curves, cutting=None):
-        with open(Path(clean_dir) / (sample + ".fq.gz"), "wb") as fh:
-            fh.write(gzip.compress(text, compresslevel=1))
-        report = {"read1_after_filtering": {"content_curves": curves}}
-        if cutting is not None:
-            report["adapter_cutting"] = cutting
-        with open(Path(clean_dir) / (sample + "_fastp_gpu.json"), "w") as fh:
-            json.dump(report, fh)
-
     done = False
     try:   # (an error below must not leave the pool writing files into outdir behind the caller's back)
-        i = 0
-        while i < len(mine):
-            batch, nbytes = [], 0
-            t0 = time.perf_counter()
-            for s, sf in mine[i:]:
-                sz = sum(text_bytes(f) for f, _ in sf)
-                if batch and nbytes + sz > batch_bytes:
-                    break
-                batch.append((s, sf))
-                nbytes += sz
-            i += len(batch)
-            paths = [Path(f) for _, sf in batch for f, _ in sf]
-            dev, offs, lens = eng.upload_files(paths, pool)
-            lines = eng.clean_lines(dev, offs, lens)
-            records, roles, owner, failed = [], [], [], set()
-            at = 0
-            for j, (s, sf) in enumerate(batch):
-                sl = slice(at, at + len(sf))
-                try:
-                    records += _budget(eng, dev, offs[sl], lens[sl], lines[sl], sf, max_bp)
-                except ZeroDivisionError:     # (a file without reads and a read budget: the reference fails here too)
-                    records += [0] * len(sf)
-                    failed.add(j)
-                roles += [r for _, r in sf]
-                owner += [j] * len(sf)
-                at += len(sf)
-            table = None
-            if by_sequence:
-                found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=trim[1])
-                         if detect_adapters else [[None] * 3 for _ in batch])
-                table = [[e if e is not None else d for e, d in zip(explicit, det)] for det in found]
-            out, ooffs, olens, cst, status, *rest = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
-                                                              adapter=adapter, merge=merge, dedup=dedup, adapters=table)
-            ast = rest[0] if rest else None   # (adapter stats: with a table only)
-            del dev
-            tc = time.perf_counter()
-            ok = []
-            for j, (s, sf) in enumerate(batch):
-                st = stats.setdefault(s, OrderedDict())
-                if status[j] or j in failed:
-                    eprint("CLEAN FAIL:", [f for f, _ in sf], "- status", int(status[j]))
-                    st["failed_step"] = "clean"
-                    continue
-                row = cst[j]
-                curves = content_curves(row[2:2 + 160], row[162:202])
-                base_sd[s] = curves_sd(curves)
-                st["clean_basepairs"] = int(row[0]) if (adapter or merge) else float("nan")
-                st["cleaning_time"] = (tc - t0) / len(batch)
-                if clean_dir is not None:
-                    text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
-                    cutting = None
-                    if by_sequence:
-                        name = [a.decode("latin-1") if a is not None else None for a in table[j]]
-                        cutting = {"read1_adapter_sequence": name[0], "read2_adapter_sequence": name[1],
-                                   "single_adapter_sequence": name[2], "adapter_trimmed_reads": int(ast[j][0]),
-                                   "adapter_trimmed_bases": int(ast[j][1])}
-                    writes.append(pool.submit(write_clean, s, text, curves, cutting))
-                ok.append(j)
-            if ok:
-                _ladder_images(eng, out, ooffs[ok], olens[ok], [batch[j][0] for j in ok], [batch[j][0] for j in ok], tc,
-                               outdir, stats, pending, pool, k, mapping_code, min_bp, max_bp, False, seeds, labels,
-                               base_sd, subfolder_levels)
-            if verbose:
-                eprint(f"batch of {len(batch)} samples, {nbytes} raw bytes: upload+clean {tc - t0:.3f}s")
+        for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter,
+                                                           merge, dedup, adapters, detect_adapters, clean_dir,
+                                                           batch_bytes or DEFAULT_BATCH_BYTES, verbose):
+            _ladder_images(eng, out, ooffs, olens, names, names, tc, outdir, stats, pending, pool, k, mapping_code, min_bp,
+                           max_bp, False, seeds, labels, base_sd, subfolder_levels)
         for w in writes:
             w.result()
         for s, t, fut in pending:
@@ -544,3 +555,87 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     if engine is None:
         eng.close()
     return stats, base_sd
+
+
+def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, found):
+    """Step C of a query for cleaned samples in HBM: the one subsample that `query` images (split_fastq with
+    is_query, commands/image.py:677-701), a launch per seed.  found[sample] = (bp, histogram on the device, sd); a
+    sample without one is reported (SPLIT FAIL) and left out."""
+    from .subsample import ladder_counts
+    by_seed = OrderedDict()
+    for j, s in enumerate(names):
+        by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
+    for seed, idx in by_seed.items():
+        recs = ladder_counts(eng, text, offs[idx], lens[idx], seed=seed, max_bp=max_bp, is_query=True)
+        for j, rec in zip(idx, recs):
+            if rec["error"] or not rec["steps"]:
+                eprint("SPLIT FAIL:", sources[j], "-", rec["error"])
+                continue
+            bp, hist, _ = rec["steps"][0]
+            found[names[j]] = (bp, hist, base_sd.get(names[j], 0))
+
+
+def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
+                 seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
+                 weights=None, clean_dir=None, adapters=None, detect_adapters=False):
+    """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
+    cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
+    base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
+    reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
+    the cleaned reads and their reports as raw_to_images writes them."""
+    from .engine import ImageEngine
+    seeds = seeds or {}
+    mine = _raw_plans(samples, weights, rank, world)
+    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
+    stats, base_sd, found = OrderedDict(), {}, OrderedDict()
+    pool = ThreadPoolExecutor(io_threads)
+    writes = []
+    done = False
+    try:
+        for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter,
+                                                          merge, dedup, adapters, detect_adapters, clean_dir,
+                                                          batch_bytes or DEFAULT_BATCH_BYTES, verbose):
+            _query_rungs(eng, out, ooffs, olens, names, names, seeds, max_bp, base_sd, found)
+        for w in writes:
+            w.result()
+        done = True
+    finally:
+        pool.shutdown(wait=True, cancel_futures=not done)
+        if not done and engine is None:
+            eng.close()
+    if engine is None:
+        eng.close()
+    return found
+
+
+def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, k=7, mapping_code="cgr", device=0,
+                   batch_bytes=None, io_threads=8):
+    """raw_to_query's result for samples = [(sample, its cleaned read file)] that an earlier run left in clean_dir
+    (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table)."""
+    import os
+
+    from .engine import ImageEngine
+    samples = [(s, Path(f)) for s, f in samples]
+    base_sd, seeds = base_sd or {}, seeds or {}
+    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
+    found = OrderedDict()
+    pool = ThreadPoolExecutor(io_threads)
+    batch_bytes = batch_bytes or DEFAULT_BATCH_BYTES
+    try:
+        i = 0
+        while i < len(samples):
+            batch, nbytes = [], 0
+            for s, f in samples[i:]:
+                sz = gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
+                if batch and nbytes + sz > batch_bytes:
+                    break
+                batch.append((s, f))
+                nbytes += sz
+            i += len(batch)
+            dev, offs, lens = eng.upload_files([f for _, f in batch], pool)
+            _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], [f for _, f in batch], seeds, max_bp, base_sd, found)
+    finally:
+        pool.shutdown(wait=True)
+        if engine is None:
+            eng.close()
+    return found

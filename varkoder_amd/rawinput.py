@@ -1,7 +1,8 @@
-"""Raw-read input of `image --from-raw` (step B's host half): which files make a sample, how they pair up and how
-many records of each the cleaning takes.  Behaviour of the reference's process_input (non-query branch,
-core/utils.py:283-411), clean_reads' R1/R2 split (commands/image.py:358-384) and calculate_reads_needed
-(:164-221), pinned on the reference's own functions by tests/golden/raw_input_cases.json."""
+"""Raw-read input of `image --from-raw` and `query --from-raw` (step B's host half): which files make a sample, how
+they pair up and how many records of each the cleaning takes.  Behaviour of the reference's process_input
+(core/utils.py:283-411), clean_reads' R1/R2 split (commands/image.py:358-384) and calculate_reads_needed (:164-221),
+pinned on the reference's own functions by tests/golden/raw_input_cases.json and, for process_input's query branch,
+tests/golden/query_input_cases.json."""
 import re
 from pathlib import Path
 
@@ -16,13 +17,33 @@ def is_fastq_file(name):
     return str(name).endswith(FASTQ_SUFFIXES)
 
 
-def process_input(inpath):
+def process_input(inpath, is_query=False):
     """[(sample, labels, files)] sorted by sample: from a folder `<taxon>/<sample>/<reads>` (labels: the taxon
     folders the sample appears under) or from a CSV with columns labels, sample, files (';'-separated, files
-    relative to the CSV's folder).  Labels and files are sorted and unique."""
+    relative to the CSV's folder).  Labels and files are sorted and unique.
+
+    is_query (core/utils.py:340-383): the input is a folder of reads to identify, labelled ["query"].  Without
+    sub-folders every FASTQ file is a sample of its own, named by what precedes the first '.' of its file name
+    (`s_1.fq` and `s_2.fq` are two samples; files whose names agree up to there are one).  With sub-folders (or links
+    to folders) each of them is a sample made of the FASTQ files directly inside it, and files beside them are ignored."""
     inpath = Path(inpath)
     rows = []
-    if inpath.is_dir():
+    if is_query:
+        import os
+        entries = list(inpath.iterdir())
+        if not any(f.is_dir() or (f.is_symlink() and Path(os.readlink(f)).is_dir()) for f in entries):
+            for fl in inpath.rglob("*"):
+                if is_fastq_file(fl.name):
+                    rows.append((("query",), fl.name.split(".")[0], [str(fl)]))
+        else:
+            for sample in entries:
+                if sample.resolve().is_dir():
+                    for fl in sample.iterdir():
+                        if is_fastq_file(fl.name):
+                            rows.append((("query",), sample.name, [str(sample / fl.name)]))
+        if not rows:   # (the reference fails here as well: pandas raises a KeyError ahead of its own check)
+            raise Exception("Folder detected, but no records read. Check format.")
+    elif inpath.is_dir():
         # (a sample under two taxa is one sample with both labels: the reference's duplicate check never fires)
         for taxon in inpath.iterdir():
             if not taxon.is_dir():
