@@ -1,14 +1,17 @@
 """Step B (`image --from-raw`) on the CPU: the cleaning rules as tests/clean_ref.py restates them, at every boundary;
 the host half (inputs, R1/R2 pairing, read budget) against the reference's own functions
-(tests/golden/raw_input_cases.json, written by tools/gen_raw_input_golden.py); the CLI's new flag."""
+(tests/golden/raw_input_cases.json, written by tools/gen_raw_input_golden.py); the CLI's new flag; and that the edge
+batches of tests/clean_cases.py hit what they are built to hit."""
 import json
 import os
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clean_cases as K  # noqa: E402
 import clean_ref as R  # noqa: E402
 
 from varkoder_amd import cli, rawinput  # noqa: E402
@@ -132,7 +135,157 @@ def test_parse_fastq_framing():
     assert R.parse_fastq(good.replace(b"IIII", b"III")) is None
 
 
-# ---------------------------------------------------------------- host half ---
+# ------------------------------------------------- the edge batches (clean_cases) ---
+# What each builder is meant to hit, shown on the reference side: the GPU tests (test_gpu_clean_edges.py) then hold the
+# kernels to the same batches.
+
+def test_budget_batch_hits_its_cases():
+    b = K.budgets()
+    want = K.expected(b)
+    names = b["names"]
+    assert [w[2] for w in want] == [K.RAGGED if j == names["ragged"] else 0 for j in range(b["nsamples"])]
+    files = lambda j: [i for i in range(len(b["owner"])) if b["owner"][i] == j]
+    held = lambda i: b["texts"][i].count(b"\n") // 4
+    # crossed: unequal files, equal budgets, the R1 / R2 file boundary at different pairs; a middle file that gives none
+    r1 = [i for i in files(names["crossed"]) if b["roles"][i] == K.R1]
+    r2 = [i for i in files(names["crossed"]) if b["roles"][i] == K.R2]
+    se = [i for i in files(names["crossed"]) if b["roles"][i] == K.SE]
+    assert len(r1) == len(r2) == 2 and len(se) == 3
+    assert sum(b["records"][i] for i in r1) == sum(b["records"][i] for i in r2) == 400
+    assert b["records"][r1[0]] != b["records"][r2[0]] and sum(map(held, r1)) != sum(map(held, r2))
+    assert b["records"][se[1]] == 0 and held(se[1]) > 0 and b["records"][se[0]] and b["records"][se[2]]
+    assert sum(b["records"][i] < held(i) for i in r1 + r2 + se) >= 5
+    g = K.groups(b)[names["crossed"]]
+    assert [h.split(b" ")[0] for h, _, _ in g[0]] == [h.split(b" ")[0] for h, _, _ in g[1]]   # mates meet
+    assert want[names["crossed"]][0] and not any(b"extra" in ln for ln in want[names["crossed"]][0].split(b"\n")[::4])
+    # every budget 0: nothing out, no status, no stats
+    assert all(b["records"][i] == 0 and held(i) for i in files(names["all_zero"]))
+    assert want[names["all_zero"]] == (b"", [0] * K.NSTAT, 0)
+    assert [b["records"][i] for i in files(names["one"])] == [1] and want[names["one"]][1][1] == 1
+    # a budget that ends with byte 16383 of its file, and one a record later
+    for tag, more in (("at", 0), ("past", 1)):
+        i, n = b["chunk_files"][tag]
+        text = b["texts"][i]
+        assert b["records"][i] == n + more < held(i)
+        assert len(b"\n".join(text.split(b"\n")[:4 * n]) + b"\n") == K.CHUNK and text[K.CHUNK - 1:K.CHUNK] == b"\n"
+    # garbage behind the budget: status 0 as budgeted, bad framing as a whole file
+    i = names["garbage_file"]
+    assert R.parse_fastq(b["texts"][i], b["records"][i]) is not None and R.parse_fastq(b["texts"][i]) is None
+    assert want[names["garbage"]][2] == 0 and want[names["garbage"]][0]
+    for bad in (K.GARBAGE[:23], K.GARBAGE[23:51], K.GARBAGE[51:]):     # each record of it is bad in its own way
+        assert bad.count(b"\n") == 4 and R.parse_fastq(bad) is None
+    # ragged by budget alone
+    i, j = files(names["ragged"])
+    assert held(i) == held(j) and b["records"][i] != b["records"][j]
+    whole = dict(b, records=[held(i) for i in range(len(b["texts"]))])
+    assert K.groups(whole)[names["ragged"]][3] == 0
+
+
+def test_file_end_batch_hits_its_cases():
+    b = K.file_ends()
+    lens = [len(t) for t in b["texts"]]
+    assert {n % 64 for n in lens[:64]} == set(range(64))
+    assert [lens[b["sized"][n]] for n in (16383, 16384, 16385)] == [16383, 16384, 16385]
+    i = b["unterminated"]
+    assert not b["texts"][i].endswith(b"\n") and b["records"][i] == (b["texts"][i] + b"\n").count(b"\n") // 4 - 1
+    assert lens[b["empty"]] == 0 and 0 in lens[b["empty"] + 1:]
+    for text, slack in zip(b["texts"], b["slack"]):
+        assert len(slack) >= 80 and len(R.parse_fastq(slack)) * 4 == slack.count(b"\n") >= 56
+        assert b"\n" in slack[:4 - len(text) % 4] or len(text) % 4 in (0, 3)   # a newline in the end's own word
+    want = K.expected(b, F=0, T=0)
+    assert not any(w[2] for w in want) and sum(1 for w in want if w[0]) == b["nsamples"] - 1
+    assert want[b["owner"][b["empty"]]] == (b"", [0] * K.NSTAT, 0)
+
+
+def test_long_line_batch_hits_its_cases():
+    b = K.long_lines()
+    lines = b["texts"][0].split(b"\n")
+    assert max(map(len, lines)) == 40000 and sorted(map(len, lines))[-3] == 20000
+    assert b"\n" not in b["texts"][0][3 * K.CHUNK:4 * K.CHUNK]            # a chunk without a newline
+    want = K.expected(b)
+    assert not any(w[2] for w in want)
+    assert max(map(len, want[0][0].split(b"\n"))) == 40000 - 20
+    merged = [ln for ln in want[1][0].split(b"\n") if len(ln) > 20000]
+    assert len(merged) == 2 and len(merged[0]) == 31000 - 20               # the mates overlap: one read of the insert
+
+
+def test_many_small_batch_hits_its_cases():
+    b = K.many_small()
+    assert b["nsamples"] == 300 and len(b["texts"]) > 300
+    g = K.groups(b)
+    units = [len(r1) + len(se) for r1, _, se, _ in g]
+    assert units == [K.UNIT_CYCLE[j % 11] for j in range(300)]
+    kinds = {(bool(r1), bool(se)) for r1, _, se, _ in g}
+    assert kinds == {(True, False), (False, True), (True, True), (False, False)}
+    starts = np.cumsum([0] + units[:-1])
+    assert len({int(s) % 64 for s in starts}) > 48 and len({int(s) % 256 for s in starts}) > 100
+    assert {int(s) % 64 for s in starts} >= {0, 1, 15, 16, 17, 63}         # wavefront and workgroup edges
+    want = K.expected(b)
+    assert not any(w[2] for w in want)
+    assert sum(1 for w in want if w[1][1]) > 250
+    import adapter_ref as A
+    ads = [A.clean_sample_adapters(r1, r2, se, adapters=t)[2] for (r1, r2, se, _), t in zip(g, b["adapters"])]
+    assert sum(1 for a in ads if a["reads"]) > 150                        # trimming by sequence has work all over
+
+
+@pytest.mark.parametrize("F,T", K.TRIMS)
+def test_dirty_pair_batch_hits_its_cases(F, T):
+    b = K.dirty_pairs(F, T)
+    r1, r2 = b["pairs"]
+    assert 2900 <= len(r1) == len(r2) <= 3100
+    kept = {(len(a[1]) - F - T, len(c[1]) - F - T) for a, c in zip(r1, r2)}
+    for k in K.KEPT:
+        assert any(x == k for x, _ in kept) and any(y == k for _, y in kept), k
+    assert any(x <= 1 and y == 150 for x, y in kept) and any(y <= 1 and x == 150 for x, y in kept)
+    outcomes = [K.outcome(a, c, F, T) for a, c in zip(r1, r2)]
+    count = {o: outcomes.count(o) for o in set(outcomes)}
+    assert set(count) == {"merged", "cut", "unmerged", "dropped"} and min(count.values()) >= 50, count
+    # the planted mismatches decide: 4 and 5 merge, 6 do not; an equal N costs nothing, an unequal byte one mismatch
+    by = {}
+    for a, o in zip(r1, outcomes):
+        if a[0].startswith(b"@m"):
+            m, f = int(a[0][2:3]), int(a[0][5:6])
+            by.setdefault((m, f), []).append(o in ("merged", "cut"))
+    assert len(by) == 12 and all(len(v) >= 30 for v in by.values())
+    for (m, f), v in by.items():
+        assert all(v) == (m + (f >= 2) <= 5) and any(v) == all(v), (m, f)
+    seqs = [(a[1], c[1]) for a, c in zip(r1, r2)]
+    assert 200 <= len(seqs) - len(set(seqs)) <= 400                        # exact duplicates
+    assert 200 <= sum(1 for a in r1 if a[0].startswith(b"@r2only")) <= 400
+    every = b"".join(a[1] + c[1] for a, c in zip(r1, r2))
+    assert all(ch in every for ch in b"NnacgtRY.-")
+
+
+def test_framing_batch_is_well_formed():
+    b = K.framing()
+    assert b["texts"][0].count(b"\r\n") == b["texts"][0].count(b"\n") and b["roles"][:3] == [K.SE, K.R1, K.R2]
+    for text in b["texts"][3:]:
+        lines = text.split(b"\n")
+        assert any(p.startswith(b"+") and len(p) > 1 for p in lines[2::4])
+        assert b"@" in lines[0::4] and b"" in lines[1::4]
+        assert any(q.startswith(b"@") for q in lines[3::4]) and any(q.startswith(b"+") for q in lines[3::4])
+    want = K.expected(b)
+    assert not any(w[2] for w in want) and all(w[0] for w in want)
+    assert b"\r\n+\n" in K.expected(b, F=0, T=0)[0][0]                     # the '\r' is a byte of the sequence line
+    assert all(ln == b"+" for w in want for ln in w[0].split(b"\n")[2::4])
+
+
+def test_big_identity_closed_form():
+    b = K.big_identity()
+    assert b["records"][0] > 1 << 20 and len(b["texts"][0]) == 62 * b["records"][0]
+    text, words = b["closed"][0](0, 0, True, True, True)
+    assert text is b["texts"][0] and words[:2] == [24 * b["records"][0], b["records"][0]]
+    n = 2000
+    small = K.big_identity(n)
+    for i in range(0, n, 97):                                            # the same headers and ordinals
+        assert small["texts"][0][62 * i:62 * i + 24] == b["texts"][0][62 * i:62 * i + 24]
+    recs = R.parse_fastq(small["texts"][0])
+    assert len(recs) == n and len({s for _, s, _ in recs}) == n and not any(b"G" in s for _, s, _ in recs)
+    for flags in ((True, True, True), (False, False, False)):
+        got, st = R.clean_sample([], [], recs, 0, 0, *flags)
+        assert (got, K.stats_words(st)) == small["closed"][0](0, 0, *flags)
+
+
 
 def test_process_input_folder(tmp_path):
     root = tmp_path / "input"
