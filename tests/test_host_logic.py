@@ -354,3 +354,93 @@ def test_route_chooser_tries_the_other_route_when_the_first_runs_under_the_link_
     assert seen[-1] == "staged" and "mapped" in seen and tm["plain_route_rates_gb_s"]["chosen"] == "staged"
     seen, tm = run({"staged": 48e9, "mapped": 10e9})
     assert set(seen) == {"staged"} and tm["plain_route_rates_gb_s"]["chosen"] == "staged" and "mapped" not in tm["plain_route_rates_gb_s"]
+
+
+# ---- the host path's shared helpers (pipeline.batches, engine_scope, sample_weights; cli.draw_seeds) ----
+
+def test_batches_pack_in_order_under_the_limit():
+    from varkoder_amd.pipeline import batches
+
+    def packed(sizes, limit, **kw):
+        return [(b, n) for b, n, _ in batches(sizes, limit, size=lambda x: x, **kw)]
+    assert packed([], 10) == []
+    assert packed([25], 10) == [([25], 25)]                                   # over the limit: a batch of its own
+    assert packed([3, 25, 3], 10) == [([3], 3), ([25], 25), ([3], 3)]
+    assert packed([4, 6, 1], 10) == [([4, 6], 10), ([1], 1)]                  # exactly the limit stays together
+    assert packed([4, 7, 1], 10) == [([4], 4), ([7, 1], 8)]                   # one byte more splits
+    assert packed([2, 2, 2, 2, 2, 2, 2], 6, first_limit=4) == [([2, 2], 4), ([2, 2, 2], 6), ([2, 2], 4)]   # the first batch only
+    assert packed([2, 2, 2, 2], 4, first_limit=100) == [([2, 2], 4), ([2, 2], 4)]   # never longer than the limit
+    sizes = [int(x) for x in np.random.default_rng(5).integers(0, 40, 300)]
+    got = packed(sizes, 64, first_limit=16)
+    assert [x for b, _ in got for x in b] == sizes and all(n == sum(b) for b, n in got)
+    assert all(n <= 64 or len(b) == 1 for b, n in got)
+    times = [t for _, _, t in batches(sizes, 64, size=lambda x: x)]
+    assert times == sorted(times)
+
+
+def test_draw_seeds_is_the_reference_rule():
+    """str(row index) + str(rng draw), one draw per sample in row order (image.py:1017)."""
+    from varkoder_amd import cli
+    samples = ["b", "a", "c", "a2"]
+    rng = np.random.default_rng(11)
+    want = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(samples)}
+    assert cli.draw_seeds(samples, 11) == want and list(cli.draw_seeds(samples, 11)) == samples
+    assert cli.draw_seeds([], 11) == {}
+
+
+def test_sample_weights_sum_the_files_of_a_sample(tmp_path, monkeypatch):
+    from varkoder_amd import pipeline
+    monkeypatch.setattr(pipeline, "agreed_weights", lambda files: (_ for _ in ()).throw(AssertionError("a collective")))
+    for name, n in (("a_1.fq", 100), ("a_2.fq", 30), ("b.fq", 7), ("c.fq", 0)):
+        (tmp_path / name).write_bytes(b"x" * n)
+    samples = [("a", [tmp_path / "a_1.fq", tmp_path / "a_2.fq"]), ("none", []), ("b", [str(tmp_path / "b.fq")]),
+               ("c", [tmp_path / "c.fq", tmp_path / "missing.fq"])]
+    assert pipeline.sample_weights(samples, 1) == [130, 0, 7, 0]
+    assert pipeline.sample_weights([], 1) == []
+    assert pipeline.sample_weights([], 2) == []                               # no collective either
+
+
+def test_engine_scope_closes_what_it_made_once_and_cancels_on_error(monkeypatch):
+    import threading
+
+    from varkoder_amd import engine, pipeline
+
+    class Engine:
+        made = []
+
+        def __init__(self, **kw):
+            self.kw, self.closed = kw, 0
+            Engine.made.append(self)
+
+        def close(self):
+            self.closed += 1
+    monkeypatch.setattr(engine, "ImageEngine", Engine)
+    with pipeline.engine_scope(None, 5, "cgr", 3, 2) as (eng, pool):
+        assert eng.kw == dict(k=5, mapping="cgr", device=3) and eng.closed == 0
+        fut = pool.submit(lambda: 7)
+    assert fut.result() == 7 and eng.closed == 1 and len(Engine.made) == 1
+    # an exception: the engine made here is closed once, work that is still queued is cancelled, work that runs is waited for
+    given, box, ran = threading.Event(), {}, []
+
+    def busy():   # holds the pool's one thread until the scope has cancelled what is queued behind it
+        import time
+        given.wait(30)
+        end = time.monotonic() + 30   # (never reached by a scope that cancels)
+        while not box["queued"].cancelled() and time.monotonic() < end:
+            pass
+        ran.append("running")
+    with pytest.raises(KeyError):
+        with pipeline.engine_scope(None, 5, "cgr", 0, 1) as (eng2, pool):
+            running = pool.submit(busy)
+            box["queued"] = queued = pool.submit(ran.append, "queued")
+            given.set()
+            raise KeyError("boom")
+    assert eng2.closed == 1 and queued.cancelled() and running.done() and ran == ["running"]
+    # an engine that was passed in is the caller's, on either path
+    mine = Engine()
+    with pipeline.engine_scope(mine, 5, "cgr", 0, 1) as (eng3, pool):
+        assert eng3 is mine
+    with pytest.raises(KeyError):
+        with pipeline.engine_scope(mine, 5, "cgr", 0, 1):
+            raise KeyError("boom")
+    assert mine.closed == 0 and len(Engine.made) == 3

@@ -127,7 +127,7 @@ def test_seeds_follow_the_table_order(tmp_path):
     import numpy as np
     make_tree(tmp_path / "in", {"files": ["b.fq", "a.fq", "c.fq.gz"]})
     ns = cli.parse_args(["query", str(tmp_path / "in"), "OUT", "-l", "m", "--vocab", "v", "--from-raw", "-R", "11"])
-    plan = cli.RawQueryPlan(ns)
+    plan = cli.RawPlan(ns, is_query=True)
     rng = np.random.default_rng(11)
     want = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(["a", "b", "c"])}
     assert plan.samples == ["a", "b", "c"] and plan.seeds == want and len(plan) == 3

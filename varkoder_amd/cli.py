@@ -179,6 +179,37 @@ def run_convert(args):
     eprint(f"Converted {n} images; written to {args.outdir}")
 
 
+def draw_seeds(samples, seed):
+    """{sample: seed}: str(row index) + str(random integer), one draw per sample in row order (image.py:1017) --
+    drawn for every sample on every rank."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(samples)}
+
+
+def max_bp_of(args):
+    """-M: '0' = all of the data (cli.py:496-501)."""
+    return None if str(args.max_bp) == "0" else parse_size(args.max_bp)
+
+
+def clean_options(args):
+    """The cleaning flags of `--from-raw` (-T, -a, -r, -D and the adapters by sequence: absent = off) as
+    pipeline.raw_to_images and raw_to_query take them."""
+    front, tail = (int(x) for x in str(args.trim_bp).split(","))
+    a1, a2 = getattr(args, "adapter_sequence", None), getattr(args, "adapter_sequence_r2", None)
+    return dict(trim=(front, tail), adapter=not args.no_adapter, merge=not args.no_merge, dedup=not args.no_deduplicate,
+                adapters=(a1, a2) if a1 is not None or a2 is not None else None,
+                detect_adapters=getattr(args, "detect_adapters", False))
+
+
+def clean_read_files(src):
+    """The cleaned read files of `src` (of its clean_reads/, when it is an intermediate folder), sorted."""
+    src = Path(src)
+    if (src / "clean_reads").is_dir():
+        src = src / "clean_reads"
+    return sorted(f for f in src.iterdir() if f.is_file() and f.name.endswith((".fq", ".fq.gz", ".fastq", ".fastq.gz")))
+
+
 def run_query(args):
     """`varKoder query` from step C on (commands/query.py:188-324): images are made on the GPU and
     stay there for the model's input transform; predictions.csv has the reference's columns.  With --from-raw from
@@ -195,9 +226,10 @@ def run_query(args):
     from . import query as Q
     from .convert import get_metadata_from_img_filename
     from .engine import ImageEngine
-    from .image import write_png
-    from .shard import agreed_weights, shard_by_size, world_info
-    from .subsample import ladder_counts, split_name
+    from .image import stem, write_png
+    from .pipeline import clean_to_query
+    from .shard import agreed_weights, io_threads_per_rank, shard_by_size, world_info
+    from .subsample import split_name
     rank, world, device = world_info()
     outdir = Path(args.outdir)
     if not args.overwrite and (outdir / "predictions.csv").exists():
@@ -206,12 +238,9 @@ def run_query(args):
     if args.images:
         inputs = sorted(Path(args.input).rglob("*.png"))
     elif from_raw:
-        inputs = RawQueryPlan(args)   # (no collective in it, nothing on the GPU: an input error leaves every rank here)
+        inputs = RawPlan(args, is_query=True)   # (no collective in it, nothing on the GPU: an input error leaves every rank here)
     else:
-        src = Path(args.input)
-        if (src / "clean_reads").is_dir():
-            src = src / "clean_reads"
-        inputs = sorted(f for f in src.iterdir() if f.is_file() and f.name.endswith((".fq", ".fq.gz", ".fastq", ".fastq.gz")))
+        inputs = clean_read_files(args.input)
     if not inputs:
         raise Exception("No images found to query. Please check your input.")
     if world > 1:
@@ -234,32 +263,40 @@ def run_query(args):
         records, images, order = [], None, []   # order: index of each record's input in `inputs`
         eng = None
         mine = [] if from_raw else shard_by_size(weights, rank, world)
-        if from_raw:
-            eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
-            found = inputs.run(eng, raw_weights, clean_weights, rank, world)
+
+        def found_images(found, wanted, labels):
+            """Records (in the order of wanted = [(index in `inputs`, sample)]), stacked images and kept PNGs of the
+            samples that found = {sample: (bp, histogram, sd)} holds; labels: {sample: [labels]}."""
             hists, keep = [], []
-            for i, sample in enumerate(inputs.samples):
+            for i, sample in wanted:
                 if sample not in found:
                     continue
                 bp, hist, sd = found[sample]
                 name = split_name(sample, bp) + f"+{args.kmer_mapping}+k{args.kmer_size}.png"
                 path = str(outdir / "query_images" / name) if args.keep_images else name
                 # what write_png puts into the image's text chunks, read back as a query of that image reads it
-                labels, qual, freq_sd = Q.image_metadata({"varkoderKeywords": LABELS_SEP.join(inputs.labels),
-                                                          "varkoderBaseFreqSd": str(sd),
-                                                          "varkoderLowQualityFlag": str(sd > QUAL_THRESH)})
+                text, qual, freq_sd = Q.image_metadata({"varkoderKeywords": LABELS_SEP.join(labels.get(sample, [])),
+                                                        "varkoderBaseFreqSd": str(sd),
+                                                        "varkoderLowQualityFlag": str(sd > QUAL_THRESH)})
                 records.append(dict(path=path, sample=sample, bp=int(bp / 1000) * 1000, k=args.kmer_size,
-                                    mapping=args.kmer_mapping, labels=labels, qual=qual, freq_sd=freq_sd))
+                                    mapping=args.kmer_mapping, labels=text, qual=qual, freq_sd=freq_sd))
                 hists.append(hist)
-                keep.append((name, sd))
+                keep.append((name, sample, sd))
                 order.append(i)
-            if hists:
-                images = eng.images(torch.stack(hists))
-                if args.keep_images:
-                    (outdir / "query_images").mkdir(parents=True, exist_ok=True)
-                    host = images.cpu().numpy()
-                    for j, (name, sd) in enumerate(keep):
-                        write_png(host[j], outdir / "query_images" / name, inputs.labels, sd, QUAL_THRESH, args.kmer_mapping)
+            if not hists:
+                return None
+            images = eng.images(torch.stack(hists))
+            if args.keep_images:
+                (outdir / "query_images").mkdir(parents=True, exist_ok=True)
+                host = images.cpu().numpy()
+                for j, (name, sample, sd) in enumerate(keep):
+                    write_png(host[j], outdir / "query_images" / name, labels.get(sample, []), sd, QUAL_THRESH, args.kmer_mapping)
+            return images
+
+        if from_raw:
+            eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
+            found = inputs.run(eng, raw_weights, clean_weights, rank, world)
+            images = found_images(found, enumerate(inputs.samples), inputs.labels)
         elif args.images:
             arrays = []
             for i in mine:
@@ -278,36 +315,16 @@ def run_query(args):
                 eng = state["eng"] = ImageEngine(k=records[0]["k"], mapping="cgr", device=device)
                 images = torch.from_numpy(np.stack(arrays)).to(eng.device)
         else:
-            max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)
-            rng = np.random.default_rng(args.seed)
-            # one seed per sample in input order, as image.py:1017 -- drawn for every input on every rank
-            seeds = [int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i in range(len(inputs))]
-            hists, keep = [], []
+            # cleaned reads, a sample per file: no labels and no base-frequency sd, as images written with neither read back
+            max_bp = max_bp_of(args)
+            seeds = draw_seeds([stem(f) for f in inputs], args.seed)
             if mine:
                 eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
-                files = [inputs[i] for i in mine]
-                dev, offs, lens = eng.upload_files(files)
-                for j, (i, f) in enumerate(zip(mine, files)):
-                    sample = str(f.name.removesuffix("".join(f.suffixes)))
-                    rec = ladder_counts(eng, dev, offs[j:j + 1], lens[j:j + 1], seed=seeds[i], max_bp=max_bp, is_query=True)[0]
-                    if rec["error"] or not rec["steps"]:
-                        eprint("SPLIT FAIL:", f, "-", rec["error"])
-                        continue
-                    bp, hist, _ = rec["steps"][0]
-                    name = split_name(sample, bp) + f"+{args.kmer_mapping}+k{args.kmer_size}.png"
-                    path = str(outdir / "query_images" / name) if args.keep_images else name
-                    records.append(dict(path=path, sample=sample, bp=int(bp / 1000) * 1000, k=args.kmer_size,
-                                        mapping=args.kmer_mapping, labels="", qual=bool("False"), freq_sd=0.0))
-                    hists.append(hist)
-                    keep.append(name)
-                    order.append(i)
-                if hists:
-                    images = eng.images(torch.stack(hists))
-                    if args.keep_images:
-                        (outdir / "query_images").mkdir(parents=True, exist_ok=True)
-                        host = images.cpu().numpy()
-                        for j, name in enumerate(keep):
-                            write_png(host[j], outdir / "query_images" / name, [], 0, QUAL_THRESH, args.kmer_mapping)
+                wanted = [(i, stem(inputs[i])) for i in mine]
+                found = clean_to_query([(s, inputs[i]) for i, s in wanted], max_bp=max_bp, seeds=seeds, engine=eng,
+                                       k=args.kmer_size, mapping_code=args.kmer_mapping,
+                                       io_threads=io_threads_per_rank(args.n_threads))
+                images = found_images(found, wanted, {})
         if rank == 0:
             if args.single_label:
                 eprint("This is a single label classification model, each input may will have only one prediction.")
@@ -356,26 +373,24 @@ def run_query(args):
         raise failure
 
 
-class RawQueryPlan:
-    """What `query --from-raw` works on: the input table (rawinput.process_input with is_query), one seed per sample
-    in table order (image.py:1017, drawn for every sample on every rank), the cleaning options, and which samples
-    an earlier run with the same -i has cleaned already.  len() = the samples."""
-    labels = ["query"]
+class RawPlan:
+    """What `image --from-raw` and `query --from-raw` work on: the input table (rawinput.process_input), the labels
+    and one seed per sample in table order (draw_seeds), and which samples an earlier run with the same -i has
+    cleaned already.  len() = the samples."""
 
-    def __init__(self, args):
-        import numpy as np
+    def __init__(self, args, is_query):
         from .rawinput import process_input
         src = Path(args.input)
-        if list(src.glob("*.png")):                                           # query.py:111-120
+        if is_query and list(src.glob("*.png")):                              # query.py:111-120
             eprint("ERROR: Found PNG files in input directory.")
             eprint("If your input directory contains pre-generated images, use the --images flag:")
             eprint("    varkoder_amd query --images " + str(src) + " " + str(args.outdir))
             raise Exception("Input directory contains PNG files. Use --images flag for pre-generated images.")
-        table = process_input(src, is_query=True)
+        table = process_input(args.input, is_query=is_query)
         self.args = args
         self.samples = [s for s, _, _ in table]
-        rng = np.random.default_rng(args.seed)
-        self.seeds = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(self.samples)}
+        self.labels = {s: lab for s, lab, _ in table}   # (a query's: ["query"])
+        self.seeds = draw_seeds(self.samples, args.seed)
         self.clean_dir = Path(args.int_folder) / "clean_reads" if args.int_folder else None
         # a cleaned file from an earlier run is used as it is (clean_reads, commands/image.py:350-352)
         reuse = {s for s in self.samples
@@ -388,37 +403,29 @@ class RawQueryPlan:
     def __len__(self):
         return len(self.samples)
 
+    def reused_files(self):
+        return [self.clean_dir / (s + ".fq.gz") for s in self.reused]
+
     def agree_weights(self):
         """(weight of each raw sample -- the sum of its files' --, weight of each reused cleaned file) as every rank
-        uses them: collectives."""
-        from .shard import agreed_weights
-        every = [f for _, files in self.raw for f in files]
-        fw = agreed_weights(every) if every else []
-        weights, at = [], 0
-        for _, files in self.raw:
-            weights.append(sum(fw[at:at + len(files)]))
-            at += len(files)
-        done = [self.clean_dir / (s + ".fq.gz") for s in self.reused]
-        return weights, (agreed_weights(done) if done else [])
+        uses them: collectives, raw first, none for an empty list."""
+        from .pipeline import sample_weights
+        from .shard import agreed_weights, world_info
+        done = self.reused_files()
+        return sample_weights(self.raw, world_info()[1]), (agreed_weights(done) if done else [])
 
     def run(self, eng, raw_weights, clean_weights, rank, world):
-        """{sample: (bp, histogram on the device, base-frequency sd)} of this rank's share."""
+        """A query's {sample: (bp, histogram on the device, base-frequency sd)} of this rank's share."""
         from .image import base_sd_table
         from .pipeline import clean_to_query, raw_to_query
         from .shard import io_threads_per_rank, shard_by_size
         args = self.args
-        max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)     # cli.py:496-501
-        front, tail = (int(x) for x in str(args.trim_bp).split(","))
-        a1, a2 = getattr(args, "adapter_sequence", None), getattr(args, "adapter_sequence_r2", None)
-        common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp, seeds=self.seeds, engine=eng,
+        common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp_of(args), seeds=self.seeds, engine=eng,
                       io_threads=io_threads_per_rank(args.n_threads))
         found = {}
         if self.raw:
-            found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, trim=(front, tail),
-                                      adapter=not args.no_adapter, merge=not args.no_merge, dedup=not args.no_deduplicate,
-                                      clean_dir=self.clean_dir, verbose=args.verbose,
-                                      adapters=(a1, a2) if a1 is not None or a2 is not None else None,
-                                      detect_adapters=getattr(args, "detect_adapters", False), **common))
+            found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
+                                      verbose=args.verbose, **clean_options(args), **common))
         mine = [self.reused[i] for i in shard_by_size(clean_weights, rank, world)]
         if mine:
             found.update(clean_to_query([(s, self.clean_dir / (s + ".fq.gz")) for s in mine],
@@ -445,26 +452,19 @@ def parse_size(text):
 
 
 def run_image_from_clean(args, outdir, rank, world, local_rank):
-    import numpy as np
+    from .image import base_sd_table, stem
     from .pipeline import clean_to_images
-    from .shard import io_threads_per_rank
-    src = Path(args.input)
-    if (src / "clean_reads").is_dir():
-        src = src / "clean_reads"
-    files = sorted(f for f in src.iterdir() if f.is_file() and f.name.endswith((".fq", ".fq.gz", ".fastq", ".fastq.gz")))
+    from .shard import agreed_weights, io_threads_per_rank
+    files = clean_read_files(args.input)
     if not files:
         raise Exception("No files found in input. Please check.")
-    samples = [str(f.name.removesuffix("".join(f.suffixes))) for f in files]
-    max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)     # cli.py:496-501
-    rng = np.random.default_rng(args.seed)
-    # image.py:1017: str(row index) + str(random integer), one draw per sample in row order
-    seeds = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(samples)}
+    samples = [stem(f) for f in files]
+    max_bp = max_bp_of(args)
+    seeds = draw_seeds(samples, args.seed)
     labels = read_labels(args.labels_csv)
-    from .image import base_sd_table
-    base_sd = base_sd_table(src, samples)                                     # image.py:1094-1097
+    base_sd = base_sd_table(files[0].parent, samples)                         # image.py:1094-1097
     eprint("Subsampling, counting kmers and creating images for", len(files), "samples")
     per_sample, error = OrderedDict(), None
-    from .shard import agreed_weights
     weights = agreed_weights(files)   # (a collective: before the try block, while every rank is still here)
     try:   # (a rank whose share fails still reaches the gather below: see finish_image_job)
         failpoint(rank)
@@ -482,60 +482,34 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
 
 def run_image_from_raw(args, outdir, rank, world, local_rank):
     """`image --from-raw`: steps B-E per sample (run_clean2img, commands/image.py:938-1127) with step B on the GPU."""
-    import numpy as np
     from .image import base_sd_table
     from .pipeline import clean_to_images, raw_to_images
-    from .rawinput import process_input
-    from .shard import agreed_weights, io_threads_per_rank
-    table = process_input(args.input)
-    if not table:
+    from .shard import io_threads_per_rank
+    plan = RawPlan(args, is_query=False)
+    if not plan:
         raise Exception("No files found in input. Please check.")
-    samples = [s for s, _, _ in table]
-    labels = {s: lab for s, lab, _ in table}
-    max_bp = None if str(args.max_bp) == "0" else parse_size(args.max_bp)     # cli.py:496-501
-    front, tail = (int(x) for x in str(args.trim_bp).split(","))
-    rng = np.random.default_rng(args.seed)
-    # image.py:1017: str(row index) + str(random integer), one draw per sample in row order
-    seeds = {s: int(str(i) + str(rng.integers(low=0, high=2 ** 32))) % (1 << 63) for i, s in enumerate(samples)}
-    clean_dir = Path(args.int_folder) / "clean_reads" if args.int_folder else None
-    # a cleaned file from an earlier run is used as it is (clean_reads, commands/image.py:350-352)
-    reuse = {s for s in samples if clean_dir is not None and not args.overwrite and (clean_dir / (s + ".fq.gz")).is_file()}
-    for s in sorted(reuse):
-        eprint("Skipping cleaning for", s + ":", "File exists.")
-    raw = [(s, files) for s, _, files in table if s not in reuse]
-    done_clean = [clean_dir / (s + ".fq.gz") for s in samples if s in reuse]
-    eprint("Cleaning reads, subsampling, counting kmers and creating images for", len(samples), "samples")
+    max_bp, cleaning = max_bp_of(args), clean_options(args)
+    eprint("Cleaning reads, subsampling, counting kmers and creating images for", len(plan), "samples")
     per_sample, base_sd, error = OrderedDict(), {}, None
-    # (collectives: before the try block, while every rank is still here)
-    every = [f for _, files in raw for f in files]
-    fw = agreed_weights(every) if every else []
-    weights, at = [], 0
-    for _, files in raw:
-        weights.append(sum(fw[at:at + len(files)]))
-        at += len(files)
-    cw = agreed_weights(done_clean) if done_clean else []
+    weights, cw = plan.agree_weights()   # (collectives: before the try block, while every rank is still here)
     try:   # (a rank whose share fails still reaches the gather below: see finish_image_job)
         failpoint(rank)
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
-                      seeds=seeds, labels=labels, device=local_rank, rank=rank, world=world,
+                      seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
-        if raw:
-            a1, a2 = getattr(args, "adapter_sequence", None), getattr(args, "adapter_sequence_r2", None)
-            got, sds = raw_to_images(raw, outdir, weights=weights, trim=(front, tail), adapter=not args.no_adapter,
-                                     merge=not args.no_merge, dedup=not args.no_deduplicate, clean_dir=clean_dir,
-                                     adapters=(a1, a2) if a1 is not None or a2 is not None else None,
-                                     detect_adapters=getattr(args, "detect_adapters", False), **common)
+        if plan.raw:
+            got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, **cleaning, **common)
             per_sample.update(got)
             base_sd.update(sds)
-        if done_clean:
-            sds = base_sd_table(clean_dir, sorted(reuse))
+        if plan.reused:
+            sds = base_sd_table(plan.clean_dir, plan.reused)
             base_sd.update(sds)
-            per_sample.update(clean_to_images(done_clean, outdir, weights=cw, base_sd=sds, **common))
+            per_sample.update(clean_to_images(plan.reused_files(), outdir, weights=cw, base_sd=sds, **common))
         for s, v in per_sample.items():
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
         error = e
-    finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, base_sd)
+    finish_image_job(args, outdir, rank, world, per_sample, error, samples=plan.samples, labels=plan.labels, base_sd=base_sd)
 
 
 def failpoint(rank):

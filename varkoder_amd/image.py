@@ -103,7 +103,7 @@ def read_counts(path):
     return k, np.frombuffer(raw, dtype="<u4", offset=12).astype(np.uint32)
 
 
-def _stem(path):
+def stem(path):
     """File name minus ALL suffixes (the reference's naming rule, image.py:753, :840)."""
     p = Path(path)
     return str(p.name.removesuffix("".join(p.suffixes)))
@@ -111,12 +111,12 @@ def _stem(path):
 
 def counts_name(infile, k):
     """`<stem>+k<k>.fq.h5` (image.py:752-759)."""
-    return f"{_stem(infile)}{BP_KMER_SEP}k{k}.fq.h5"
+    return f"{stem(infile)}{BP_KMER_SEP}k{k}.fq.h5"
 
 
 def png_name(counts_file, mapping_code):
     """`<sample>@<bp>K+<mapping>+k<k>.png` from a counts file name (image.py:840-849)."""
-    base, in_k = _stem(counts_file).split(BP_KMER_SEP)
+    base, in_k = stem(counts_file).split(BP_KMER_SEP)
     return BP_KMER_SEP.join((base, mapping_code, in_k)) + ".png"
 
 

@@ -6,14 +6,16 @@ Steps B/C of the reference (fastp, reformat.sh) are external tools that are out 
 path's scope; this module enters where the reference enters step D: with
 files named `<sample>@<bp>K.fq[.gz]` as split_fastq leaves them (image.py:699-709).
 """
+import os
 import time
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
+from dataclasses import dataclass
 from pathlib import Path
 
-
 from .config import QUAL_THRESH
-from .image import counts_name, eprint, png_name, shard_folder, write_png
+from .image import counts_name, eprint, png_name, shard_folder, stem, write_png
 from .shard import TailQueue, agreed_weights, file_weights, gz_text_bytes, shard_by_size, split_head_tail
 
 
@@ -96,6 +98,90 @@ class RouteChooser:
             self.on = False
 
 
+def text_bytes(path):
+    """Text bytes of a read file as it lies in HBM (a gzip file counts the text its framing names, shard.gz_text_bytes:
+    it is inflated on the GPU)."""
+    path = Path(path)
+    return gz_text_bytes(path) if path.suffix == ".gz" else os.path.getsize(path)
+
+
+def batches(items, limit, size=text_bytes, first_limit=None):
+    """Pack `items` greedily, in order, into batches of at most `limit` bytes by size(item); the first batch at most
+    min(limit, first_limit).  An item joins the batch unless the batch is non-empty and would pass its limit: an item
+    larger than the limit gets a batch of its own, a batch that lands exactly on the limit is not split.  Yields
+    (batch, its bytes, the time it was begun: before its items are sized, except the first of a later batch)."""
+    cap = limit if first_limit is None else min(limit, first_limit)
+    batch, nbytes, t0 = [], 0, time.perf_counter()
+    for item in items:
+        sz = size(item)
+        if batch and nbytes + sz > cap:
+            yield batch, nbytes, t0
+            batch, nbytes, cap, t0 = [], 0, limit, time.perf_counter()
+        batch.append(item)
+        nbytes += sz
+    if batch:
+        yield batch, nbytes, t0
+
+
+@contextmanager
+def engine_scope(engine, k, mapping_code, device, io_threads):
+    """(engine, host thread pool) of one entry point: `engine`, or one made here and closed here, once.  An error
+    inside must not leave the pool writing files into outdir behind the caller's back: queued work is cancelled
+    when an exception leaves, and what runs is waited for either way."""
+    from .engine import ImageEngine
+    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
+    pool = ThreadPoolExecutor(io_threads)
+    failed = True
+    try:
+        yield eng, pool
+        failed = False
+    finally:
+        pool.shutdown(wait=True, cancel_futures=failed)
+        if engine is None:
+            eng.close()
+
+
+class PngSink:
+    """Where an entry point's images go: the output folder (made here) with its md5 sub-folders, the text chunks'
+    sources (labels and base_sd by sample; base_sd may still be filling), the pool that writes and what it has pending."""
+
+    def __init__(self, outdir, pool, k, mapping_code, labels, base_sd, subfolder_levels):
+        self.outdir, self.pool, self.k, self.mapping_code = Path(outdir), pool, k, mapping_code
+        self.labels, self.base_sd, self.subfolder_levels = labels, base_sd, subfolder_levels
+        self.pending = []
+        self.outdir.mkdir(parents=True, exist_ok=True)
+
+    def path(self, name):
+        return shard_folder(self.outdir, name, self.subfolder_levels) / name
+
+    def submit(self, key, sample, name, arr):
+        """Queue image `arr` of `sample` as file `name`; its writing time goes to stats row `key` (finish)."""
+        path = self.path(name)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        self.pending.append((key, time.perf_counter(),
+                             self.pool.submit(write_png, arr.copy(), path, self.labels.get(sample, []),
+                                              self.base_sd.get(sample, 0), QUAL_THRESH, self.mapping_code)))
+
+    def finish(self, stats):
+        """Wait for every image (a failed write raises here) and add `k<k>_img_time` to its stats row."""
+        key = "k" + str(self.k) + "_img_time"
+        for row, t, fut in self.pending:
+            fut.result()
+            stats[row][key] = stats[row].get(key, 0) + (time.perf_counter() - t)
+
+
+def sample_weights(samples, world):
+    """Work estimate of each of samples = [(sample, [files])]: the sum of its files' weights, as every rank uses them
+    (shard.agreed_weights: a collective) when world > 1.  No samples: [] and no collective."""
+    every = [f for _, files in samples for f in files]
+    fw = (agreed_weights(every) if world > 1 else file_weights(every)) if every else []
+    weights, at = [], 0
+    for _, files in samples:
+        weights.append(sum(fw[at:at + len(files)]))
+        at += len(files)
+    return weights
+
+
 def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_sd=None, overwrite=False,
                      subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None, io_threads=8,
                      engine=None, verbose=False, timings=None, weights=None, tail_frac=0.1):
@@ -109,10 +195,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
     staging thread (`stage_wait_s`), the copy to the device and the inflate (`upload_s`, of which
     `inflate_s`), kernels + copies back (`kernels_s`) and waiting for the last hand-overs and PNGs (`png_tail_s`);
     `png_submit_s` = handing images to the PNG pool, on a thread of its own since round 5 (not this thread's time); `batches`."""
-    from .engine import ImageEngine
     files = [Path(f) for f in files]
-    labels = labels or {}
-    base_sd = base_sd or {}
     if weights is None:   # (a collective only when this call itself is one rank's share of a job: bench.py's per-rank legs call with world = 1 inside a group)
         weights = agreed_weights(files) if world > 1 else file_weights(files)
     # Size-aware (rank 0's view of the sizes: shard.agreed_weights).  With a process group, the longest files -- nine tenths
@@ -127,137 +210,106 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
     tail_files = [files[i] for i in tail]
     tail_queue = TailQueue(len(tail_files)) if tail_files else None
     tail_chunk = max(1, len(tail_files) // (6 * world))   # files per claim: ~6 claims per rank
-    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
-    outdir = Path(outdir)
-    outdir.mkdir(parents=True, exist_ok=True)
     stats = OrderedDict()
-    pool = ThreadPoolExecutor(io_threads)
-    pending = []
-
-    def target(f):
-        name = image_name(f, k, mapping_code)
-        return shard_folder(outdir, name, subfolder_levels), name
-
-    def wanted(fs):
-        out = []
-        for f in fs:
-            d, name = target(f)
-            if not overwrite and (d / name).is_file():
-                eprint("File exists. Skipping image for file:", str(f))
-                continue
-            out.append(f)
-        return out
-
-    todo = wanted(mine)
-    import os
-    if batch_bytes is None:
-        every = todo + tail_files
-        batch_bytes = DEFAULT_GZ_BATCH_BYTES if every and all(f.suffix == ".gz" for f in every) else DEFAULT_BATCH_BYTES
     tm = timings if timings is not None else {}
     for key in ("stage_wait_s", "upload_s", "inflate_s", "kernels_s", "png_submit_s", "png_tail_s"):
         tm.setdefault(key, 0.0)
+    with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
 
-    def text_bytes(f):
-        return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
+        def wanted(fs):
+            out = []
+            for f in fs:
+                if not overwrite and sink.path(image_name(f, k, mapping_code)).is_file():
+                    eprint("File exists. Skipping image for file:", str(f))
+                    continue
+                out.append(f)
+            return out
 
-    def batch_source():
-        """This rank's batches, by text size in HBM (a gzip file counts the text its framing names, shard.gz_text_bytes: it is
-        inflated on the GPU): its static share first, then what it claims of the tail, a chunk per batch."""
-        batch, nbytes, first = [], 0, True
-        for f in todo:
-            sz = text_bytes(f)
-            if batch and nbytes + sz > (min(batch_bytes, FIRST_BATCH_BYTES) if first else batch_bytes):
+        todo = wanted(mine)
+        if batch_bytes is None:
+            every = todo + tail_files
+            batch_bytes = DEFAULT_GZ_BATCH_BYTES if every and all(f.suffix == ".gz" for f in every) else DEFAULT_BATCH_BYTES
+
+        def batch_source():
+            """This rank's batches by text size in HBM: its static share first (the first batch cut short), then what it
+            claims of the tail, a chunk per batch."""
+            for batch, nbytes, _ in batches(todo, batch_bytes, first_limit=FIRST_BATCH_BYTES):
                 yield batch, nbytes
-                batch, nbytes, first = [], 0, False
-            batch.append(f)
-            nbytes += sz
-        if batch:
-            yield batch, nbytes
-        while tail_queue is not None:
-            got = tail_queue.next(tail_chunk)
-            if len(got) == 0:
-                break
-            batch = wanted([tail_files[i] for i in got])
-            tm["tail_files"] = tm.get("tail_files", 0) + len(batch)
-            if batch:
-                yield batch, sum(text_bytes(f) for f in batch)
-    # The host half of a batch (file reads into a pinned buffer) runs one batch ahead on its own
-    # thread, into the other of two staging buffers, while this thread copies and processes.
-    stager = ThreadPoolExecutor(1)
-    finisher, handed = ThreadPoolExecutor(1), []
-    done = False
-    chooser = RouteChooser(eng, tm)
-    try:
-        source = batch_source()
-        cur = next(source, None)
-        staged = stager.submit(eng.stage_files, cur[0], pool, 0) if cur else None
-        bi = -1
-        while cur is not None:
-            bi += 1
-            batch, nbytes = cur
-            t0 = time.perf_counter()
-            ready = staged.result()
-            tm["stage_wait_s"] += time.perf_counter() - t0
-            cur = next(source, None)          # (a chunk of the tail is claimed here: one batch ahead, like the staging)
-            if cur is not None:
-                staged = stager.submit(eng.stage_files, cur[0], pool, (bi + 1) & 1)
-            for h in handed:   # a hand-over that failed (a folder that cannot be made) stops the pass here, not after the last batch
-                if h.done() and h.exception() is not None:
-                    raise h.exception()
-            tu = time.perf_counter()
-            dev, offs, lens = eng.upload_staged(ready, timings=tm)
-            t1 = time.perf_counter()
-            tm["upload_s"] += t1 - tu
-            img, hist, status = eng.fastq_to_images(dev, offs, lens)
-            st = status.cpu().numpy()
-            imgs = img.cpu().numpy()
-            nz = (hist != 0).any(dim=1).cpu().numpy()
-            t2 = time.perf_counter()
-            tm["kernels_s"] += t2 - t1
-            chooser.batch_done(bi, ready, t2 - t0)
+            while tail_queue is not None:
+                got = tail_queue.next(tail_chunk)
+                if len(got) == 0:
+                    break
+                batch = wanted([tail_files[i] for i in got])
+                tm["tail_files"] = tm.get("tail_files", 0) + len(batch)
+                if batch:
+                    yield batch, sum(text_bytes(f) for f in batch)
+        # The host half of a batch (file reads into a pinned buffer) runs one batch ahead on its own
+        # thread, into the other of two staging buffers, while this thread copies and processes.
+        stager = ThreadPoolExecutor(1)
+        finisher, handed = ThreadPoolExecutor(1), []
+        done = False
+        chooser = RouteChooser(eng, tm)
+        try:
+            source = batch_source()
+            cur = next(source, None)
+            staged = stager.submit(eng.stage_files, cur[0], pool, 0) if cur else None
+            bi = -1
+            while cur is not None:
+                bi += 1
+                batch, nbytes = cur
+                t0 = time.perf_counter()
+                ready = staged.result()
+                tm["stage_wait_s"] += time.perf_counter() - t0
+                cur = next(source, None)          # (a chunk of the tail is claimed here: one batch ahead, like the staging)
+                if cur is not None:
+                    staged = stager.submit(eng.stage_files, cur[0], pool, (bi + 1) & 1)
+                for h in handed:   # a hand-over that failed (a folder that cannot be made) stops the pass here, not after the last batch
+                    if h.done() and h.exception() is not None:
+                        raise h.exception()
+                tu = time.perf_counter()
+                dev, offs, lens = eng.upload_staged(ready, timings=tm)
+                t1 = time.perf_counter()
+                tm["upload_s"] += t1 - tu
+                img, hist, status = eng.fastq_to_images(dev, offs, lens)
+                st = status.cpu().numpy()
+                imgs = img.cpu().numpy()
+                nz = (hist != 0).any(dim=1).cpu().numpy()
+                t2 = time.perf_counter()
+                tm["kernels_s"] += t2 - t1
+                chooser.batch_done(bi, ready, t2 - t0)
 
-            def hand_over(batch=batch, st=st, imgs=imgs, nz=nz, per_file=(t2 - t0) / len(batch)):
-                # stats rows and PNG jobs of one batch: on a thread of its own (batches in order), beside the next batch's
-                # upload and inflate, in whose C calls this thread's interpreter lock is free (9 % of a .fq.gz pass before)
-                th = time.perf_counter()
-                for j, f in enumerate(batch):
-                    key = str(f.name.removesuffix("".join(f.suffixes)))
-                    s = stats.setdefault(key, OrderedDict())
-                    if st[j] or not nz[j]:
-                        eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
-                        s["failed_step"] = "image"
-                        continue
-                    s[str(k) + "mer_counting_time"] = per_file
-                    d, name = target(f)
-                    d.mkdir(parents=True, exist_ok=True)
-                    sample = key.split("@")[0]
-                    sd = base_sd.get(sample, 0)
-                    pending.append((key, time.perf_counter(),
-                                    pool.submit(write_png, imgs[j].copy(), d / name, labels.get(sample, []), sd,
-                                                QUAL_THRESH, mapping_code)))
-                tm["png_submit_s"] += time.perf_counter() - th   # (this thread's time: off the main thread's path)
+                def hand_over(batch=batch, st=st, imgs=imgs, nz=nz, per_file=(t2 - t0) / len(batch)):
+                    # stats rows and PNG jobs of one batch: on a thread of its own (batches in order), beside the next batch's
+                    # upload and inflate, in whose C calls this thread's interpreter lock is free (9 % of a .fq.gz pass before)
+                    th = time.perf_counter()
+                    for j, f in enumerate(batch):
+                        key = stem(f)
+                        s = stats.setdefault(key, OrderedDict())
+                        if st[j] or not nz[j]:
+                            eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
+                            s["failed_step"] = "image"
+                            continue
+                        s[str(k) + "mer_counting_time"] = per_file
+                        sink.submit(key, key.split("@")[0], image_name(f, k, mapping_code), imgs[j])
+                    tm["png_submit_s"] += time.perf_counter() - th   # (this thread's time: off the main thread's path)
 
-            handed.append(finisher.submit(hand_over))
-            if verbose:
-                eprint(f"batch of {len(batch)} files, {nbytes} bytes: upload {t1 - t0:.3f}s kernels {t2 - t1:.3f}s")
-        tt = time.perf_counter()
-        for h in handed:
-            h.result()   # (an exception of a batch's hand-over surfaces here)
-        for key, t, fut in pending:
-            fut.result()
-            stats[key]["k" + str(k) + "_img_time"] = time.perf_counter() - t
-        done = True
-    finally:
-        # An error anywhere above (a copy that runs out of memory, a PNG that cannot be written) must not leave the staging
-        # thread reading the next batch or queued hand-overs writing PNGs into outdir behind the caller's back.
-        for ex in (stager, finisher, pool):
-            ex.shutdown(wait=True, cancel_futures=not done)
-        if not done and engine is None:
-            eng.close()
-    tm["png_tail_s"] += time.perf_counter() - tt
-    tm["batches"] = tm.get("batches", 0) + bi + 1
-    if engine is None:
-        eng.close()
+                handed.append(finisher.submit(hand_over))
+                if verbose:
+                    eprint(f"batch of {len(batch)} files, {nbytes} bytes: upload {t1 - t0:.3f}s kernels {t2 - t1:.3f}s")
+            tt = time.perf_counter()
+            for h in handed:
+                h.result()   # (an exception of a batch's hand-over surfaces here)
+            sink.finish(stats)
+            done = True
+        finally:
+            # An error anywhere above (a copy that runs out of memory, a PNG that cannot be written) must not leave the staging
+            # thread reading the next batch or queued hand-overs writing PNGs into outdir behind the caller's back (the pool's
+            # turn comes last, as the scope is left).
+            for ex in (stager, finisher):
+                ex.shutdown(wait=True, cancel_futures=not done)
+        tm["png_tail_s"] += time.perf_counter() - tt
+        tm["batches"] = tm.get("batches", 0) + bi + 1
     return stats
 
 
@@ -271,72 +323,48 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
-    import os
-
-    from .engine import ImageEngine
     files = [Path(f) for f in files]
-    labels, base_sd, seeds = labels or {}, base_sd or {}, seeds or {}
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded: see fastqs_to_images)
     mine = [files[i] for i in shard_by_size(weights, rank, world)]   # size-aware; rank 0's view of the sizes: see shard.agreed_weights
-    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
-    outdir = Path(outdir)
-    outdir.mkdir(parents=True, exist_ok=True)
     stats = OrderedDict()
-    pool = ThreadPoolExecutor(io_threads)
-    pending = []
     if batch_bytes is None:
         batch_bytes = DEFAULT_GZ_BATCH_BYTES if mine and all(f.suffix == ".gz" for f in mine) else DEFAULT_BATCH_BYTES
-    done = False
-    try:   # (an error below must not leave the pool writing PNGs into outdir behind the caller's back: see fastqs_to_images)
-        i = 0
-        while i < len(mine):
-            batch, nbytes = [], 0
-            t0 = time.perf_counter()
-            for f in mine[i:]:
-                sz = gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
-                if batch and nbytes + sz > batch_bytes:
-                    break
-                batch.append(f)
-                nbytes += sz
-            i += len(batch)
-            names = [str(f.name.removesuffix("".join(f.suffixes))) for f in batch]
+    with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
+        for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
-            t1, t2 = _ladder_images(eng, dev, offs, lens, names, batch, t0, outdir, stats, pending, pool, k, mapping_code,
-                                    min_bp, max_bp, is_query, seeds, labels, base_sd, subfolder_levels)
+            t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
+                                    min_bp=min_bp, max_bp=max_bp, is_query=is_query)
             if verbose:
                 eprint(f"batch of {len(batch)} samples, {nbytes} bytes: upload+ladder {t1 - t0:.3f}s images {t2 - t1:.3f}s")
-        for s, t, fut in pending:
-            fut.result()
-            key = "k" + str(k) + "_img_time"
-            stats[s][key] = stats[s].get(key, 0) + (time.perf_counter() - t)
-        done = True
-    finally:
-        pool.shutdown(wait=True, cancel_futures=not done)
-        if not done and engine is None:
-            eng.close()
-    if engine is None:
-        eng.close()
+        sink.finish(stats)
     return stats
 
 
-def _ladder_images(eng, dev, offs, lens, names, sources, t0, outdir, stats, pending, pool, k, mapping_code, min_bp, max_bp,
-                   is_query, seeds, labels, base_sd, subfolder_levels):
-    """Steps C+D+E for one batch of cleaned samples in HBM (dev[offs[i] .. +lens[i]) is sample names[i], read from
-    sources[i]): the ladder, the images, the stats rows and the PNG jobs (appended to `pending`).  Returns the times
-    the ladder and the images were done."""
-    import torch
-
-    from .subsample import ladder_counts, split_name
-    # one seed per launch: samples with different seeds go in separate calls
+def _ladders(eng, text, offs, lens, names, seeds, **ladder):
+    """subsample.ladder_counts for the samples `names` in HBM (text[offs[i] .. +lens[i])), one launch per seed:
+    samples with different seeds go in separate calls.  The records, in the samples' order."""
+    from .subsample import ladder_counts
     by_seed = OrderedDict()
     for j, s in enumerate(names):
         by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
     recs = [None] * len(names)
     for seed, idx in by_seed.items():
-        for j, r in zip(idx, ladder_counts(eng, dev, offs[idx], lens[idx], seed=seed, min_bp=min_bp,
-                                           max_bp=max_bp, is_query=is_query)):
+        for j, r in zip(idx, ladder_counts(eng, text, offs[idx], lens[idx], seed=seed, **ladder)):
             recs[j] = r
+    return recs
+
+
+def _ladder_images(eng, text, offs, lens, names, sources, t0, sink, stats, seeds, **ladder):
+    """Steps C+D+E for one batch of cleaned samples in HBM (text[offs[i] .. +lens[i]) is sample names[i], read from
+    sources[i]; the batch was begun at t0): the ladder (seeds by sample, **ladder: min_bp, max_bp, is_query), the
+    images, the stats rows and the PNG jobs (to `sink`).  Returns the times the ladder and the images were done."""
+    import torch
+
+    from .subsample import split_name
+    k = sink.k
+    recs = _ladders(eng, text, offs, lens, names, seeds, **ladder)
     t1 = time.perf_counter()
     flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
     imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
@@ -357,12 +385,7 @@ def _ladder_images(eng, dev, offs, lens, names, sources, t0, outdir, stats, pend
             eprint("IMAGE FAIL:", split_name(s, bp))
             stats[s]["failed_step"] = "image"
             continue
-        name = png_name(split_name(s, bp) + "+k" + str(k) + ".fq.h5", mapping_code)
-        d = shard_folder(outdir, name, subfolder_levels)
-        d.mkdir(parents=True, exist_ok=True)
-        pending.append((s, time.perf_counter(),
-                        pool.submit(write_png, imgs[n].copy(), d / name, labels.get(s, []), base_sd.get(s, 0),
-                                    QUAL_THRESH, mapping_code)))
+        sink.submit(s, s, png_name(split_name(s, bp) + "+k" + str(k) + ".fq.h5", sink.mapping_code), imgs[n])
     return t1, t2
 
 
@@ -394,68 +417,62 @@ def _raw_plans(samples, weights, rank, world):
     the sum of its files' weights; None: agreed on here, a collective when sharded)."""
     plans = [(s, _sample_files(files)) for s, files in samples]
     if weights is None:
-        every = [f for _, sf in plans for f, _ in sf]
-        fw = agreed_weights(every) if world > 1 else file_weights(every)
-        weights, at = [], 0
-        for _, sf in plans:
-            weights.append(sum(fw[at:at + len(sf)]))
-            at += len(sf)
+        weights = sample_weights([(s, [f for f, _ in sf]) for s, sf in plans], world)
     return [plans[i] for i in shard_by_size(weights, rank, world)]
 
 
-def _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter, merge, dedup, adapters, detect_adapters,
-                   clean_dir, batch_bytes, verbose):
-    """Step B for this rank's raw samples `mine` [(sample, [(file, role)])], as raw_to_images and raw_to_query share
-    it: batch after batch is uploaded (a .gz inflated in HBM), gets its read budget (the files' line counts and mean
-    read lengths, one call each for the batch: ImageEngine.clean_lines / clean_heads), its adapters and is cleaned.
+@dataclass
+class Cleaning:
+    """Step B's options as raw_to_images and raw_to_query take them (their docstrings)."""
+    trim: tuple
+    adapter: bool
+    merge: bool
+    dedup: bool
+    adapters: tuple
+    detect_adapters: bool
+    clean_dir: object
+    max_bp: int
+
+
+def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, verbose):
+    """Step B for this rank's raw samples `mine` [(sample, [(file, role)])] under the options `opt` (Cleaning), as
+    raw_to_images and raw_to_query share it: batch after batch is uploaded (a .gz inflated in HBM), gets its read
+    budget (the files' line counts and mean read lengths, one call each for the batch: ImageEngine.clean_lines /
+    clean_heads), its adapters and is cleaned.
     Yields (text on the device, offsets, lengths, samples, time the cleaning was done) for the samples of a batch that
     came through; the others are reported (CLEAN FAIL) and get `failed_step` in stats.  Fills stats (`clean_basepairs`,
-    `cleaning_time`) and base_sd, and with clean_dir queues the writes of `<sample>.fq.gz` and
+    `cleaning_time`) and base_sd, and with opt.clean_dir queues the writes of `<sample>.fq.gz` and
     `<sample>_fastp_gpu.json` on the pool (their futures go to `writes`)."""
     import gzip
     import json
-    import os
 
     from .rawinput import content_curves, curves_sd
-    by_sequence = adapters is not None or detect_adapters
-    if by_sequence and not adapter:
+    by_sequence = opt.adapters is not None or opt.detect_adapters
+    if by_sequence and not opt.adapter:
         raise ValueError("adapters by sequence need adapter trimming (not -a)")
     explicit = [None, None, None]
-    if adapters is not None:
-        a1, a2 = adapters
+    if opt.adapters is not None:
+        a1, a2 = opt.adapters
         explicit = [a1, a2 if a2 is not None else a1, a1]
+    clean_dir = None if opt.clean_dir is None else Path(opt.clean_dir)
     if clean_dir is not None:
-        Path(clean_dir).mkdir(parents=True, exist_ok=True)
-
-    def text_bytes(f):
-        f = Path(f)
-        return gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
+        clean_dir.mkdir(parents=True, exist_ok=True)
 
     def write_clean(sample, text, curves, cutting=None):
-        with open(Path(clean_dir) / (sample + ".fq.gz"), "wb") as fh:
+        with open(clean_dir / (sample + ".fq.gz"), "wb") as fh:
             fh.write(gzip.compress(text, compresslevel=1))
         report = {"read1_after_filtering": {"content_curves": curves}}
         if cutting is not None:
             report["adapter_cutting"] = cutting
-        with open(Path(clean_dir) / (sample + "_fastp_gpu.json"), "w") as fh:
+        with open(clean_dir / (sample + "_fastp_gpu.json"), "w") as fh:
             json.dump(report, fh)
 
-    i = 0
-    while i < len(mine):
-        batch, nbytes = [], 0
-        t0 = time.perf_counter()
-        for s, sf in mine[i:]:
-            sz = sum(text_bytes(f) for f, _ in sf)
-            if batch and nbytes + sz > batch_bytes:
-                break
-            batch.append((s, sf))
-            nbytes += sz
-        i += len(batch)
+    for batch, nbytes, t0 in batches(mine, batch_bytes, size=lambda plan: sum(text_bytes(f) for f, _ in plan[1])):
         paths = [Path(f) for _, sf in batch for f, _ in sf]
         dev, offs, lens = eng.upload_files(paths, pool)
         lines = eng.clean_lines(dev, offs, lens)
         avgs = [0] * len(paths)
-        if max_bp is not None:   # (the mean length of each file's first 10,000 reads: estimate_read_lengths, commands/image.py:90-115)
+        if opt.max_bp is not None:   # (the mean length of each file's first 10,000 reads: estimate_read_lengths, commands/image.py:90-115)
             totals, counted = eng.clean_heads(dev, offs, lens, 10000)
             avgs = [round(int(t) / int(n)) if n else 0 for t, n in zip(totals, counted)]
         records, roles, owner, failed = [], [], [], set()
@@ -463,7 +480,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapte
         for j, (s, sf) in enumerate(batch):
             sl = slice(at, at + len(sf))
             try:
-                records += _budget(avgs[sl], lines[sl], sf, max_bp)
+                records += _budget(avgs[sl], lines[sl], sf, opt.max_bp)
             except ZeroDivisionError:     # (a file without reads and a read budget: the reference fails here too)
                 records += [0] * len(sf)
                 failed.add(j)
@@ -472,11 +489,12 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapte
             at += len(sf)
         table = None
         if by_sequence:
-            found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=trim[1])
-                     if detect_adapters else [[None] * 3 for _ in batch])
+            found = (eng.detect_adapters(dev, offs, lens, records, roles, owner, len(batch), trim_tail=opt.trim[1])
+                     if opt.detect_adapters else [[None] * 3 for _ in batch])
             table = [[e if e is not None else d for e, d in zip(explicit, det)] for det in found]
-        out, ooffs, olens, cst, status, *rest = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=trim,
-                                                          adapter=adapter, merge=merge, dedup=dedup, adapters=table)
+        out, ooffs, olens, cst, status, *rest = eng.clean(dev, offs, lens, records, roles, owner, len(batch), trim=opt.trim,
+                                                          adapter=opt.adapter, merge=opt.merge, dedup=opt.dedup,
+                                                          adapters=table)
         ast = rest[0] if rest else None   # (adapter stats: with a table only)
         del dev
         tc = time.perf_counter()
@@ -490,7 +508,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapte
             row = cst[j]
             curves = content_curves(row[2:2 + 160], row[162:202])
             base_sd[s] = curves_sd(curves)
-            st["clean_basepairs"] = int(row[0]) if (adapter or merge) else float("nan")
+            st["clean_basepairs"] = int(row[0]) if (opt.adapter or opt.merge) else float("nan")
             st["cleaning_time"] = (tc - t0) / len(batch)
             if clean_dir is not None:
                 text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
@@ -525,54 +543,31 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
-    from .engine import ImageEngine
-    labels, seeds = labels or {}, seeds or {}
     mine = _raw_plans(samples, weights, rank, world)
-    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
-    outdir = Path(outdir)
-    outdir.mkdir(parents=True, exist_ok=True)
-    stats, base_sd = OrderedDict(), {}
-    pool = ThreadPoolExecutor(io_threads)
-    pending, writes = [], []
-    done = False
-    try:   # (an error below must not leave the pool writing files into outdir behind the caller's back)
-        for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter,
-                                                           merge, dedup, adapters, detect_adapters, clean_dir,
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp)
+    stats, base_sd, writes = OrderedDict(), {}, []
+    with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels)
+        for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
                                                            batch_bytes or DEFAULT_BATCH_BYTES, verbose):
-            _ladder_images(eng, out, ooffs, olens, names, names, tc, outdir, stats, pending, pool, k, mapping_code, min_bp,
-                           max_bp, False, seeds, labels, base_sd, subfolder_levels)
+            _ladder_images(eng, out, ooffs, olens, names, names, tc, sink, stats, seeds or {}, min_bp=min_bp,
+                           max_bp=max_bp, is_query=False)
         for w in writes:
             w.result()
-        for s, t, fut in pending:
-            fut.result()
-            key = "k" + str(k) + "_img_time"
-            stats[s][key] = stats[s].get(key, 0) + (time.perf_counter() - t)
-        done = True
-    finally:
-        pool.shutdown(wait=True, cancel_futures=not done)
-        if not done and engine is None:
-            eng.close()
-    if engine is None:
-        eng.close()
+        sink.finish(stats)
     return stats, base_sd
 
 
 def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, found):
     """Step C of a query for cleaned samples in HBM: the one subsample that `query` images (split_fastq with
-    is_query, commands/image.py:677-701), a launch per seed.  found[sample] = (bp, histogram on the device, sd); a
-    sample without one is reported (SPLIT FAIL) and left out."""
-    from .subsample import ladder_counts
-    by_seed = OrderedDict()
-    for j, s in enumerate(names):
-        by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
-    for seed, idx in by_seed.items():
-        recs = ladder_counts(eng, text, offs[idx], lens[idx], seed=seed, max_bp=max_bp, is_query=True)
-        for j, rec in zip(idx, recs):
-            if rec["error"] or not rec["steps"]:
-                eprint("SPLIT FAIL:", sources[j], "-", rec["error"])
-                continue
-            bp, hist, _ = rec["steps"][0]
-            found[names[j]] = (bp, hist, base_sd.get(names[j], 0))
+    is_query, commands/image.py:677-701).  found[sample] = (bp, histogram on the device, sd); a sample without one
+    is reported (SPLIT FAIL) and left out."""
+    for s, source, rec in zip(names, sources, _ladders(eng, text, offs, lens, names, seeds, max_bp=max_bp, is_query=True)):
+        if rec["error"] or not rec["steps"]:
+            eprint("SPLIT FAIL:", source, "-", rec["error"])
+            continue
+        bp, hist, _ = rec["steps"][0]
+        found[s] = (bp, hist, base_sd.get(s, 0))
 
 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
@@ -583,28 +578,15 @@ def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), a
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
     the cleaned reads and their reports as raw_to_images writes them."""
-    from .engine import ImageEngine
-    seeds = seeds or {}
     mine = _raw_plans(samples, weights, rank, world)
-    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
-    stats, base_sd, found = OrderedDict(), {}, OrderedDict()
-    pool = ThreadPoolExecutor(io_threads)
-    writes = []
-    done = False
-    try:
-        for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, max_bp, trim, adapter,
-                                                          merge, dedup, adapters, detect_adapters, clean_dir,
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp)
+    stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
+    with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
                                                           batch_bytes or DEFAULT_BATCH_BYTES, verbose):
-            _query_rungs(eng, out, ooffs, olens, names, names, seeds, max_bp, base_sd, found)
+            _query_rungs(eng, out, ooffs, olens, names, names, seeds or {}, max_bp, base_sd, found)
         for w in writes:
             w.result()
-        done = True
-    finally:
-        pool.shutdown(wait=True, cancel_futures=not done)
-        if not done and engine is None:
-            eng.close()
-    if engine is None:
-        eng.close()
     return found
 
 
@@ -612,30 +594,11 @@ def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, 
                    batch_bytes=None, io_threads=8):
     """raw_to_query's result for samples = [(sample, its cleaned read file)] that an earlier run left in clean_dir
     (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table)."""
-    import os
-
-    from .engine import ImageEngine
     samples = [(s, Path(f)) for s, f in samples]
-    base_sd, seeds = base_sd or {}, seeds or {}
-    eng = engine or ImageEngine(k=k, mapping=mapping_code, device=device)
     found = OrderedDict()
-    pool = ThreadPoolExecutor(io_threads)
-    batch_bytes = batch_bytes or DEFAULT_BATCH_BYTES
-    try:
-        i = 0
-        while i < len(samples):
-            batch, nbytes = [], 0
-            for s, f in samples[i:]:
-                sz = gz_text_bytes(f) if f.suffix == ".gz" else os.path.getsize(f)
-                if batch and nbytes + sz > batch_bytes:
-                    break
-                batch.append((s, f))
-                nbytes += sz
-            i += len(batch)
-            dev, offs, lens = eng.upload_files([f for _, f in batch], pool)
-            _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], [f for _, f in batch], seeds, max_bp, base_sd, found)
-    finally:
-        pool.shutdown(wait=True)
-        if engine is None:
-            eng.close()
+    with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        for batch, _, _ in batches(samples, batch_bytes or DEFAULT_BATCH_BYTES, size=lambda sample: text_bytes(sample[1])):
+            files = [f for _, f in batch]
+            dev, offs, lens = eng.upload_files(files, pool)
+            _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], files, seeds or {}, max_bp, base_sd or {}, found)
     return found
