@@ -294,6 +294,37 @@ int vk_clean_adapters_device(vk_ctx* ctx, const void* d_text, const uint64_t* of
                              uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, const uint32_t* adapter_lengths,
                              const uint8_t* adapter_seqs, uint64_t* d_adapter_stats);
 
+/* Step C's files: replaces run_parallel_reformats / run_reformat (commands/image.py:577-627: one `reformat.sh
+ * samplebasestarget=N sampleseed=S breaklength=500 iupacToN=t` per subsample) for the steps of a batch of cleaned
+ * samples resident in HBM.  The rule is this project's ("Step C", and tests/ladder_emit_ref.py), not
+ * BBTools byte for byte: step j writes, in input order, the records of sample step_sample[j] that
+ * vk_count_sampled_device counts with seed step_seed[j] and threshold step_threshold[j] (in [0, 2^32]) -- a read of
+ * more than 500 bases as records of 500, named `<header>_<n>` -- or, with step_whole[j] != 0, every record uncut
+ * (what vk_count_device counts).  A record is four lines ended by '\n' (a trailing '\r' dropped, the third line a
+ * bare '+'); sequence bytes outside ACGTacgt are written as 'N'.  Counting a step's text gives the step's histogram.
+ *
+ * Samples as for vk_count_device: offsets[i] is a multiple of 16 (the newline passes load 16 bytes at a time from the
+ * sample's start), any other offset returns VK_EINVAL before anything is read; the records inside a sample, its end and
+ * the records of its files lie at any residue.  records[i] (host) = the lines of sample i over 4, a last line without '\n'
+ * counted: (vk_clean_lines_device's lines[i] + 1) / 4.  d_ws: caller-allocated device workspace of
+ * vk_ladder_emit_workspace_size bytes (same records and step_sample).  Host arrays out: out_lengths[nsteps] the bytes
+ * of each step's file, out_offsets[nsteps] where it starts in d_out (a multiple of 16; the bytes up to its 16-byte
+ * rounded end are zeroed) and status[nsamples]: VK_ST_* as vk_read_index_device reports them, VK_EM_TOO_LARGE for a
+ * sample of 4 GiB or more, VK_EM_BAD_RECORDS when records[i] is not the sample's.  A sample with a non-zero status
+ * gives its steps no text.  The files lie one after another and take the sum of their rounded lengths: when that is
+ * more than out_capacity the call returns VK_ENOSPC with out_lengths and status filled and d_out untouched (d_out
+ * NULL with out_capacity 0 asks for the sizes only).  The call synchronises. */
+#define VK_ENOSPC 6            /* the output does not fit the caller's buffer */
+#define VK_EM_TOO_LARGE 4u
+#define VK_EM_BAD_RECORDS 8u
+int vk_ladder_emit_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths,
+                                  const uint32_t* step_sample, uint32_t nsteps, uint64_t* bytes);
+int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths,
+                          const uint64_t* records, uint32_t nsamples, const uint32_t* step_sample,
+                          const uint64_t* step_seed, const uint64_t* step_threshold, const uint8_t* step_whole,
+                          uint32_t nsteps, uint8_t* d_out, uint64_t out_capacity, uint64_t* out_offsets,
+                          uint64_t* out_lengths, uint32_t* status, void* d_ws, uint64_t ws_bytes);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

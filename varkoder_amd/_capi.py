@@ -6,8 +6,9 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VKIMG_LIB") or os.path.join(HERE, "libvkimg_hip.so")  # (VKIMG_LIB: A/B timing of experimental builds)
 
-VK_OK, VK_EINVAL, VK_EHIP, VK_ENOMAP, VK_EFORMAT, VK_ENOMEM = 0, 1, 2, 3, 4, 5
+VK_OK, VK_EINVAL, VK_EHIP, VK_ENOMAP, VK_EFORMAT, VK_ENOMEM, VK_ENOSPC = 0, 1, 2, 3, 4, 5, 6
 VK_ST_BAD_START, VK_ST_BAD_PHASE = 1, 2
+VK_EM_TOO_LARGE, VK_EM_BAD_RECORDS = 4, 8
 VK_CL_ROLE_UNPAIRED, VK_CL_ROLE_R1, VK_CL_ROLE_R2 = 0, 1, 2
 VK_CL_ADAPTER, VK_CL_MERGE, VK_CL_DEDUP = 1, 2, 4
 VK_CL_BAD_FRAMING, VK_CL_RAGGED = 1, 2
@@ -22,7 +23,8 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_last_count_launch", "vk_count_sampled_device", "vk_inflate_device", "vk_upload_mapped", "vk_host_register", "vk_host_unregister",
            "vk_synth_shaped_lengths", "vk_synth_shaped_device", "vk_last_count_general", "vk_read_index_device", "vk_count_index_device",
            "vk_clean_lines_device", "vk_clean_workspace_size", "vk_clean_device", "vk_clean_detect_workspace_size",
-           "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device")
+           "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device", "vk_ladder_emit_workspace_size",
+           "vk_ladder_emit_device")
 
 _lib = None
 
@@ -81,6 +83,9 @@ def lib():
     L.vk_clean_adapters_device.argtypes = [vp, vp, u64p, u64p, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p, C.c_uint64, vp, vp, vp, u32p,
                                            u8p, vp]
+    L.vk_ladder_emit_workspace_size.argtypes = [u64p, C.c_uint32, u64p, u32p, C.c_uint32, u64p]
+    L.vk_ladder_emit_device.argtypes = [vp, vp, u64p, u64p, u64p, C.c_uint32, u32p, u64p, u64p, u8p, C.c_uint32, vp, C.c_uint64,
+                                        u64p, u64p, u32p, vp, C.c_uint64]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]
     L.vk_preprocess_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float, vp]

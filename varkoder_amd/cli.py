@@ -9,7 +9,9 @@ drawn on the GPU).  `--from-raw` enters at step B like the reference's own `varK
 the input is a folder `<taxon>/<sample>/<reads>.fq[.gz]` or a CSV `labels,sample,files`, the reads are cleaned on
 the GPU (rules: INTEGRATION.md, "Step B"; -a/-D/-r/-T take effect, -M sets the read budget) and go on to the ladder
 without leaving the device; with `-i INT` the cleaned reads and their base-content report are also written to
-`INT/clean_reads/` (and reused there by a later run unless -x).  `stats.csv` (and `labels.csv` with -t) are written
+`INT/clean_reads/` (and reused there by a later run unless -x).  With `--write-splits` (and `-i INT`) both entries also
+write every subsample's reads to `INT/split_fastqs/`, the folder the default entry takes (rules: INTEGRATION.md,
+"Step C"), and `-X` then stops after these intermediates.  `stats.csv` (and `labels.csv` with -t) are written
 like process_stats does (commands/image.py:1144-1185).  With torchrun, ranks shard the files (samples).
 
 `python -m varkoder_amd query ...`: `varKoder query` (run_query); with `--from-raw` from raw reads, cleaned on the GPU
@@ -69,7 +71,9 @@ def setup_parser():
     p.add_argument("-a", "--no-adapter", action="store_true", help="with --from-raw: no adapter trimming; otherwise accepted for parity")
     p.add_argument("-D", "--no-deduplicate", action="store_true", help="with --from-raw: no deduplication; otherwise accepted for parity")
     p.add_argument("-r", "--no-merge", action="store_true", help="with --from-raw: no merging of read pairs; otherwise accepted for parity")
-    p.add_argument("-X", "--no-image", action="store_true", help="nothing to do here without images")
+    p.add_argument("-X", "--no-image", action="store_true",
+                   help="with --write-splits: stop after the intermediate files (no counting, no images); otherwise "
+                        "nothing to do here without images")
     p.add_argument("-T", "--trim-bp", default="10,10",
                    help="with --from-raw: bases trimmed from the front and the tail of every read; otherwise accepted for parity")
     p.add_argument("--labels-csv", help="optional CSV `sample,labels` (labels separated by ';')")
@@ -81,6 +85,10 @@ def setup_parser():
     entry.add_argument("--from-raw", action="store_true",
                        help="input holds RAW reads (`<taxon>/<sample>/*.fq[.gz]` or a CSV labels,sample,files): clean them "
                             "on the GPU (step B, the reference's fastp pass) and go on with the ladder")
+    p.add_argument("--write-splits", action="store_true", default=argparse.SUPPRESS,   # (absent = off, as the adapter flags)
+                   help="with --from-raw / --from-clean and -i INT: also write every subsample's reads to "
+                        "`INT/split_fastqs/<sample>@<bp>K.fq.gz`, the files the default entry takes (kept unless -x "
+                        "when a sample's files are all there)")
     add_adapter_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
@@ -156,6 +164,11 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
+    if args.command == "image" and getattr(args, "write_splits", False):
+        if not (args.from_raw or args.from_clean):
+            parser.error("--write-splits: only with --from-raw or --from-clean")
+        if not args.int_folder:
+            parser.error("--write-splits: needs -i/--int-folder")
     if args.command in ("image", "query"):
         given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
         if given and not args.from_raw:
@@ -451,6 +464,14 @@ def parse_size(text):
     return int(float(t))
 
 
+def split_options(args):
+    """--write-splits as pipeline.clean_to_images and raw_to_images take it: the folder, -x, and -X (honoured with the
+    flag only: commands/image.py:1055)."""
+    if not getattr(args, "write_splits", False):
+        return {}
+    return dict(split_dir=Path(args.int_folder) / "split_fastqs", overwrite=args.overwrite, no_image=args.no_image)
+
+
 def run_image_from_clean(args, outdir, rank, world, local_rank):
     from .image import base_sd_table, stem
     from .pipeline import clean_to_images
@@ -470,7 +491,7 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
         failpoint(rank)
         per_sample = clean_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
                                      min_bp=parse_size(args.min_bp), max_bp=max_bp, seeds=seeds, labels=labels,
-                                     base_sd=base_sd,
+                                     base_sd=base_sd, **split_options(args),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
                                      verbose=args.verbose)
         for s, v in per_sample.items():
@@ -496,7 +517,7 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
         failpoint(rank)
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
-                      io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
+                      io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, **cleaning, **common)
             per_sample.update(got)

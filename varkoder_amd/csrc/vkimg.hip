@@ -51,6 +51,7 @@
 #include "vk_aux.h"
 #include "vk_clean.h"
 #include "vk_adapter.h"
+#include "vk_emit.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -603,6 +604,7 @@ const char* vk_strerror(int status) {
         case VK_ENOMAP: return "no k-mer mapping installed for this k";
         case VK_EFORMAT: return "inconsistent FASTQ framing";
         case VK_ENOMEM: return "out of memory";
+        case VK_ENOSPC: return "the output does not fit the buffer";
         default: return "unknown status";
     }
 }
@@ -2091,6 +2093,131 @@ int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offs
                 break;
             }
     }
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------- step C's files --
+
+namespace {
+
+// the pieces of a vk_ladder_emit_device workspace: the record index in vk_clean_device's layout (the pieces of it that
+// cl_index_run fills), then the steps' tables and the items' bytes
+struct EmLayout {
+    ClLayout c;
+    EmSample* samples;
+    EmStep* steps;
+    uint64_t *step_base, *sizes, *obytes, *oprefix;
+    uint32_t* status;
+    size_t total;
+    uint64_t nitems;
+};
+
+EmLayout em_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, const uint32_t* step_sample,
+                   uint32_t nsteps) {
+    EmLayout L{};
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        L.c.nrec += records[i];
+    }
+    for (uint32_t j = 0; j < nsteps; ++j) L.nitems += step_sample[j] < nsamples ? records[step_sample[j]] : 0;
+    const uint64_t nb = (std::max(L.c.nchunks, L.nitems) + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.c.files, nsamples);
+    take(L.c.fchunk, nsamples);
+    take(L.c.ccount, L.c.nchunks);
+    take(L.c.cprefix, L.c.nchunks + 1);
+    take(L.c.sums, nb + 1);
+    take(L.c.recs, L.c.nrec);
+    take(L.samples, nsamples);
+    take(L.status, nsamples);
+    take(L.steps, nsteps);
+    take(L.step_base, nsteps + 1ull);
+    take(L.sizes, nsteps);
+    take(L.obytes, L.nitems);
+    take(L.oprefix, L.nitems + 1);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_ladder_emit_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths,
+                                  const uint32_t* step_sample, uint32_t nsteps, uint64_t* bytes) {
+    if (!bytes || (nsamples && (!records || !lengths)) || (nsteps && !step_sample)) return VK_EINVAL;
+    *bytes = em_layout(nullptr, records, nsamples, lengths, step_sample, nsteps).total;
+    return VK_OK;
+}
+
+int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths,
+                          const uint64_t* records, uint32_t nsamples, const uint32_t* step_sample,
+                          const uint64_t* step_seed, const uint64_t* step_threshold, const uint8_t* step_whole,
+                          uint32_t nsteps, uint8_t* d_out, uint64_t out_capacity, uint64_t* out_offsets,
+                          uint64_t* out_lengths, uint32_t* status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nsamples == 0 || !d_fastq || !offsets || !lengths || !records || !status || !d_ws) return VK_EINVAL;
+    if (nsteps && (!step_sample || !step_seed || !step_threshold || !step_whole || !out_offsets || !out_lengths)) return VK_EINVAL;
+    if (!d_out && out_capacity) return VK_EINVAL;
+    for (uint32_t i = 0; i < nsamples; ++i)
+        if (offsets[i] % 16) return VK_EINVAL;
+    for (uint32_t j = 0; j < nsteps; ++j)
+        if (step_sample[j] >= nsamples || step_threshold[j] > (1ull << 32)) return VK_EINVAL;
+    const EmLayout L = em_layout(d_ws, records, nsamples, lengths, step_sample, nsteps);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    // a sample is one file of the record index
+    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
+    std::vector<EmSample> smp(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i)
+        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
+                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
+    std::vector<EmStep> steps(nsteps);
+    std::vector<uint64_t> step_base(nsteps + 1ull, 0);
+    for (uint32_t j = 0; j < nsteps; ++j) {
+        steps[j] = EmStep{step_seed[j], step_threshold[j], 0, step_sample[j], step_whole[j] ? 1u : 0u};
+        step_base[j + 1] = step_base[j] + records[step_sample[j]];
+    }
+    const uint64_t nitems = step_base[nsteps];
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_fastq);
+    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.step_base, step_base.data(), step_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (nsteps) VK_HIP(ctx, hipMemcpyAsync(L.steps, steps.data(), nsteps * sizeof(EmStep), hipMemcpyHostToDevice, ctx->stream));
+    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                       L.samples, nsamples, L.c.recs, L.c.cprefix, L.status);
+    if (nitems)
+        hipLaunchKernelGGL(vk_em_plan_kernel, dim3((nitems + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                           L.samples, L.steps, L.step_base, nsteps, nitems, L.c.recs, L.status, L.obytes);
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.obytes, nitems, L.c.sums, L.oprefix);
+    if (rc) return rc;
+    if (nsteps)
+        hipLaunchKernelGGL(vk_em_sizes_kernel, dim3((nsteps + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                           L.step_base, nsteps, L.oprefix, L.sizes);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(status, L.status, nsamples * 4ull, hipMemcpyDeviceToHost, ctx->stream));
+    if (nsteps) VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.sizes, nsteps * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // the files one after another, each at a multiple of 16 bytes
+    uint64_t at = 0;
+    for (uint32_t j = 0; j < nsteps; ++j) {
+        out_offsets[j] = steps[j].out_off = at;
+        at += (out_lengths[j] + 15) / 16 * 16;
+    }
+    if (at > out_capacity) return VK_ENOSPC;
+    if (at == 0) return VK_OK;
+    VK_HIP(ctx, hipMemcpyAsync(L.steps, steps.data(), nsteps * sizeof(EmStep), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(vk_em_write_kernel, dim3((nitems + kEmItemsPerBlock - 1) / kEmItemsPerBlock), dim3(kClThreads), 0,
+                       ctx->stream, text, L.samples, L.steps, L.step_base, nsteps, nitems, L.c.recs, L.oprefix, d_out);
+    hipLaunchKernelGGL(vk_em_pad_kernel, dim3((nsteps + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.steps,
+                       nsteps, L.sizes, d_out);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
     return VK_OK;
 }
 

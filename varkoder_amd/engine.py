@@ -693,6 +693,55 @@ class ImageEngine:
             _capi.check(self.ctx, st, "vk_clean_adapters_device")
         return (out, out_offs) + tuple(t.cpu().numpy().astype(dt) for t, dt in results)
 
+    def ladder_emit(self, fastq, offsets, lengths, step_sample, step_seed, step_threshold, step_whole, records=None,
+                    capacity=None, out=None):
+        """Step C's files for cleaned samples in HBM (vk_ladder_emit_device): step j writes the reads of sample
+        step_sample[j] that count_sampled counts with step_seed[j] / step_threshold[j] -- with step_whole[j] every
+        read, as count does -- as FASTQ text.  records: the samples' record counts (None: clean_lines here).
+        Returns (text uint8 tensor on the device, offsets uint64[nsteps], lengths uint64[nsteps], status
+        uint32[nsamples]); a sample with a non-zero status gives no text.  capacity: bytes of the text buffer (None:
+        what the selection is expected to take; the call is repeated once with the size it reports when that falls
+        short); with a capacity given, text that does not fit raises VkError(VK_ENOSPC) and nothing is written.  out: the
+        text buffer to use (a uint8 device tensor of at least `capacity` bytes).  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        sidx = np.ascontiguousarray(step_sample, dtype=np.uint32)
+        seeds = np.ascontiguousarray(step_seed, dtype=np.uint64)
+        thr = np.ascontiguousarray(step_threshold, dtype=np.uint64)
+        whole = np.ascontiguousarray(step_whole, dtype=np.uint8)
+        ns = len(sidx)
+        if not (len(seeds) == len(thr) == len(whole) == ns):
+            raise ValueError("one sample, seed, threshold and whole flag per step")
+        if records is None:
+            records = (self.clean_lines(fastq, offs, lens) + np.uint64(1)) // np.uint64(4)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_ladder_emit_workspace_size(_u64(recs), n, _u64(lens), _u32(sidx), ns, C.byref(ws_bytes)),
+                    "vk_ladder_emit_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        out_offs = np.zeros(ns, dtype=np.uint64)
+        out_lens = np.zeros(ns, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        if out is not None and (capacity is None or out.numel() < capacity):
+            raise ValueError("a text buffer needs its capacity, within its size")
+        want = capacity
+        if want is None:   # (a read's text is its record's, and a cut read's header comes once per piece: a tenth on top)
+            share = np.where(whole != 0, 1.0, thr.astype(np.float64) / float(1 << 32))
+            want = int((share * lens[sidx.astype(np.int64)].astype(np.float64)).sum() * 1.1) + 16 * ns + 4096
+        for attempt in range(2):
+            if out is None or capacity is None:
+                out = torch.empty(want + 64, dtype=torch.uint8, device=self.device)   # (readable past the last file's end)
+            st = self.L.vk_ladder_emit_device(self.ctx, self._ptr(fastq), _u64(offs), _u64(lens), _u64(recs), n, _u32(sidx),
+                                              _u64(seeds), _u64(thr), _u8(whole), ns, self._ptr(out), want, _u64(out_offs),
+                                              _u64(out_lens), _u32(status), self._ptr(ws), ws.numel())
+            if st != _capi.VK_ENOSPC or capacity is not None or attempt:
+                break
+            out = None   # (free the short buffer before the next one is made)
+            want = int(((out_lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)).sum())
+        _capi.check(self.ctx, st, "vk_ladder_emit_device")
+        return out, out_offs, out_lens, status
+
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""
         torch = _torch()

@@ -14,7 +14,7 @@ from contextlib import contextmanager
 from dataclasses import dataclass
 from pathlib import Path
 
-from .config import QUAL_THRESH
+from .config import QUAL_THRESH, SAMPLE_BP_SEP
 from .image import counts_name, eprint, png_name, shard_folder, stem, write_png
 from .shard import TailQueue, agreed_weights, file_weights, gz_text_bytes, shard_by_size, split_head_tail
 
@@ -315,11 +315,15 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
-                    io_threads=8, engine=None, verbose=False, weights=None):
+                    io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
     reformat.sh, and every step becomes `<sample>@<bp>K+<mapping>+k<k>.png`.
+
+    split_dir: also write every step's reads to `split_dir/<sample>@<bp>K.fq.gz` (SplitSink), as the reference's
+    split_fastq leaves them; overwrite: also where a sample's files are all there.  no_image (with split_dir: the
+    reference's -X, :1055): stop after step C -- no counting, no PNG.
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -332,41 +336,134 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
         batch_bytes = DEFAULT_GZ_BATCH_BYTES if mine and all(f.suffix == ".gz" for f in mine) else DEFAULT_BATCH_BYTES
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
+        splits = SplitSink(split_dir, pool, overwrite) if split_dir is not None else None
         for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
-                                    min_bp=min_bp, max_bp=max_bp, is_query=is_query)
+                                    splits=splits, no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=is_query)
             if verbose:
                 eprint(f"batch of {len(batch)} samples, {nbytes} bytes: upload+ladder {t1 - t0:.3f}s images {t2 - t1:.3f}s")
+        if splits is not None:
+            splits.finish()
         sink.finish(stats)
     return stats
+
+
+def _seed_groups(names, seeds):
+    """{seed: [indices into names]}: samples with different seeds go in separate calls."""
+    by_seed = OrderedDict()
+    for j, s in enumerate(names):
+        by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
+    return by_seed
 
 
 def _ladders(eng, text, offs, lens, names, seeds, **ladder):
     """subsample.ladder_counts for the samples `names` in HBM (text[offs[i] .. +lens[i])), one launch per seed:
     samples with different seeds go in separate calls.  The records, in the samples' order."""
     from .subsample import ladder_counts
-    by_seed = OrderedDict()
-    for j, s in enumerate(names):
-        by_seed.setdefault(int(seeds.get(s, 0)), []).append(j)
     recs = [None] * len(names)
-    for seed, idx in by_seed.items():
+    for seed, idx in _seed_groups(names, seeds).items():
         for j, r in zip(idx, ladder_counts(eng, text, offs[idx], lens[idx], seed=seed, **ladder)):
             recs[j] = r
     return recs
 
 
-def _ladder_images(eng, text, offs, lens, names, sources, t0, sink, stats, seeds, **ladder):
+def _ladder_plans(eng, text, offs, lens, names, **ladder):
+    """_ladders' records without the counting (a run that only writes step C's files): the read index and the plan;
+    a step is (bp, None, None)."""
+    from .subsample import ladder_plan
+    nsites, status = eng.read_index(text, offs, lens)
+    recs, plans = ladder_plan(nsites, status, **ladder)
+    for rec, sizes in zip(recs, plans):
+        rec["steps"] = [(bp, None, None) for bp in sizes]
+    return recs
+
+
+class SplitSink:
+    """Where step C's files go: `<split_dir>/<sample>@<bp>K.fq.gz` (split_fastq, commands/image.py:696-714), gzip'ed on
+    the pool like the cleaned reads of clean_dir.  A sample whose files are all there is left alone unless `overwrite`
+    (:711-714); a file gets its name only once it is whole (written under a temporary name without the `@`, then renamed), so a run that
+    was killed leaves nothing that the next one would take for done.  At most MAX_PENDING_BYTES of text wait for
+    their gzip, besides the slice being queued."""
+
+    MAX_PENDING_BYTES = 1 << 30
+
+    def __init__(self, split_dir, pool, overwrite):
+        self.dir, self.pool, self.overwrite = Path(split_dir), pool, overwrite
+        self.pending = []   # [(the futures of one slice, its bytes on the host)], oldest first
+        self.dir.mkdir(parents=True, exist_ok=True)
+
+    def path(self, sample, bp):
+        from .subsample import split_name
+        return self.dir / (split_name(sample, bp) + ".fq.gz")
+
+    def done(self, sample, sizes):
+        return not self.overwrite and all(self.path(sample, bp).is_file() for bp in sizes)
+
+    @staticmethod
+    def _write(path, text):
+        import gzip
+        part = path.with_name(".part." + path.name.replace(SAMPLE_BP_SEP, "+"))   # (no file of a sample to the default entry)
+        with open(part, "wb") as fh:
+            fh.write(gzip.compress(text, compresslevel=1))
+        os.replace(part, path)
+
+    def _drain(self, room):
+        """Wait for the oldest slices' files until no more than `room` bytes of text are waiting."""
+        while self.pending and sum(n for _, n in self.pending) > room:
+            for fut in self.pending.pop(0)[0]:
+                fut.result()
+
+    def emit(self, eng, text, offs, lens, names, recs, seeds, **ladder):
+        """The files of the samples `names` in HBM whose ladder `recs` (_ladders / _ladder_plans) has steps: emitted
+        on the GPU by the counting's own plan (subsample.ladder_files), copied back a slice at a time, queued.  A sample
+        that the emit's framing check refuses gets the error of a failed split in its record and loses its steps."""
+        from .subsample import ladder_files
+        for seed, idx in _seed_groups(names, seeds).items():
+            skip = set()
+            for local, j in enumerate(idx):
+                sizes = [bp for bp, _, _ in recs[j]["steps"]]
+                if sizes and self.done(names[j], sizes):
+                    eprint("Skipping subsampling for", names[j] + ":", "Files exist.")
+                    skip.add(local)
+            nsites = [recs[j]["nsites"] for j in idx]
+            status = [recs[j]["status"] for j in idx]
+            failed = {}
+            for dev, steps in ladder_files(eng, text, offs[idx], lens[idx], nsites, status, seed=seed, skip=skip,
+                                           failed=failed, **ladder):
+                self._drain(self.MAX_PENDING_BYTES)
+                host = dev.cpu().numpy()
+                del dev
+                # (gzip reads a file's bytes where they lie in the slice: no second copy)
+                self.pending.append(([self.pool.submit(self._write, self.path(names[idx[local]], bp), host[o:o + n])
+                                      for local, bp, o, n in steps], host.nbytes))
+            for local, st in failed.items():
+                recs[idx[local]]["error"] = "inconsistent FASTQ framing (status %d writing the files)" % st
+                recs[idx[local]]["steps"] = []
+
+    def finish(self):
+        """Wait for every file (a failed write raises here)."""
+        self._drain(-1)
+
+
+def _ladder_images(eng, text, offs, lens, names, sources, t0, sink, stats, seeds, splits=None, no_image=False, **ladder):
     """Steps C+D+E for one batch of cleaned samples in HBM (text[offs[i] .. +lens[i]) is sample names[i], read from
-    sources[i]; the batch was begun at t0): the ladder (seeds by sample, **ladder: min_bp, max_bp, is_query), the
-    images, the stats rows and the PNG jobs (to `sink`).  Returns the times the ladder and the images were done."""
+    sources[i]; the batch was begun at t0): the ladder (seeds by sample, **ladder: min_bp, max_bp, is_query), with
+    `splits` (SplitSink) its files, the images, the stats rows and the PNG jobs (to `sink`); no_image: the ladder's plan
+    and files only.  Returns the times the ladder and the images were done."""
     import torch
 
     from .subsample import split_name
     k = sink.k
-    recs = _ladders(eng, text, offs, lens, names, seeds, **ladder)
+    if no_image:
+        recs = _ladder_plans(eng, text, offs, lens, names, **ladder)
+    else:
+        recs = _ladders(eng, text, offs, lens, names, seeds, **ladder)
+    t_counted = time.perf_counter()
+    if splits is not None:   # (the files are the splitting's time, not the counting's)
+        splits.emit(eng, text, offs, lens, names, recs, seeds, **ladder)
     t1 = time.perf_counter()
-    flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
+    flat = [] if no_image else [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
     imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
     nz = [bool((h != 0).any().item()) for _, _, h in flat]
     t2 = time.perf_counter()
@@ -378,7 +475,8 @@ def _ladder_images(eng, text, offs, lens, names, sources, t0, sink, stats, seeds
             continue
         st["splitting_time"] = (t1 - t0) / len(names)
         st["splitting_bp_per_file"] = ",".join(str(bp) for bp, _, _ in recs[j]["steps"])
-        st[str(k) + "mer_counting_time"] = (t1 - t0) / len(names)
+        if not no_image:
+            st[str(k) + "mer_counting_time"] = (t_counted - t0) / len(names)
     for n, (j, bp, _) in enumerate(flat):
         s = names[j]
         if not nz[n]:
@@ -529,7 +627,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
-                  detect_adapters=False):
+                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -540,6 +638,8 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     sequence ("Step B"); an explicit sequence wins over detection for its groups, detection runs per
     batch (ImageEngine.detect_adapters) after the read budget.  The JSON then holds `adapter_cutting`.
 
+    split_dir, overwrite, no_image: as clean_to_images takes them.
+
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
@@ -548,12 +648,15 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels)
+        splits = SplitSink(split_dir, pool, overwrite) if split_dir is not None else None
         for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
                                                            batch_bytes or DEFAULT_BATCH_BYTES, verbose):
-            _ladder_images(eng, out, ooffs, olens, names, names, tc, sink, stats, seeds or {}, min_bp=min_bp,
-                           max_bp=max_bp, is_query=False)
+            _ladder_images(eng, out, ooffs, olens, names, names, tc, sink, stats, seeds or {}, splits=splits,
+                           no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=False)
         for w in writes:
             w.result()
+        if splits is not None:
+            splits.finish()
         sink.finish(stats)
     return stats, base_sd
 

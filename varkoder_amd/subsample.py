@@ -58,6 +58,32 @@ def threshold(bp, nsites):
     return min(ALL_READS, int(bp) * ALL_READS // int(nsites))
 
 
+def ladder_plan(nsites, status, min_bp=50000, max_bp=None, is_query=False):
+    """The ladder of every sample of a batch from its read index (nsites, status): (records, plans) -- per sample an
+    OrderedDict(nsites, status, steps=[], error) and the sizes (bp) of its steps, largest first.  ladder_counts and
+    ladder_files both start here."""
+    out, plans = [], []
+    for i in range(len(nsites)):
+        rec = OrderedDict(nsites=int(nsites[i]), status=int(status[i]), steps=[], error=None)
+        try:
+            sizes = sites_ladder(nsites[i], min_bp, max_bp, is_query) if not status[i] else []
+            if status[i]:
+                rec["error"] = "inconsistent FASTQ framing"
+        except Exception as e:  # noqa: BLE001 - the reference's "less than minimum data"
+            sizes, rec["error"] = [], str(e)
+        plans.append(sizes)
+        out.append(rec)
+    return out, plans
+
+
+def plan_steps(plans, nsites, seed):
+    """The steps of a batch as the kernels take them, from ladder_plan's sizes: (sample, level, bp, seed + level,
+    threshold, whole) in the samples' order, largest first.  whole: the step takes every read and is counted plainly
+    (the first step of a sample that holds no more than it asks for)."""
+    return [(i, level, bp, seed + level, threshold(bp, nsites[i]), level == 0 and bp >= nsites[i])
+            for i in range(len(plans)) for level, bp in enumerate(plans[i])]
+
+
 def ladder_counts(engine, fastq, offsets, lengths, seed=0, min_bp=50000, max_bp=None, is_query=False, parts=0):
     """All ladder steps of a batch of cleaned samples resident in HBM.
 
@@ -75,17 +101,7 @@ def ladder_counts(engine, fastq, offsets, lengths, seed=0, min_bp=50000, max_bp=
         full_hist, nsites, status_h = engine.count_index(fastq, offsets, lengths, parts=parts)
     else:
         nsites, status_h = engine.read_index(fastq, offsets, lengths, parts=parts)
-    out, plans = [], []
-    for i in range(n):
-        rec = OrderedDict(nsites=int(nsites[i]), status=int(status_h[i]), steps=[], error=None)
-        try:
-            sizes = sites_ladder(nsites[i], min_bp, max_bp, is_query) if not status_h[i] else []
-            if status_h[i]:
-                rec["error"] = "inconsistent FASTQ framing"
-        except Exception as e:  # noqa: BLE001 - the reference's "less than minimum data"
-            sizes, rec["error"] = [], str(e)
-        plans.append(sizes)
-        out.append(rec)
+    out, plans = ladder_plan(nsites, status_h, min_bp, max_bp, is_query)
     # steps that take everything: the plain count of those samples, one launch
     whole = [i for i in range(n) if plans[i] and plans[i][0] >= nsites[i]]
     if whole and full_hist is not None:
@@ -97,9 +113,10 @@ def ladder_counts(engine, fastq, offsets, lengths, seed=0, min_bp=50000, max_bp=
             out[i]["steps"].append((plans[i][0], h[j], int(nsites[i])))
     # every further step of every sample in ONE launch: a (sample, step) pair is a sample of its own to the kernel
     # (same bytes, its own seed and threshold)
-    pairs = [(i, level) for i in range(n) for level, bp in enumerate(plans[i]) if not (level == 0 and bp >= nsites[i])]
+    sampled = [st for st in plan_steps(plans, nsites, seed) if not st[5]]
+    pairs = [(i, level) for i, level, _, _, _, _ in sampled]
     if pairs:
-        thr_all = np.array([threshold(plans[i][level], nsites[i]) for i, level in pairs], dtype=np.uint64)
+        thr_all = np.array([st[4] for st in sampled], dtype=np.uint64)
         # k = 8, 9: the walker only pays for subsamples of a few per cent of the reads (WALK_MAX_THRESHOLD_SPILL, the
         # library's rule for a whole call): the larger steps go in a call of their own, which streams
         small = thr_all <= WALK_MAX_THRESHOLD_SPILL if engine.k > 7 else np.ones(len(pairs), dtype=bool)
@@ -108,7 +125,7 @@ def ladder_counts(engine, fastq, offsets, lengths, seed=0, min_bp=50000, max_bp=
             if sel.size == 0:
                 continue
             idx = [pairs[j][0] for j in sel]
-            seeds = np.array([seed + pairs[j][1] for j in sel], dtype=np.uint64)
+            seeds = np.array([sampled[j][3] for j in sel], dtype=np.uint64)
             h, _, st = engine.count_sampled(fastq, offsets[idx], lengths[idx], seeds, thr_all[sel], parts=parts)
             taken = st[:, 1].cpu().numpy()
             for jj, j in enumerate(sel):
@@ -118,3 +135,51 @@ def ladder_counts(engine, fastq, offsets, lengths, seed=0, min_bp=50000, max_bp=
         for rec in out:      # (steps in the ladder's order, largest first)
             rec["steps"].sort(key=lambda t: -t[0])
     return out
+
+
+# text bytes of the steps that one ladder_files call emits together (the files of a 2 GiB batch come to about twice that)
+EMIT_SLICE_BYTES = 1 << 30
+
+
+def ladder_files(engine, fastq, offsets, lengths, nsites, status, seed=0, min_bp=50000, max_bp=None, is_query=False,
+                 skip=(), slice_bytes=EMIT_SLICE_BYTES, failed=None):
+    """The reads of every ladder step of a batch of cleaned samples resident in HBM, as FASTQ text (the files the
+    reference's split_fastq writes, commands/image.py:629-725; vk_ladder_emit_device).  nsites, status: the samples'
+    read index (engine.read_index, or the records ladder_counts returned); the plan is ladder_counts' own --
+    ladder_plan and plan_steps -- so a step's text counts to the step's histogram.  skip: samples (indices) to leave out.
+    Yields (text uint8 tensor on the device, [(sample, bp, offset, length)]) per slice of steps whose expected text
+    fits slice_bytes (a step larger than that alone); a sample without steps (bad framing, too little data) gives none.
+    failed: a dict that receives {sample: status} for a sample whose framing the emit refuses although the read index
+    accepted it (the two checks are separate code); its steps are left out and the others' files are not affected.
+    Without the dict such a sample raises RuntimeError."""
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    _, plans = ladder_plan(nsites, status, min_bp, max_bp, is_query)
+    steps = [st for st in plan_steps(plans, nsites, seed) if st[0] not in skip]
+    if not steps:
+        return
+    used = sorted({st[0] for st in steps})
+    records = np.zeros(len(offsets), dtype=np.uint64)
+    records[used] = (engine.clean_lines(fastq, offsets[used], lengths[used]) + np.uint64(1)) // np.uint64(4)
+    at = 0
+    while at < len(steps):
+        end, expect = at, 0
+        while end < len(steps):
+            i, _, _, _, thr, whole = steps[end]
+            size = int(lengths[i]) if whole else int(lengths[i]) * thr // ALL_READS
+            if end > at and expect + size > slice_bytes:
+                break
+            expect += size
+            end += 1
+        part = steps[at:end]
+        idx = sorted({st[0] for st in part})
+        local = {i: j for j, i in enumerate(idx)}
+        text, offs, lens, st_h = engine.ladder_emit(fastq, offsets[idx], lengths[idx], [local[st[0]] for st in part],
+                                                    [st[3] for st in part], [st[4] for st in part], [st[5] for st in part],
+                                                    records=records[idx])
+        if st_h.any():   # (the read index passed these samples: the two disagree; such a sample got no text)
+            if failed is None:
+                raise RuntimeError("ladder_files: status %s for samples the read index accepted" % st_h.tolist())
+            failed.update({i: int(st_h[local[i]]) for i in idx if st_h[local[i]]})
+        yield text, [(st[0], st[2], int(o), int(n)) for st, o, n in zip(part, offs, lens) if st[0] not in (failed or ())]
+        at = end
