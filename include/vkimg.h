@@ -204,6 +204,24 @@ int vk_preprocess_device(vk_ctx* ctx, const uint8_t* d_img, uint32_t nimg, uint3
                          uint32_t out, const int32_t* bounds, const int32_t* coef, uint32_t kmax,
                          float mean, float stdv, float* d_out);
 
+/* The training-time counterpart of vk_preprocess_device: one launch turns `batch` indices into a resident image
+ * set d_img[nset][side*side] (device) into the model's input d_out[batch][3][out][out] (device, float32).
+ * Row i: BOX-resample image idx[i] as vk_preprocess_device does (out == side: the tables must be the identity
+ * and no intermediate is needed, so any side goes), /255, lighting where bshift[i] != 0 or cscale[i] != 1
+ * (x = sigmoid((logit(clamp(x, 1e-7, 1 - 1e-7)) + bshift[i]) * cscale[i])), (x - mean) / std = s_i; then
+ * mode 0: s_i;  mode 1 (MixUp): lam[i] * s_i + (1 - lam[i]) * s_partner[i];  mode 2 (CutMix): s_partner[i] for
+ * x1 <= x < x2 and y1 <= y < y2, else s_i -- s_partner[i] being the same steps for row partner[i] (a position in
+ * the batch) with that row's lighting.  A row with partner[i] == i, lam[i] == 1 (mode 1) or an empty rectangle
+ * (mode 2) is s_i itself.  idx, partner, lam, bshift, cscale: host arrays of length batch.  VK_EINVAL, with nothing
+ * launched, for idx[i] >= nset, partner[i] >= batch, lam[i] outside [0, 1], lighting parameters that are not finite,
+ * a rectangle that is not 0 <= x1 <= x2 <= out (y alike), a mode other than 0, 1, 2, and what vk_preprocess_device
+ * refuses.  The rule in full: INTEGRATION.md, "train". */
+int vk_train_batch_device(vk_ctx* ctx, const uint8_t* d_img, uint32_t nset, uint32_t side, uint32_t out,
+                          const int32_t* bounds, const int32_t* coef, uint32_t kmax, float mean, float stdv,
+                          uint32_t batch, const uint32_t* idx, const uint32_t* partner, const float* lam,
+                          const float* bshift, const float* cscale, uint32_t x1, uint32_t y1, uint32_t x2,
+                          uint32_t y2, int mode, float* d_out);
+
 /* Replaces: dsk opening and reading `-file <sample>.fq` (commands/image.py:771-796), for plain-text files: nfiles
  * host regions -- each a page-aligned, read-only MAP_SHARED mapping of a whole file -- are copied to
  * d_dst + dst_offsets[i] by DMA from the page-cache pages where they lie: no read() into a staging buffer (a copy

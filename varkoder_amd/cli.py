@@ -16,6 +16,9 @@ like process_stats does (commands/image.py:1144-1185).  With torchrun, ranks sha
 
 `python -m varkoder_amd query ...`: `varKoder query` (run_query); with `--from-raw` from raw reads, cleaned on the GPU
 like `image --from-raw`.
+
+`python -m varkoder_amd train ...`: `varKoder train` (train.run_train) with the reference's flags; it writes the model and
+label files `query` takes.
 """
 import argparse
 import math
@@ -150,6 +153,46 @@ def setup_parser():
     c.add_argument("output_mapping", choices=MAPPING_CHOICES, help="kmer mapping of output images.")
     c.add_argument("input", help="path to folder with png images files to be converted.")
     c.add_argument("outdir", help="path to the folder where results will be saved.")
+    t = sub.add_parser("train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                       help="Train a neural network on images (cli.py:168-323); batches are built on the GPU.")
+    t.add_argument("input", help="path to the folder with input images.")
+    t.add_argument("outdir", help="path to the folder where trained model will be stored.")
+    t.add_argument("-R", "--seed", type=int, help="random seed (split, weights, order and augmentation).")
+    t.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
+    t.add_argument("-v", "--verbose", action="store_true", default=False)
+    t.add_argument("-n", "--num-workers", type=int, default=0, help="accepted for parity and inert: there are no loader workers")
+    t.add_argument("-t", "--label-table-path", help="csv table `sample,labels`; by default labels come from the image metadata.")
+    t.add_argument("-S", "--single-label", action="store_true",
+                   help="single-label model; several labels of a sample are concatenated to one.")
+    t.add_argument("-d", "--threshold", type=float, default=0.7,
+                   help="threshold of the validation precision and recall. Ignored with --single-label")
+    t.add_argument("-V", "--validation-set", help="comma-separated sample IDs of the validation set, or a file with such a list.")
+    t.add_argument("-f", "--validation-set-fraction", type=float, default=0.2,
+                   help="fraction of samples held out per label combination. Ignored with --validation-set.")
+    t.add_argument("-c", "--architecture", default="hf-hub:brunoasm/vit_large_patch32_224.NCBI_SRA",
+                   help="arias2022, fiannaca2018, vit_l32 or pkg.module:factory (the reference's default and timm names "
+                        "are refused: timm is not assumed here)")
+    t.add_argument("-m", "--pretrained-model", help="model file (as `query -l` loads it) whose matching weights start the training.")
+    t.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size.")
+    t.add_argument("-B", "--min-batch-size", type=int, default=1, help="minimum batch size.")
+    t.add_argument("-C", "--cpu", action="store_true", default=False, help="refused: there is no CPU path")
+    t.add_argument("-r", "--base-learning-rate", type=float, default=5e-3, help="base learning rate.")
+    t.add_argument("-e", "--epochs", type=int, default=30, help="number of epochs to train.")
+    t.add_argument("-z", "--freeze-epochs", type=int, default=0, help="epochs that train the last linear layer only, first.")
+    t.add_argument("-w", "--random-weights", action="store_true",
+                   help="accepted for parity and inert: weights are random unless -m is given")
+    t.add_argument("-i", "--negative_downweighting", type=float, default=4,
+                   help="gamma(negative) of the asymmetric loss (arXiv:2009.14119). Ignored with --single-label.")
+    t.add_argument("-X", "--mix-augmentation", choices=["CutMix", "MixUp", "None"], default="MixUp")
+    t.add_argument("-s", "--label-smoothing", action="store_true", default=False,
+                   help="label smoothing 0.1. Only with --single-label and a mix augmentation.")
+    t.add_argument("-p", "--p-lighting", type=float, default=0.75, help="probability of a lighting transform; 0 for none.")
+    t.add_argument("-l", "--max-lighting", type=float, default=0.25, help="maximum scale of the lighting transform.")
+    t.add_argument("-g", "--no-logging", action="store_true", default=False, help="no per-epoch lines on stderr.")
+    t.add_argument("-M", "--no-metrics", action="store_true", default=False, help="skip validation loss and metrics.")
+    t.add_argument("--input-size", type=int, default=224,
+                   help="side of the input of vit_l32 and of a pkg.module:factory model (squish, BOX filter); arias2022 and "
+                        "fiannaca2018 take the images at their own size")
     return main
 
 
@@ -672,6 +715,9 @@ def main(argv=None):
         run_convert(args)
     elif args.command == "query":
         run_query(args)
+    elif args.command == "train":
+        from .train import run_train
+        run_train(args)
     eprint("DONE")
 
 

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +50,7 @@
 #include "vk_image.h"
 #include "vk_inflate.h"
 #include "vk_aux.h"
+#include "vk_train.h"
 #include "vk_clean.h"
 #include "vk_adapter.h"
 #include "vk_emit.h"
@@ -1588,6 +1590,67 @@ int vk_preprocess_device(vk_ctx* ctx, const uint8_t* d_img, uint32_t nimg, uint3
                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     hipLaunchKernelGGL(vk_preprocess_kernel, dim3(nimg), dim3(256), lds, ctx->stream, d_img, side, out, d_bounds,
                        d_coef, kmax, mean, stdv, d_out);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+int vk_train_batch_device(vk_ctx* ctx, const uint8_t* d_img, uint32_t nset, uint32_t side, uint32_t out,
+                          const int32_t* bounds, const int32_t* coef, uint32_t kmax, float mean, float stdv,
+                          uint32_t batch, const uint32_t* idx, const uint32_t* partner, const float* lam,
+                          const float* bshift, const float* cscale, uint32_t x1, uint32_t y1, uint32_t x2,
+                          uint32_t y2, int mode, float* d_out) {
+    if (!ctx || !d_img || !d_out || !bounds || !coef || side == 0 || out == 0 || kmax == 0 || stdv == 0.0f)
+        return VK_EINVAL;
+    if (!idx || !partner || !lam || !bshift || !cscale || nset == 0 || mode < 0 || mode > 2) return VK_EINVAL;
+    if (side > 32768u || out > 32768u) return VK_EINVAL;   // (pixel counts stay below 2^31)
+    const bool resize = out != side;
+    if (resize && static_cast<size_t>(side) * out + kTrainLutBytes > 160u * 1024u) return VK_EINVAL;  // LDS intermediate
+    for (uint32_t i = 0; i < out; ++i) {
+        const int32_t x0 = bounds[2 * i], n = bounds[2 * i + 1];
+        if (x0 < 0 || n < 0 || static_cast<uint32_t>(n) > kmax || static_cast<uint32_t>(x0 + n) > side) return VK_EINVAL;
+        // out == side: the kernel reads the source pixels themselves, so the tables must say exactly that
+        if (!resize && (static_cast<uint32_t>(x0) != i || n != 1 || coef[static_cast<size_t>(i) * kmax] != (1 << 22)))
+            return VK_EINVAL;
+    }
+    if (x1 > x2 || x2 > out || y1 > y2 || y2 > out) return VK_EINVAL;
+    for (uint32_t i = 0; i < batch; ++i) {
+        if (idx[i] >= nset || partner[i] >= batch) return VK_EINVAL;
+        if (!(lam[i] >= 0.0f && lam[i] <= 1.0f)) return VK_EINVAL;   // (refuses NaN too)
+        if (!std::isfinite(bshift[i]) || !std::isfinite(cscale[i])) return VK_EINVAL;
+    }
+    if (batch == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    // one host block, one copy: [bounds | coef | idx | partner | lam | bshift | cscale], all 4-byte words
+    const size_t nb = static_cast<size_t>(out) * 2, nc = static_cast<size_t>(out) * kmax;
+    std::vector<uint32_t> h(nb + nc + 5 * static_cast<size_t>(batch));
+    uint32_t* w = h.data();
+    memcpy(w, bounds, nb * 4);
+    memcpy(w += nb, coef, nc * 4);
+    memcpy(w += nc, idx, batch * 4u);
+    memcpy(w += batch, partner, batch * 4u);
+    memcpy(w += batch, lam, batch * 4u);
+    memcpy(w += batch, bshift, batch * 4u);
+    memcpy(w += batch, cscale, batch * 4u);
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_stage), &ctx->stage_cap, h.size() * 4 + 256);
+    if (rc) return rc;
+    VK_HIP(ctx, hipMemcpyAsync(ctx->d_stage, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host block goes away
+    const int32_t* d_bounds = reinterpret_cast<const int32_t*>(ctx->d_stage);
+    const int32_t* d_coef = d_bounds + nb;
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(d_coef + nc);
+    const uint32_t* d_partner = d_idx + batch;
+    const float* d_lam = reinterpret_cast<const float*>(d_partner + batch);
+    const float* d_bshift = d_lam + batch;
+    const float* d_cscale = d_bshift + batch;
+    const size_t lds = kTrainLutBytes + (resize ? (static_cast<size_t>(side) * out + 15) / 16 * 16 : 0);
+    // four pixels per thread where every uchar4 / float4 access is aligned
+    const bool wide = out % 4 == 0 && reinterpret_cast<uintptr_t>(d_out) % 16 == 0 &&
+                      (resize || reinterpret_cast<uintptr_t>(d_img) % 4 == 0);
+    auto kernel = wide ? vk_train_batch_kernel<4> : vk_train_batch_kernel<1>;
+    VK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(lds)));
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(256), lds, ctx->stream, d_img, side, out, d_bounds, d_coef, kmax, mean,
+                       stdv, d_idx, d_partner, d_lam, d_bshift, d_cscale, x1, y1, x2, y2, mode, d_out);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }
