@@ -343,6 +343,31 @@ int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offs
                           uint32_t nsteps, uint8_t* d_out, uint64_t out_capacity, uint64_t* out_offsets,
                           uint64_t* out_lengths, uint32_t* status, void* d_ws, uint64_t ws_bytes);
 
+/* The .fq.gz files of the intermediates: replaces `pigz` behind clean_reads (commands/image.py:529-540) and
+ * reformat.sh's own .fq.gz output in split_fastq (:696-708) for a batch of texts resident in HBM.  Text i is
+ * d_text[offsets[i] .. +lengths[i]) (offsets[i] a multiple of 16, any other returns VK_EINVAL before anything is launched;
+ * a length of 0 is a file).  Each becomes one BGZF file, the format BBTools writes through `bgzip`: gzip members of at
+ * most 65,280 bytes of text, each with the 6-byte `BC` extra field (BSIZE = the member's size - 1), CRC-32 and ISIZE,
+ * then bgzip's 28-byte empty member; an empty text is that member alone.  A member is one dynamic-Huffman DEFLATE block
+ * over LZ77 tokens (matches of 3..258 bytes at distances up to 32,768, none reaching before the member), over the
+ * literals alone when that is smaller, or a stored block when no code pays.  The same texts give the same bytes.
+ * Any gzip reader reads the files (vk_inflate_device inflates their members in parallel); they are NOT the
+ * single-member files pigz writes, and their bytes are not pinned between versions -- only the text they inflate to.
+ *
+ * vk_deflate_bound: *out_bound = the bytes d_out must hold: per file members * 31 + length + 28 rounded up to 16,
+ * members = ceil(length / 65280).  Host arithmetic.  vk_deflate_workspace_size: the bytes of d_work (a 65,536-byte
+ * slot per member, and tables).
+ * vk_deflate_device: every argument is checked before anything is launched: VK_EINVAL for a null pointer, nfiles 0, an
+ * unaligned offset or a workspace that is too small; VK_ENOSPC when out_capacity is below the bound (d_out untouched).
+ * File i is written to d_out[out_offsets[i] .. +out_lengths[i]) (host arrays out; offsets multiples of 16, the files in
+ * the order given, packed: the last one ends below the bound; the bytes up to a file's 16-byte rounded end are zeroed).
+ * The number of launches does not depend on the files or their sizes.  The call synchronises. */
+int vk_deflate_bound(const uint64_t* lengths, uint32_t nfiles, uint64_t* out_bound);
+int vk_deflate_workspace_size(const uint64_t* lengths, uint32_t nfiles, uint64_t* out_bytes);
+int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, uint32_t nfiles,
+                      uint8_t* d_out, uint64_t out_capacity, void* d_work, uint64_t work_bytes, uint64_t* out_offsets,
+                      uint64_t* out_lengths);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

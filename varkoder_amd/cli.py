@@ -92,6 +92,10 @@ def setup_parser():
                    help="with --from-raw / --from-clean and -i INT: also write every subsample's reads to "
                         "`INT/split_fastqs/<sample>@<bp>K.fq.gz`, the files the default entry takes (kept unless -x "
                         "when a sample's files are all there)")
+    p.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="compress the .fq.gz files that this run writes (`INT/clean_reads/` with --from-raw and -i INT, "
+                        "`INT/split_fastqs/` with --write-splits) on the GPU, as BGZF, and copy back the compressed bytes "
+                        "only; without it the host's gzip (level 1) compresses them")
     add_adapter_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
@@ -134,6 +138,9 @@ def setup_parser():
     q.add_argument("--from-raw", action="store_true",
                    help="input holds RAW reads, as the reference's `query` takes them: clean them on the GPU (step B, the "
                         "reference's fastp pass), subsample, image and predict without leaving the device")
+    q.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-raw and -i INT: compress the cleaned reads on the GPU, as BGZF, and copy back the "
+                        "compressed bytes only")
     add_adapter_flags(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
@@ -212,6 +219,11 @@ def parse_args(argv=None):
             parser.error("--write-splits: only with --from-raw or --from-clean")
         if not args.int_folder:
             parser.error("--write-splits: needs -i/--int-folder")
+    if args.command in ("image", "query") and getattr(args, "gpu_gzip", False):
+        # only where this run writes a .fq.gz: the cleaned reads of --from-raw -i INT, or --write-splits' files
+        if not ((args.from_raw and args.int_folder) or getattr(args, "write_splits", False)):
+            parser.error("--gpu-gzip: only with --from-raw and -i/--int-folder" +
+                         (", or with --write-splits" if args.command == "image" else ""))
     if args.command in ("image", "query"):
         given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
         if given and not args.from_raw:
@@ -481,7 +493,8 @@ class RawPlan:
         found = {}
         if self.raw:
             found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
-                                      verbose=args.verbose, **clean_options(args), **common))
+                                      verbose=args.verbose, gpu_gzip=getattr(args, "gpu_gzip", False),
+                                      **clean_options(args), **common))
         mine = [self.reused[i] for i in shard_by_size(clean_weights, rank, world)]
         if mine:
             found.update(clean_to_query([(s, self.clean_dir / (s + ".fq.gz")) for s in mine],
@@ -534,7 +547,7 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
         failpoint(rank)
         per_sample = clean_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
                                      min_bp=parse_size(args.min_bp), max_bp=max_bp, seeds=seeds, labels=labels,
-                                     base_sd=base_sd, **split_options(args),
+                                     base_sd=base_sd, **split_options(args), gpu_gzip=getattr(args, "gpu_gzip", False),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
                                      verbose=args.verbose)
         for s, v in per_sample.items():
@@ -560,7 +573,8 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
         failpoint(rank)
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
-                      io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args))
+                      io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
+                      gpu_gzip=getattr(args, "gpu_gzip", False))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, **cleaning, **common)
             per_sample.update(got)

@@ -54,6 +54,7 @@
 #include "vk_clean.h"
 #include "vk_adapter.h"
 #include "vk_emit.h"
+#include "vk_deflate.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -2280,6 +2281,106 @@ int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offs
     hipLaunchKernelGGL(vk_em_pad_kernel, dim3((nsteps + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.steps,
                        nsteps, L.sizes, d_out);
     VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------- .fq.gz files (BGZF) --
+
+namespace {
+
+// the pieces of a vk_deflate_device workspace
+struct DfLayout {
+    uint8_t* slots;
+    DfMember* mem;
+    DfFile* files;
+    uint64_t *sizes, *mprefix, *sums, *flens, *fsizes, *fprefix;
+    size_t total;
+    uint64_t nmem;
+};
+
+uint64_t df_members(uint64_t len) { return (len + kDfMemberText - 1) / kDfMemberText; }
+uint64_t df_file_bound(uint64_t len) { return (df_members(len) * 31 + len + kDfEofBytes + 15) / 16 * 16; }
+
+DfLayout df_layout(void* d_work, const uint64_t* lengths, uint32_t nfiles) {
+    DfLayout L{};
+    for (uint32_t i = 0; i < nfiles; ++i) L.nmem += df_members(lengths[i]);
+    const uint64_t nb = (std::max<uint64_t>(L.nmem, nfiles) + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_work), 0};
+    take(L.slots, L.nmem * kDfSlot);
+    take(L.mem, L.nmem);
+    take(L.files, nfiles);
+    take(L.sizes, L.nmem);
+    take(L.mprefix, L.nmem + 1);
+    take(L.sums, nb + 1);
+    take(L.flens, nfiles);
+    take(L.fsizes, nfiles);
+    take(L.fprefix, nfiles + 1ull);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_deflate_bound(const uint64_t* lengths, uint32_t nfiles, uint64_t* out_bound) {
+    if (!out_bound || (nfiles && !lengths)) return VK_EINVAL;
+    uint64_t b = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) b += df_file_bound(lengths[i]);
+    *out_bound = b;
+    return VK_OK;
+}
+
+int vk_deflate_workspace_size(const uint64_t* lengths, uint32_t nfiles, uint64_t* out_bytes) {
+    if (!out_bytes || (nfiles && !lengths)) return VK_EINVAL;
+    *out_bytes = df_layout(nullptr, lengths, nfiles).total;
+    return VK_OK;
+}
+
+int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, uint32_t nfiles,
+                      uint8_t* d_out, uint64_t out_capacity, void* d_work, uint64_t work_bytes, uint64_t* out_offsets,
+                      uint64_t* out_lengths) {
+    if (!ctx || nfiles == 0 || !d_text || !offsets || !lengths || !d_out || !d_work || !out_offsets || !out_lengths) return VK_EINVAL;
+    for (uint32_t i = 0; i < nfiles; ++i)
+        if (offsets[i] % 16) return VK_EINVAL;
+    const DfLayout L = df_layout(d_work, lengths, nfiles);
+    if (work_bytes < L.total || L.nmem + nfiles > 0x7FFFFFFFull) return VK_EINVAL;
+    uint64_t bound = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) bound += df_file_bound(lengths[i]);
+    if (out_capacity < bound) return VK_ENOSPC;
+    std::vector<DfMember> mem(L.nmem);
+    std::vector<DfFile> files(nfiles);
+    uint64_t m = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        files[i] = DfFile{m, df_members(lengths[i])};
+        for (uint64_t at = 0; at < lengths[i]; at += kDfMemberText)
+            mem[m++] = DfMember{offsets[i] + at, static_cast<uint32_t>(std::min<uint64_t>(kDfMemberText, lengths[i] - at)), i};
+    }
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipMemcpyAsync(L.files, files.data(), nfiles * sizeof(DfFile), hipMemcpyHostToDevice, ctx->stream));
+    if (L.nmem) {
+        VK_HIP(ctx, hipMemcpyAsync(L.mem, mem.data(), L.nmem * sizeof(DfMember), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(vk_df_member_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        static_cast<int>(sizeof(DfLds))));
+        hipLaunchKernelGGL(vk_df_member_kernel, dim3(static_cast<uint32_t>(L.nmem)), dim3(kDfThreads), sizeof(DfLds), ctx->stream,
+                           static_cast<const uint8_t*>(d_text), L.mem, L.slots, L.sizes);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    int rc = cl_scan(ctx, L.sizes, L.nmem, L.sums, L.mprefix);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_df_files_kernel, dim3((nfiles + kDfThreads - 1) / kDfThreads), dim3(kDfThreads), 0, ctx->stream, L.files,
+                       nfiles, L.mprefix, L.flens, L.fsizes);
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.fsizes, nfiles, L.sums, L.fprefix);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_df_gather_kernel, dim3(static_cast<uint32_t>(L.nmem + nfiles)), dim3(kDfThreads), 0, ctx->stream, L.mem,
+                       L.nmem, L.files, L.slots, L.mprefix, L.flens, L.fprefix, d_out);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(out_offsets, L.fprefix, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.flens, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
     return VK_OK;
 }

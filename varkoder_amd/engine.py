@@ -742,6 +742,35 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_ladder_emit_device")
         return out, out_offs, out_lens, status
 
+    def deflate_bound(self, lengths):
+        """Bytes that the files of texts of these lengths take at most (vk_deflate_bound)."""
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+        b = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_deflate_bound(_u64(lens), len(lens), C.byref(b)), "vk_deflate_bound")
+        return int(b.value)
+
+    def deflate(self, text, offs, lens):
+        """The texts text[offs[i] .. +lens[i]) (a uint8 device tensor; offsets multiples of 16) as one BGZF .fq.gz file
+        each, compressed where they lie (vk_deflate_device).  Returns (uint8 device tensor, file offsets uint64[n], file
+        lengths uint64[n]): the files lie packed in the order given, so [0, offsets[-1] + lengths[-1]) is all there is
+        to copy back.  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        if n == 0:
+            return torch.empty(0, dtype=torch.uint8, device=self.device), offs, lens
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_deflate_workspace_size(_u64(lens), n, C.byref(ws_bytes)), "vk_deflate_workspace_size")
+        cap = self.deflate_bound(lens)
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        out_offs = np.zeros(n, dtype=np.uint64)
+        out_lens = np.zeros(n, dtype=np.uint64)
+        _capi.check(self.ctx, self.L.vk_deflate_device(self.ctx, self._ptr(text), _u64(offs), _u64(lens), n, self._ptr(out), cap,
+                                                       self._ptr(ws), ws.numel(), _u64(out_offs), _u64(out_lens)),
+                    "vk_deflate_device")
+        return out, out_offs, out_lens
+
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""
         torch = _torch()

@@ -315,7 +315,8 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
-                    io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False):
+                    io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False,
+                    gpu_gzip=False):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
@@ -323,7 +324,8 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
 
     split_dir: also write every step's reads to `split_dir/<sample>@<bp>K.fq.gz` (SplitSink), as the reference's
     split_fastq leaves them; overwrite: also where a sample's files are all there.  no_image (with split_dir: the
-    reference's -X, :1055): stop after step C -- no counting, no PNG.
+    reference's -X, :1055): stop after step C -- no counting, no PNG.  gpu_gzip: the files are compressed on the GPU
+    (SplitSink).
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -336,7 +338,7 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
         batch_bytes = DEFAULT_GZ_BATCH_BYTES if mine and all(f.suffix == ".gz" for f in mine) else DEFAULT_BATCH_BYTES
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
-        splits = SplitSink(split_dir, pool, overwrite) if split_dir is not None else None
+        splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
         for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
@@ -384,12 +386,15 @@ class SplitSink:
     the pool like the cleaned reads of clean_dir.  A sample whose files are all there is left alone unless `overwrite`
     (:711-714); a file gets its name only once it is whole (written under a temporary name without the `@`, then renamed), so a run that
     was killed leaves nothing that the next one would take for done.  At most MAX_PENDING_BYTES of text wait for
-    their gzip, besides the slice being queued."""
+    their gzip, besides the slice being queued.
+
+    gpu_gzip: a slice's files are compressed where they lie in HBM (ImageEngine.deflate: BGZF), only the compressed
+    bytes are copied back, and the pool job writes them as they are; MAX_PENDING_BYTES then counts compressed bytes."""
 
     MAX_PENDING_BYTES = 1 << 30
 
-    def __init__(self, split_dir, pool, overwrite):
-        self.dir, self.pool, self.overwrite = Path(split_dir), pool, overwrite
+    def __init__(self, split_dir, pool, overwrite, gpu_gzip=False):
+        self.dir, self.pool, self.overwrite, self.gpu_gzip = Path(split_dir), pool, overwrite, gpu_gzip
         self.pending = []   # [(the futures of one slice, its bytes on the host)], oldest first
         self.dir.mkdir(parents=True, exist_ok=True)
 
@@ -401,11 +406,12 @@ class SplitSink:
         return not self.overwrite and all(self.path(sample, bp).is_file() for bp in sizes)
 
     @staticmethod
-    def _write(path, text):
+    def _write(path, text, compressed=False):
+        """text: the file's text, or with `compressed` the .gz file's own bytes"""
         import gzip
         part = path.with_name(".part." + path.name.replace(SAMPLE_BP_SEP, "+"))   # (no file of a sample to the default entry)
         with open(part, "wb") as fh:
-            fh.write(gzip.compress(text, compresslevel=1))
+            fh.write(text if compressed else gzip.compress(text, compresslevel=1))
         os.replace(part, path)
 
     def _drain(self, room):
@@ -432,10 +438,16 @@ class SplitSink:
             for dev, steps in ladder_files(eng, text, offs[idx], lens[idx], nsites, status, seed=seed, skip=skip,
                                            failed=failed, **ladder):
                 self._drain(self.MAX_PENDING_BYTES)
-                host = dev.cpu().numpy()
-                del dev
+                if self.gpu_gzip and steps:   # the slice's files compressed before they leave the device
+                    gz, go, gl = eng.deflate(dev, [o for _, _, o, _ in steps], [n for _, _, _, n in steps])
+                    host = gz[:int(go[-1] + gl[-1])].cpu().numpy()
+                    del dev, gz
+                    steps = [(local, bp, int(o), int(n)) for (local, bp, _, _), o, n in zip(steps, go, gl)]
+                else:
+                    host = dev.cpu().numpy()
+                    del dev
                 # (gzip reads a file's bytes where they lie in the slice: no second copy)
-                self.pending.append(([self.pool.submit(self._write, self.path(names[idx[local]], bp), host[o:o + n])
+                self.pending.append(([self.pool.submit(self._write, self.path(names[idx[local]], bp), host[o:o + n], self.gpu_gzip)
                                       for local, bp, o, n in steps], host.nbytes))
             for local, st in failed.items():
                 recs[idx[local]]["error"] = "inconsistent FASTQ framing (status %d writing the files)" % st
@@ -530,6 +542,7 @@ class Cleaning:
     detect_adapters: bool
     clean_dir: object
     max_bp: int
+    gpu_gzip: bool = False
 
 
 def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, verbose):
@@ -556,9 +569,10 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
     if clean_dir is not None:
         clean_dir.mkdir(parents=True, exist_ok=True)
 
-    def write_clean(sample, text, curves, cutting=None):
+    def write_clean(sample, text, curves, cutting=None, compressed=False):
+        """text: the cleaned reads, or with `compressed` the .fq.gz file's own bytes (opt.gpu_gzip)"""
         with open(clean_dir / (sample + ".fq.gz"), "wb") as fh:
-            fh.write(gzip.compress(text, compresslevel=1))
+            fh.write(text if compressed else gzip.compress(text, compresslevel=1))
         report = {"read1_after_filtering": {"content_curves": curves}}
         if cutting is not None:
             report["adapter_cutting"] = cutting
@@ -595,6 +609,14 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
                                                           adapters=table)
         ast = rest[0] if rest else None   # (adapter stats: with a table only)
         del dev
+        packed = {}
+        if clean_dir is not None and opt.gpu_gzip:   # the cleaned text compressed where it lies: only the files' bytes come back
+            good = [j for j in range(len(batch)) if not status[j] and j not in failed]
+            if good:
+                gz, go, gl = eng.deflate(out, ooffs[good], olens[good])
+                host = gz[:int(go[-1] + gl[-1])].cpu().numpy()
+                del gz
+                packed = {j: host[int(o):int(o + n)] for j, o, n in zip(good, go, gl)}
         tc = time.perf_counter()
         ok = []
         for j, (s, sf) in enumerate(batch):
@@ -609,14 +631,14 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
             st["clean_basepairs"] = int(row[0]) if (opt.adapter or opt.merge) else float("nan")
             st["cleaning_time"] = (tc - t0) / len(batch)
             if clean_dir is not None:
-                text = out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
+                text = packed[j] if opt.gpu_gzip else out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
                 cutting = None
                 if by_sequence:
                     name = [a.decode("latin-1") if a is not None else None for a in table[j]]
                     cutting = {"read1_adapter_sequence": name[0], "read2_adapter_sequence": name[1],
                                "single_adapter_sequence": name[2], "adapter_trimmed_reads": int(ast[j][0]),
                                "adapter_trimmed_bases": int(ast[j][1])}
-                writes.append(pool.submit(write_clean, s, text, curves, cutting))
+                writes.append(pool.submit(write_clean, s, text, curves, cutting, opt.gpu_gzip))
             ok.append(j)
         if verbose:
             eprint(f"batch of {len(batch)} samples, {nbytes} raw bytes: upload+clean {tc - t0:.3f}s")
@@ -627,7 +649,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
-                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False):
+                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -638,17 +660,18 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     sequence ("Step B"); an explicit sequence wins over detection for its groups, detection runs per
     batch (ImageEngine.detect_adapters) after the read budget.  The JSON then holds `adapter_cutting`.
 
-    split_dir, overwrite, no_image: as clean_to_images takes them.
+    split_dir, overwrite, no_image: as clean_to_images takes them.  gpu_gzip: the .fq.gz files of clean_dir and split_dir
+    are compressed on the GPU (ImageEngine.deflate: BGZF) and only their bytes are copied back.
 
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
     mine = _raw_plans(samples, weights, rank, world)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels)
-        splits = SplitSink(split_dir, pool, overwrite) if split_dir is not None else None
+        splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
         for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
                                                            batch_bytes or DEFAULT_BATCH_BYTES, verbose):
             _ladder_images(eng, out, ooffs, olens, names, names, tc, sink, stats, seeds or {}, splits=splits,
@@ -675,14 +698,14 @@ def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, 
 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
                  seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
-                 weights=None, clean_dir=None, adapters=None, detect_adapters=False):
+                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False):
     """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
     cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
-    the cleaned reads and their reports as raw_to_images writes them."""
+    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU)."""
     mine = _raw_plans(samples, weights, rank, world)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip)
     stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
