@@ -368,6 +368,24 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
                       uint8_t* d_out, uint64_t out_capacity, void* d_work, uint64_t work_bytes, uint64_t* out_offsets,
                       uint64_t* out_lengths);
 
+/* Replaces: dsk on a FASTA input, `dsk -kmer-size k -abundance-min 1 -file IN.fa` (commands/image.py:771-796; the real dsk
+ * reads FASTA as well as FASTQ), for a batch of samples resident in HBM, laid out as for vk_count_device (offsets multiples
+ * of 16, readable up to the last sample's 16-byte rounded end).  The rule is this project's ("--from-fasta";
+ * tests/fasta_ref.py): a line ends at '\n', a '\r' directly before it or as the sample's last byte belongs to the line end;
+ * a line whose first byte is '>' is a header line and starts a record, none of its bytes are sequence; the other lines,
+ * their ends removed, join into the record (empty lines vanish).  d_hist[nsamples][4^k] (u32, wrapping) = what
+ * vk_count_device gives for the FASTQ text with one read per record: windows of ACGTacgt run across line ends, never
+ * across records or any other byte.  d_status[nsamples]: VK_ST_BAD_START for a non-empty sample whose first byte is not
+ * '>' (its histogram is not used); an empty sample has status 0 and a zero histogram.  d_bases[nsamples] (u64, device) =
+ * the sequence bytes of the sample (joined bytes, every class).  A sample is cut by bytes, not records, so a record may be
+ * of any length.  VKIMG_FASTA_UNIT_BYTES (tests) shrinks the bytes a workgroup owns.  No synchronisation. */
+int vk_count_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                          uint32_t nsamples, int k, uint32_t* d_hist, uint32_t* d_status, uint64_t* d_bases);
+
+/* One host sample: H2D copy, vk_count_fasta_device, D2H copies, sync.  VK_EFORMAT when the status word is non-zero. */
+int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k, uint32_t* hist, uint32_t* status,
+                        uint64_t* bases);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

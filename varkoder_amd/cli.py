@@ -88,6 +88,10 @@ def setup_parser():
     entry.add_argument("--from-raw", action="store_true",
                        help="input holds RAW reads (`<taxon>/<sample>/*.fq[.gz]` or a CSV labels,sample,files): clean them "
                             "on the GPU (step B, the reference's fastp pass) and go on with the ladder")
+    entry.add_argument("--from-fasta", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                       help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`: assemblies, contigs, "
+                            "organelle genomes): each is counted whole on the GPU and becomes one image "
+                            "`<sample>@<bp>K+<mapping>+k<k>.png`, bp = its bases (rule: INTEGRATION.md, \"--from-fasta\")")
     p.add_argument("--write-splits", action="store_true", default=argparse.SUPPRESS,   # (absent = off, as the adapter flags)
                    help="with --from-raw / --from-clean and -i INT: also write every subsample's reads to "
                         "`INT/split_fastqs/<sample>@<bp>K.fq.gz`, the files the default entry takes (kept unless -x "
@@ -138,6 +142,9 @@ def setup_parser():
     q.add_argument("--from-raw", action="store_true",
                    help="input holds RAW reads, as the reference's `query` takes them: clean them on the GPU (step B, the "
                         "reference's fastp pass), subsample, image and predict without leaving the device")
+    q.add_argument("--from-fasta", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`), one sample each: counted whole "
+                        "on the GPU, imaged and predicted")
     q.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-raw and -i INT: compress the cleaned reads on the GPU, as BGZF, and copy back the "
                         "compressed bytes only")
@@ -214,6 +221,12 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
+    if getattr(args, "from_fasta", False):   # one image per file, nothing written but images: no ladder, no intermediates
+        if args.command == "query" and (args.images or args.from_raw):
+            parser.error("--from-fasta: not with -I/--images or --from-raw")
+        for name, flag in (("write_splits", "--write-splits"), ("gpu_gzip", "--gpu-gzip")):
+            if getattr(args, name, False):
+                parser.error(f"--from-fasta: not with {flag}")
     if args.command == "image" and getattr(args, "write_splits", False):
         if not (args.from_raw or args.from_clean):
             parser.error("--write-splits: only with --from-raw or --from-clean")
@@ -303,7 +316,11 @@ def run_query(args):
     if not args.overwrite and (outdir / "predictions.csv").exists():
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
     from_raw = getattr(args, "from_raw", False)
-    if args.images:
+    from_fasta = getattr(args, "from_fasta", False)
+    if from_fasta:
+        from .fasta import fasta_files, fasta_to_query, sample_of
+        inputs = fasta_files(args.input)
+    elif args.images:
         inputs = sorted(Path(args.input).rglob("*.png"))
     elif from_raw:
         inputs = RawPlan(args, is_query=True)   # (no collective in it, nothing on the GPU: an input error leaves every rank here)
@@ -382,6 +399,14 @@ def run_query(args):
             if arrays:
                 eng = state["eng"] = ImageEngine(k=records[0]["k"], mapping="cgr", device=device)
                 images = torch.from_numpy(np.stack(arrays)).to(eng.device)
+        elif from_fasta:
+            # a sample per FASTA file, imaged whole: rows as for cleaned reads (no labels, no base-frequency sd)
+            if mine:
+                eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
+                wanted = [(i, sample_of(inputs[i])) for i in mine]
+                found = fasta_to_query([(s, inputs[i]) for i, s in wanted], engine=eng, k=args.kmer_size,
+                                       mapping_code=args.kmer_mapping, io_threads=io_threads_per_rank(args.n_threads))
+                images = found_images(found, wanted, {})
         else:
             # cleaned reads, a sample per file: no labels and no base-frequency sd, as images written with neither read back
             max_bp = max_bp_of(args)
@@ -557,6 +582,30 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
     finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, base_sd)
 
 
+def run_image_from_fasta(args, outdir, rank, world, local_rank):
+    """`image --from-fasta`: every FASTA file of the input folder is one sample, counted whole and imaged (fasta.py)."""
+    from .fasta import fasta_files, fasta_to_images, sample_of
+    from .shard import agreed_weights, io_threads_per_rank
+    files = fasta_files(args.input)
+    if not files:
+        raise Exception("No files found in input. Please check.")
+    samples = [sample_of(f) for f in files]
+    labels = read_labels(args.labels_csv)
+    eprint("Counting kmers and creating images for", len(files), "FASTA samples")
+    per_sample, error = OrderedDict(), None
+    weights = agreed_weights(files)   # (a collective: before the try block, while every rank is still here)
+    try:   # (a rank whose share fails still reaches the gather below: see finish_image_job)
+        failpoint(rank)
+        per_sample = fasta_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
+                                     labels=labels, device=local_rank, rank=rank, world=world,
+                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
+        for v in per_sample.values():
+            v["base_frequencies_sd"] = 0   # (no cleaning report: the flag is False, as for any sample without one)
+    except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
+        error = e
+    finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, {})
+
+
 def run_image_from_raw(args, outdir, rank, world, local_rank):
     """`image --from-raw`: steps B-E per sample (run_clean2img, commands/image.py:938-1127) with step B on the GPU."""
     from .image import base_sd_table
@@ -672,6 +721,8 @@ def run_image(args):
         return run_image_from_clean(args, outdir, rank, world, local_rank)
     if args.from_raw:
         return run_image_from_raw(args, outdir, rank, world, local_rank)
+    if getattr(args, "from_fasta", False):
+        return run_image_from_fasta(args, outdir, rank, world, local_rank)
     src = Path(args.input)
     if (src / "split_fastqs").is_dir():
         src = src / "split_fastqs"

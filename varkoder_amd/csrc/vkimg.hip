@@ -26,6 +26,7 @@
 //     (vk_bucket_kernel<K, 3>, vk_quad_count_kernel, vk_quad_merge_kernel); subsampled launches: pairs of
 //     windows through wave-private queues into 16 streams (vk_bucket_kernel<K, 1>, vk_bucket_count_kernel).
 //   vk_remap_kernel / vk_preprocess_kernel: `convert`'s remap and the input side of `query`.
+//   vk_fa_*_kernel (vk_fasta.h): the count straight from FASTA text (`--from-fasta`): cut by bytes, header state by a scan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +56,7 @@
 #include "vk_adapter.h"
 #include "vk_emit.h"
 #include "vk_deflate.h"
+#include "vk_fasta.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -138,6 +140,9 @@ struct vk_ctx {
     size_t cldetect_cap = 0;
     uint32_t clean_hash_bits = 64; // VKIMG_CLEAN_HASH_BITS=n: vk_clean_device's dedup keeps n bits of its 64-bit hash (tests: collisions on purpose)
     bool no_read_index = false;    // VKIMG_NO_READ_INDEX=1: subsampled counts always stream the text, whatever index the context holds (tests, A/B timing)
+    uint8_t* d_fasta = nullptr;    // vk_count_fasta_device: descriptors | unit summaries | the state that enters every unit
+    size_t fasta_cap = 0;
+    uint32_t fasta_unit_bytes = 0; // VKIMG_FASTA_UNIT_BYTES=n: bytes of a unit of the FASTA count, a multiple of 64 up to 16384, one unit per workgroup (tests: many seams in little text; 0 = 16384, 32 units per workgroup)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -641,6 +646,12 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     env_uint("VKIMG_CLEAN_HASH_BITS", &hash_bits);
     ctx->clean_hash_bits = hash_bits >= 1 && hash_bits <= 64 ? static_cast<uint32_t>(hash_bits) : 64u;
     ctx->k1_classic = env_flag("VKIMG_K1_CLASSIC");
+    env_uint("VKIMG_FASTA_UNIT_BYTES", &ctx->fasta_unit_bytes);
+    if (ctx->fasta_unit_bytes) {
+        ctx->fasta_unit_bytes = ctx->fasta_unit_bytes / kFaLaneBytes * kFaLaneBytes;
+        if (ctx->fasta_unit_bytes < kFaLaneBytes) ctx->fasta_unit_bytes = kFaLaneBytes;
+        if (ctx->fasta_unit_bytes > kFaUnitBytes) ctx->fasta_unit_bytes = kFaUnitBytes;
+    }
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return VK_EHIP; }
     {
@@ -663,7 +674,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -2383,6 +2394,95 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
     VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.flens, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
     return VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- FASTA count (vk_fasta.h) ------
+
+extern "C" {
+
+int vk_count_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                          int k, uint32_t* d_hist, uint32_t* d_status, uint64_t* d_bases) {
+    if (!ctx || !offsets || !lengths || !d_hist || !d_status || !d_bases || k < 5 || k > 9) return VK_EINVAL;
+    if (nsamples == 0) return VK_OK;
+    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t unit = ctx->fasta_unit_bytes ? ctx->fasta_unit_bytes : kFaUnitBytes;
+    const uint32_t span = ctx->fasta_unit_bytes ? 1u : kFaSpanUnits;
+    // offsets | lengths | first workgroup | first unit of every sample
+    std::vector<uint64_t> meta(4ull * nsamples + 2);
+    uint64_t* wg_first = meta.data() + 2ull * nsamples;
+    uint64_t* unit_first = wg_first + nsamples + 1;
+    wg_first[0] = unit_first[0] = 0;
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+        const uint64_t units = (lengths[i] + unit - 1) / unit;
+        if (units >= (1ull << 30)) return VK_EINVAL;   // (a unit's number takes 31 bits of the scan's key)
+        meta[i] = offsets[i];
+        meta[nsamples + i] = lengths[i];
+        wg_first[i + 1] = wg_first[i] + (units + span - 1) / span;
+        unit_first[i + 1] = unit_first[i] + units;
+    }
+    const uint64_t nwg = wg_first[nsamples], nunits = unit_first[nsamples];
+    if (nwg >= (1ull << 31)) return VK_EINVAL;
+    uint64_t* d_meta = nullptr;
+    uint32_t *d_ukey = nullptr, *d_carry = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
+        take(d_meta, meta.size());
+        take(d_ukey, nunits + 1);
+        take(d_carry, nunits + 1);
+    });
+    if (rc) return rc;
+    // (pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nsamples * ncode * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_bases, 0, nsamples * sizeof(uint64_t), ctx->stream));
+    const FaMeta m{d_meta, d_meta + nsamples, d_meta + 2ull * nsamples, d_meta + 3ull * nsamples + 1, nsamples, unit, span};
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    if (nwg) {
+        hipLaunchKernelGGL(vk_fa_summary_kernel, dim3(static_cast<uint32_t>(nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(vk_fa_scan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey, d_carry, d_status);
+    VK_HIP(ctx, hipGetLastError());
+    if (nwg) {
+        rc = with_k(k, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            hipLaunchKernelGGL(vk_fa_count_kernel<K>, dim3(static_cast<uint32_t>(nwg)), dim3(kFaThreads), 0, ctx->stream, text, m,
+                               d_carry, d_hist, reinterpret_cast<unsigned long long*>(d_bases));
+            VK_HIP(ctx, hipGetLastError());
+            return VK_OK;
+        });
+        if (rc) return rc;
+    }
+    return VK_OK;
+}
+
+int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k, uint32_t* hist, uint32_t* status, uint64_t* bases) {
+    if (!ctx || !hist || k < 5 || k > 9 || (nbytes && !fasta)) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_stage), &ctx->stage_cap, nbytes + 64);
+    if (rc) return rc;
+    if (!ctx->d_hist1) VK_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_hist1), (1u << 18) * sizeof(uint32_t)));
+    rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_status1), &ctx->status1_cap, 64);   // status word, then the bases at byte 8
+    if (rc) return rc;
+    if (nbytes) VK_HIP(ctx, hipMemcpyAsync(ctx->d_stage, fasta, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    uint64_t off = 0, len = nbytes;
+    uint64_t* d_bases = reinterpret_cast<uint64_t*>(ctx->d_status1 + 2);
+    rc = vk_count_fasta_device(ctx, ctx->d_stage, &off, &len, 1, k, ctx->d_hist1, ctx->d_status1, d_bases);
+    if (rc) return rc;
+    uint32_t st = 0;
+    uint64_t nb = 0;
+    VK_HIP(ctx, hipMemcpyAsync(hist, ctx->d_hist1, ncode * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(&st, ctx->d_status1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(&nb, d_bases, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (status) *status = st;
+    if (bases) *bases = nb;
+    return st ? VK_EFORMAT : VK_OK;
 }
 
 }  // extern "C"

@@ -544,6 +544,23 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_device")
         return hist, status
 
+    def count_fasta(self, fasta, offsets, lengths, hist=None, status=None, bases=None):
+        """FASTA text in HBM (laid out as for count) -> (hist [n, 4^k], status [n], bases int64 [n] = each sample's
+        sequence bytes), all on the device (vk_count_fasta_device)."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        if hist is None:
+            hist = torch.empty((n, self.ncode), dtype=torch.int32, device=self.device)
+        if status is None:
+            status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if bases is None:
+            bases = torch.empty((n,), dtype=torch.int64, device=self.device)
+        st = self.L.vk_count_fasta_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, self.k, self._ptr(hist),
+                                          self._ptr(status), self._ptr(bases))
+        _capi.check(self.ctx, st, "vk_count_fasta_device")
+        return hist, status, bases
+
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):
         """K1 over a pseudo-random subset of each sample's reads (vk_count_sampled_device):
@@ -846,6 +863,18 @@ class ImageEngine:
         if st not in (_capi.VK_OK, _capi.VK_EFORMAT):
             _capi.check(self.ctx, st, "vk_count_host")
         return hist, stw.value
+
+    def count_fasta_host(self, data):
+        """One host FASTA byte string -> (hist uint32[4^k], status bits, sequence bytes)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
+        hist = np.empty(self.ncode, dtype=np.uint32)
+        stw = C.c_uint32(0)
+        nb = C.c_uint64(0)
+        st = self.L.vk_count_fasta_host(self.ctx, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, self.k, _u32(hist),
+                                        C.byref(stw), C.byref(nb))
+        if st not in (_capi.VK_OK, _capi.VK_EFORMAT):
+            _capi.check(self.ctx, st, "vk_count_fasta_host")
+        return hist, stw.value, nb.value
 
     def image_host(self, hist):
         hist = np.ascontiguousarray(hist, dtype=np.uint32)

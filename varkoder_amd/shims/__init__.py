@@ -6,7 +6,7 @@
 
 Put `varkoder_amd/shims/bin` first on PATH (`export PATH=$(python -m varkoder_amd.shims):$PATH`)
 and the UNMODIFIED reference runs steps D and E of `varKoder image` on the GPU: `dsk` counts with
-the HIP library (no CPU fallback; a FASTQ with broken framing exits non-zero, which the reference's
+the HIP library (FASTQ, or FASTA when the text begins with '>'; no CPU fallback; a FASTQ with broken framing exits non-zero, which the reference's
 `check=True` turns into `K-MER COUNTING FAIL`), `dsk2ascii` prints the `KMER count` lines the
 reference parses.  OUT holds this package's counts container (image.write_counts), not HDF5.
 """
@@ -70,7 +70,9 @@ def dsk_main(argv=None):
             print(f"dsk (varkoder_amd shim): {opts['-file']} is not a readable FASTQ / gzip file "
                   f"(status {int(eng.last_upload_status[0])})", file=sys.stderr)
             return 1
-        h, st = eng.count(dev, offs, lens)
+        # the real dsk reads FASTA as well: a text that begins with '>' (after the inflate) is counted by the FASTA rule
+        fasta = int(lens[0]) > 0 and int(dev[int(offs[0])].cpu()) == ord(">")
+        h, st = eng.count_fasta(dev, offs, lens)[:2] if fasta else eng.count(dev, offs, lens)
         hist, stw = h.cpu().numpy().view(np.uint32)[0].copy(), int(st.cpu()[0])
         if stw:
             print(f"dsk (varkoder_amd shim): inconsistent FASTQ framing in {opts['-file']} "
