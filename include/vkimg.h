@@ -382,6 +382,26 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
 int vk_count_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
                           uint32_t nsamples, int k, uint32_t* d_hist, uint32_t* d_status, uint64_t* d_bases);
 
+/* Replaces: split_fastq + dsk on its files (commands/image.py:629-725, 771-796) for an ASSEMBLY -- the subsample ladder of
+ * `image --from-fasta --fragments`: (sample, step) pairs of a batch of FASTA samples (laid out as for
+ * vk_count_fasta_device), every pair counted over the fragments its step takes.  The rule is this project's
+ * ("--from-fasta --fragments"; tests/fasta_ladder_ref.py): the joined bytes of a sample's records, in
+ * order, have ordinals 0 .. bases - 1; the fragment of ordinal q is (q + shifts[i]) div frag_len; fragment f is taken iff
+ * sample_hash(seeds[i], f) < thresholds[i] (thresholds in [0, 2^32]; 2^32 takes every fragment).  A window of k bytes
+ * counts for pair i iff it counts in vk_count_fasta_device, its first and last byte lie in one fragment, and that one is
+ * taken -- so even at 2^32 the windows across a fragment seam are dropped.  pair_sample[npairs] (host): the sample of each
+ * pair, in any order, a sample any number of times.  d_hist[npairs][4^k] (u32); d_taken[npairs] (u64, device) = the
+ * ordinals whose fragment is taken; d_status[nsamples], d_bases[nsamples] as vk_count_fasta_device's (a sample with
+ * VK_ST_BAD_START: zero histograms, zero bases, nothing taken).  The call builds an index of the text (a u32 per 64
+ * bytes, a u64 per unit) in the context's workspace; a lane none of whose fragments is taken reads its index word and
+ * not its text.  VK_EINVAL, before anything is launched, for frag_len < k, frag_len >= 2^31, pair_sample[i] >= nsamples,
+ * a threshold above 2^32 or a shift of 2^63 or more.  VKIMG_FASTA_UNIT_BYTES shrinks the units here as well.  No
+ * synchronisation. */
+int vk_count_fasta_sampled_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                                  uint32_t nsamples, int k, uint32_t frag_len, uint32_t npairs, const uint32_t* pair_sample,
+                                  const uint64_t* seeds, const uint64_t* thresholds, const uint64_t* shifts, uint32_t* d_hist,
+                                  uint32_t* d_status, uint64_t* d_bases, uint64_t* d_taken);
+
 /* One host sample: H2D copy, vk_count_fasta_device, D2H copies, sync.  VK_EFORMAT when the status word is non-zero. */
 int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k, uint32_t* hist, uint32_t* status,
                         uint64_t* bases);

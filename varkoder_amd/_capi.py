@@ -25,7 +25,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_clean_lines_device", "vk_clean_workspace_size", "vk_clean_device", "vk_clean_detect_workspace_size",
            "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device", "vk_ladder_emit_workspace_size",
            "vk_ladder_emit_device", "vk_train_batch_device", "vk_deflate_bound", "vk_deflate_workspace_size", "vk_deflate_device",
-           "vk_count_fasta_device", "vk_count_fasta_host")
+           "vk_count_fasta_device", "vk_count_fasta_host", "vk_count_fasta_sampled_device")
 
 _lib = None
 
@@ -91,6 +91,8 @@ def lib():
     L.vk_deflate_workspace_size.argtypes = [u64p, C.c_uint32, u64p]
     L.vk_deflate_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
     L.vk_count_fasta_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, vp, vp, vp]
+    L.vk_count_fasta_sampled_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u32p, u64p, u64p, u64p,
+                                                vp, vp, vp, vp]
     L.vk_count_fasta_host.argtypes = [vp, vp, C.c_size_t, C.c_int, u32p, u32p, u64p]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]

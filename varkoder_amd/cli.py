@@ -92,6 +92,12 @@ def setup_parser():
                        help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`: assemblies, contigs, "
                             "organelle genomes): each is counted whole on the GPU and becomes one image "
                             "`<sample>@<bp>K+<mapping>+k<k>.png`, bp = its bases (rule: INTEGRATION.md, \"--from-fasta\")")
+    p.add_argument("--fragments", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-fasta: image every sample as the 1-2-5 ladder of subsamples between --min-bp and "
+                        "--max-bp, like --from-clean does for reads, each step drawn from fragments of --fragment-length "
+                        "bases of the assembly (rule: INTEGRATION.md, \"--from-fasta --fragments\")")
+    p.add_argument("--fragment-length", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --from-fasta --fragments: bases of a fragment, 16 to 1000000 (150 when absent)")
     p.add_argument("--write-splits", action="store_true", default=argparse.SUPPRESS,   # (absent = off, as the adapter flags)
                    help="with --from-raw / --from-clean and -i INT: also write every subsample's reads to "
                         "`INT/split_fastqs/<sample>@<bp>K.fq.gz`, the files the default entry takes (kept unless -x "
@@ -214,6 +220,9 @@ ADAPTER_FLAGS = (("detect_adapters", "--detect-adapters"), ("adapter_sequence", 
                  ("adapter_sequence_r2", "--adapter-sequence-r2"))
 
 
+FRAGMENT_LENGTH_DEFAULT, FRAGMENT_LENGTH_MIN, FRAGMENT_LENGTH_MAX = 150, 16, 1000000
+
+
 def parse_args(argv=None):
     """The parsed command line; the adapter flags of `image` and `query` are refused (exit 2) without --from-raw or
     with -a, and their sequences are checked."""
@@ -227,6 +236,12 @@ def parse_args(argv=None):
         for name, flag in (("write_splits", "--write-splits"), ("gpu_gzip", "--gpu-gzip")):
             if getattr(args, name, False):
                 parser.error(f"--from-fasta: not with {flag}")
+    if args.command == "image":
+        for name, flag in (("fragments", "--fragments"), ("fragment_length", "--fragment-length")):
+            if hasattr(args, name) and not getattr(args, "from_fasta", False):
+                parser.error(f"{flag}: only with --from-fasta")
+        if hasattr(args, "fragment_length") and not FRAGMENT_LENGTH_MIN <= args.fragment_length <= FRAGMENT_LENGTH_MAX:
+            parser.error(f"--fragment-length: {FRAGMENT_LENGTH_MIN} to {FRAGMENT_LENGTH_MAX}")
     if args.command == "image" and getattr(args, "write_splits", False):
         if not (args.from_raw or args.from_clean):
             parser.error("--write-splits: only with --from-raw or --from-clean")
@@ -592,13 +607,17 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
     samples = [sample_of(f) for f in files]
     labels = read_labels(args.labels_csv)
     eprint("Counting kmers and creating images for", len(files), "FASTA samples")
+    ladder = {}
+    if getattr(args, "fragments", False):   # -m, -M and -R as for --from-clean
+        ladder = dict(fragments=True, fragment_length=getattr(args, "fragment_length", FRAGMENT_LENGTH_DEFAULT),
+                      min_bp=parse_size(args.min_bp), max_bp=max_bp_of(args), seeds=draw_seeds(samples, args.seed))
     per_sample, error = OrderedDict(), None
     weights = agreed_weights(files)   # (a collective: before the try block, while every rank is still here)
     try:   # (a rank whose share fails still reaches the gather below: see finish_image_job)
         failpoint(rank)
         per_sample = fasta_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
                                      labels=labels, device=local_rank, rank=rank, world=world,
-                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
+                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **ladder)
         for v in per_sample.values():
             v["base_frequencies_sd"] = 0   # (no cleaning report: the flag is False, as for any sample without one)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives

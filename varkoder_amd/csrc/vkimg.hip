@@ -57,6 +57,7 @@
 #include "vk_emit.h"
 #include "vk_deflate.h"
 #include "vk_fasta.h"
+#include "vk_fasta_ladder.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -2398,7 +2399,55 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- FASTA count (vk_fasta.h) ------
+// ---------------------------------------------------------------- FASTA count (vk_fasta.h, vk_fasta_ladder.h) ------
+
+namespace {
+
+// How a batch of FASTA samples is cut: meta = offsets | lengths | first workgroup | first unit of every sample.
+struct FaPlan {
+    std::vector<uint64_t> meta;
+    uint32_t nsamples = 0, unit = 0, span = 0;
+    uint64_t nwg = 0, nunits = 0;
+    const uint64_t* wg_first() const { return meta.data() + 2ull * nsamples; }
+    FaMeta on_device(const uint64_t* d_meta) const {
+        return FaMeta{d_meta, d_meta + nsamples, d_meta + 2ull * nsamples, d_meta + 3ull * nsamples + 1, nsamples, unit, span};
+    }
+};
+
+int fa_plan(const vk_ctx* ctx, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples, FaPlan* pl) {
+    pl->nsamples = nsamples;
+    pl->unit = ctx->fasta_unit_bytes ? ctx->fasta_unit_bytes : kFaUnitBytes;
+    pl->span = ctx->fasta_unit_bytes ? 1u : kFaSpanUnits;
+    pl->meta.assign(4ull * nsamples + 2, 0);
+    uint64_t* wg_first = pl->meta.data() + 2ull * nsamples;
+    uint64_t* unit_first = wg_first + nsamples + 1;
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+        const uint64_t units = (lengths[i] + pl->unit - 1) / pl->unit;
+        if (units >= (1ull << 30)) return VK_EINVAL;   // (a unit's number takes 31 bits of the scan's key)
+        pl->meta[i] = offsets[i];
+        pl->meta[nsamples + i] = lengths[i];
+        wg_first[i + 1] = wg_first[i] + (units + pl->span - 1) / pl->span;
+        unit_first[i + 1] = unit_first[i] + units;
+    }
+    pl->nwg = wg_first[nsamples];
+    pl->nunits = unit_first[nsamples];
+    return pl->nwg >= (1ull << 31) ? VK_EINVAL : VK_OK;
+}
+
+// The header state that enters every unit (d_carry) and the samples' status words.
+int fa_header_state(vk_ctx* ctx, const uint8_t* text, const FaPlan& pl, const FaMeta& m, uint32_t* d_ukey, uint32_t* d_carry,
+                    uint32_t* d_status) {
+    if (pl.nwg) {
+        hipLaunchKernelGGL(vk_fa_summary_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(vk_fa_scan_kernel, dim3(pl.nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey, d_carry, d_status);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2408,50 +2457,107 @@ int vk_count_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offs
     if (nsamples == 0) return VK_OK;
     if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
     VK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t unit = ctx->fasta_unit_bytes ? ctx->fasta_unit_bytes : kFaUnitBytes;
-    const uint32_t span = ctx->fasta_unit_bytes ? 1u : kFaSpanUnits;
-    // offsets | lengths | first workgroup | first unit of every sample
-    std::vector<uint64_t> meta(4ull * nsamples + 2);
-    uint64_t* wg_first = meta.data() + 2ull * nsamples;
-    uint64_t* unit_first = wg_first + nsamples + 1;
-    wg_first[0] = unit_first[0] = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
-        const uint64_t units = (lengths[i] + unit - 1) / unit;
-        if (units >= (1ull << 30)) return VK_EINVAL;   // (a unit's number takes 31 bits of the scan's key)
-        meta[i] = offsets[i];
-        meta[nsamples + i] = lengths[i];
-        wg_first[i + 1] = wg_first[i] + (units + span - 1) / span;
-        unit_first[i + 1] = unit_first[i] + units;
-    }
-    const uint64_t nwg = wg_first[nsamples], nunits = unit_first[nsamples];
-    if (nwg >= (1ull << 31)) return VK_EINVAL;
+    FaPlan pl;
+    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    if (rc) return rc;
     uint64_t* d_meta = nullptr;
     uint32_t *d_ukey = nullptr, *d_carry = nullptr;
-    int rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
-        take(d_meta, meta.size());
-        take(d_ukey, nunits + 1);
-        take(d_carry, nunits + 1);
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
+        take(d_meta, pl.meta.size());
+        take(d_ukey, pl.nunits + 1);
+        take(d_carry, pl.nunits + 1);
     });
     if (rc) return rc;
     // (pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     const size_t ncode = static_cast<size_t>(1) << (2 * k);
     VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nsamples * ncode * sizeof(uint32_t), ctx->stream));
     VK_HIP(ctx, hipMemsetAsync(d_bases, 0, nsamples * sizeof(uint64_t), ctx->stream));
-    const FaMeta m{d_meta, d_meta + nsamples, d_meta + 2ull * nsamples, d_meta + 3ull * nsamples + 1, nsamples, unit, span};
+    const FaMeta m = pl.on_device(d_meta);
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
-    if (nwg) {
-        hipLaunchKernelGGL(vk_fa_summary_kernel, dim3(static_cast<uint32_t>(nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey);
-        VK_HIP(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(vk_fa_scan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey, d_carry, d_status);
-    VK_HIP(ctx, hipGetLastError());
-    if (nwg) {
+    rc = fa_header_state(ctx, text, pl, m, d_ukey, d_carry, d_status);
+    if (rc) return rc;
+    if (pl.nwg) {
         rc = with_k(k, [&](auto kc) {
             constexpr int K = decltype(kc)::value;
-            hipLaunchKernelGGL(vk_fa_count_kernel<K>, dim3(static_cast<uint32_t>(nwg)), dim3(kFaThreads), 0, ctx->stream, text, m,
+            hipLaunchKernelGGL(vk_fa_count_kernel<K>, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m,
                                d_carry, d_hist, reinterpret_cast<unsigned long long*>(d_bases));
+            VK_HIP(ctx, hipGetLastError());
+            return VK_OK;
+        });
+        if (rc) return rc;
+    }
+    return VK_OK;
+}
+
+int vk_count_fasta_sampled_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                                  uint32_t nsamples, int k, uint32_t frag_len, uint32_t npairs, const uint32_t* pair_sample,
+                                  const uint64_t* seeds, const uint64_t* thresholds, const uint64_t* shifts, uint32_t* d_hist,
+                                  uint32_t* d_status, uint64_t* d_bases, uint64_t* d_taken) {
+    if (!ctx || !offsets || !lengths || !d_status || !d_bases || k < 5 || k > 9) return VK_EINVAL;
+    if (frag_len < static_cast<uint32_t>(k) || frag_len >= (1u << 31)) return VK_EINVAL;
+    if (npairs && (!pair_sample || !seeds || !thresholds || !shifts || !d_hist || !d_taken)) return VK_EINVAL;
+    for (uint32_t i = 0; i < npairs; ++i)   // (q + shift stays below 2^64: ordinals are below 2^63)
+        if (pair_sample[i] >= nsamples || thresholds[i] > (1ull << 32) || shifts[i] >= (1ull << 63)) return VK_EINVAL;
+    if (nsamples == 0) return VK_OK;
+    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    FaPlan pl;
+    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    if (rc) return rc;
+    // sample | seed | threshold | shift | first workgroup of every pair
+    std::vector<uint64_t> pairs(5ull * npairs + 1);
+    uint64_t* pair_wg = pairs.data() + 4ull * npairs;
+    pair_wg[0] = 0;
+    for (uint32_t i = 0; i < npairs; ++i) {
+        pairs[i] = pair_sample[i];
+        pairs[npairs + i] = seeds[i];
+        pairs[2ull * npairs + i] = thresholds[i];
+        pairs[3ull * npairs + i] = shifts[i];
+        pair_wg[i + 1] = pair_wg[i] + (pl.wg_first()[pair_sample[i] + 1] - pl.wg_first()[pair_sample[i]]);
+    }
+    const uint64_t pair_nwg = pair_wg[npairs];
+    if (pair_nwg >= (1ull << 31)) return VK_EINVAL;
+    const uint32_t lanes = pl.unit / kFaLaneBytes;
+    uint64_t *d_meta = nullptr, *d_pairs = nullptr;
+    uint32_t *d_ukey = nullptr, *d_carry = nullptr, *d_lane = nullptr;
+    unsigned long long* d_unit_ord = nullptr;
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
+        take(d_meta, pl.meta.size());
+        take(d_pairs, pairs.size());
+        take(d_ukey, pl.nunits + 1);
+        take(d_carry, pl.nunits + 1);
+        take(d_unit_ord, pl.nunits + 1);
+        take(d_lane, pl.nunits * lanes + 1);   // the index: a word per lane of text, 1/16 of it
+    });
+    if (rc) return rc;
+    // (pageable sources: the copies have read them on return)
+    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    if (npairs) {
+        VK_HIP(ctx, hipMemsetAsync(d_hist, 0, npairs * ncode * sizeof(uint32_t), ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_taken, 0, npairs * sizeof(uint64_t), ctx->stream));
+    }
+    const FaMeta m = pl.on_device(d_meta);
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    rc = fa_header_state(ctx, text, pl, m, d_ukey, d_carry, d_status);
+    if (rc) return rc;
+    if (pl.nwg) {
+        hipLaunchKernelGGL(vk_fa_ord_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_carry,
+                           d_lane, d_unit_ord);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(vk_fa_ordscan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_unit_ord,
+                       reinterpret_cast<unsigned long long*>(d_bases));
+    VK_HIP(ctx, hipGetLastError());
+    if (pair_nwg) {
+        const FaPairs ps{d_pairs, d_pairs + npairs, d_pairs + 2ull * npairs, d_pairs + 3ull * npairs, d_pairs + 4ull * npairs, npairs,
+                         frag_len};
+        rc = with_k(k, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            hipLaunchKernelGGL(vk_fa_frag_count_kernel<K>, dim3(static_cast<uint32_t>(pair_nwg)), dim3(kFaThreads), 0, ctx->stream, text,
+                               m, ps, d_lane, d_unit_ord, d_hist, reinterpret_cast<unsigned long long*>(d_taken));
             VK_HIP(ctx, hipGetLastError());
             return VK_OK;
         });

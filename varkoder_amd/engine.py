@@ -561,6 +561,28 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_fasta_device")
         return hist, status, bases
 
+    def count_fasta_sampled(self, fasta, offsets, lengths, frag_len, pair_sample, seeds, thresholds, shifts):
+        """The subsample ladder of FASTA samples in HBM (vk_count_fasta_sampled_device; the rule: INTEGRATION.md,
+        "--from-fasta --fragments"): pair i counts sample pair_sample[i] over the fragments of frag_len bytes that
+        (seeds[i], thresholds[i], shifts[i]) take.  Returns (hist [npairs, 4^k], status [n], bases int64 [n], taken int64
+        [npairs] = the sequence bytes in taken fragments), all on the device."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        ps = np.ascontiguousarray(pair_sample, dtype=np.uint32)
+        sd, th, sh = (np.ascontiguousarray(a, dtype=np.uint64) for a in (seeds, thresholds, shifts))
+        if not (ps.ndim == 1 and ps.shape == sd.shape == th.shape == sh.shape):
+            raise ValueError("pair_sample, seeds, thresholds and shifts must be 1-D and of equal length")
+        hist = torch.empty((len(ps), self.ncode), dtype=torch.int32, device=self.device)
+        status = torch.empty((n,), dtype=torch.int32, device=self.device)
+        bases = torch.empty((n,), dtype=torch.int64, device=self.device)
+        taken = torch.empty((len(ps),), dtype=torch.int64, device=self.device)
+        st = self.L.vk_count_fasta_sampled_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, self.k, int(frag_len),
+                                                  len(ps), _u32(ps), _u64(sd), _u64(th), _u64(sh), self._ptr(hist),
+                                                  self._ptr(status), self._ptr(bases), self._ptr(taken))
+        _capi.check(self.ctx, st, "vk_count_fasta_sampled_device")
+        return hist, status, bases, taken
+
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):
         """K1 over a pseudo-random subset of each sample's reads (vk_count_sampled_device):

@@ -1,15 +1,23 @@
 """`image --from-fasta` / `query --from-fasta`: assemblies, contigs, organelle genomes -- FASTA files, one sample per
 file, counted whole on the GPU (ImageEngine.count_fasta; the rule: INTEGRATION.md, "--from-fasta") and imaged like any
-histogram.  Stands where the reference would hand dsk a FASTA `-file` (commands/image.py:771-796).  Drawing read-like
-fragments from an assembly is not done here: a sample is one image of all its bases."""
+histogram.  Stands where the reference would hand dsk a FASTA `-file` (commands/image.py:771-796).
+
+`image --from-fasta --fragments` draws the 1-2-5 subsample ladder of the read entries from an assembly (the rule:
+INTEGRATION.md, "--from-fasta --fragments"): the joined bases of a sample are tiled into fragments of `--fragment-length`
+bases, shifted per step; a step of `bp` bases takes each fragment with probability bp / bases (sample_hash of the step's
+seed and the fragment's number) and counts the k-mers inside the taken fragments (ImageEngine.count_fasta_sampled).
+fasta_plan is the plan (names, seeds, thresholds, shifts: host arithmetic), fasta_ladder runs it on a batch in HBM, and
+fasta_to_images(fragments=True) images every step as `<sample>@<bp>K+<mapping>+k<k>.png`, bp the step's size."""
 import time
 from collections import OrderedDict
 from pathlib import Path
 
+import numpy as np
+
 from .image import eprint
-from .pipeline import DEFAULT_BATCH_BYTES, PngSink, batches, engine_scope, text_bytes
+from .pipeline import DEFAULT_BATCH_BYTES, PngSink, _seed_groups, batches, engine_scope, text_bytes
 from .shard import agreed_weights, file_weights, shard_by_size
-from .subsample import split_name
+from .subsample import ladder_plan, plan_steps, split_name
 
 FASTA_SUFFIXES = (".fa", ".fasta", ".fna")
 
@@ -42,6 +50,61 @@ def image_name(sample, bases, k, mapping_code):
     return split_name(sample, bases) + f"+{mapping_code}+k{k}.png"
 
 
+def sample_hash(seed, anchor):
+    """csrc/vk_lane.h's sample_hash: what decides whether a step takes a fragment (anchor: the fragment's number)."""
+    m = 0xFFFFFFFF
+    h = (anchor ^ seed) & m
+    h = (h + ((anchor >> 32) * 0x9E3779B1 & m) + (seed >> 32)) & m
+    h ^= h >> 16
+    h = h * 0x85EBCA6B & m
+    h ^= h >> 13
+    h = h * 0xC2B2AE35 & m
+    h ^= h >> 16
+    return h
+
+
+SAMPLED_HIST_BYTES = 1 << 30   # histograms of one count_fasta_sampled call
+
+
+def fasta_plan(bases, status, frag_len, seed=0, min_bp=50000, max_bp=None):
+    """The ladder of a batch of FASTA samples from their sequence bytes and status words: (records, steps) -- the records
+    of subsample.ladder_plan over nsites = bases, and per step (sample, level, bp, seed + level, threshold, shift, whole)
+    in the samples' order, largest first: subsample.plan_steps' tuples with the step's shift, sample_hash(its seed,
+    2^64 - 1) mod frag_len, before `whole` (the step is the sample's plain count)."""
+    recs, plans = ladder_plan(bases, status, min_bp, max_bp)
+    for rec in recs:
+        if rec["status"]:
+            rec["error"] = "not a FASTA text"
+    steps = [(i, level, bp, sd, thr, sample_hash(sd & (2 ** 64 - 1), 2 ** 64 - 1) % frag_len, whole)
+             for i, level, bp, sd, thr, whole in plan_steps(plans, [int(b) for b in bases], seed)]
+    return recs, steps
+
+
+def fasta_ladder(engine, dev, offs, lens, frag_len, seed=0, min_bp=50000, max_bp=None):
+    """All ladder steps of a batch of FASTA samples resident in HBM.  Returns one record per sample, shaped like
+    subsample.ladder_counts' records: OrderedDict(nsites = its bases, status, steps=[(bp, hist uint32 tensor [4^k] on the
+    device, bases taken)], error).  The step that holds all of a sample is its plain count (count_fasta); every other
+    step of the batch goes into one count_fasta_sampled call (more when their histograms pass SAMPLED_HIST_BYTES)."""
+    offs, lens = np.asarray(offs, dtype=np.uint64), np.asarray(lens, dtype=np.uint64)
+    hist, status, bases = engine.count_fasta(dev, offs, lens)
+    bases_h = bases.cpu().numpy()
+    recs, steps = fasta_plan(bases_h, status.cpu().numpy(), frag_len, seed, min_bp, max_bp)
+    sampled = [st for st in steps if not st[6]]
+    got = {}
+    chunk = max(1, SAMPLED_HIST_BYTES // (4 * engine.ncode))
+    for at in range(0, len(sampled), chunk):
+        part = sampled[at:at + chunk]
+        h, _, _, taken = engine.count_fasta_sampled(dev, offs, lens, frag_len, [st[0] for st in part],
+                                                    [st[3] & (2 ** 64 - 1) for st in part], [st[4] for st in part],
+                                                    [st[5] for st in part])
+        taken = taken.cpu().numpy()
+        for j, st in enumerate(part):
+            got[st[:2]] = (h[j], int(taken[j]))
+    for i, level, bp, *_, whole in steps:
+        recs[i]["steps"].append((bp, hist[i], int(bases_h[i])) if whole else (bp,) + got[(i, level)])
+    return recs
+
+
 def _counted(eng, files, pool, batch_bytes):
     """Per batch of files: (batch, histograms on the device, status, bases, the time the batch was begun, after the count)."""
     for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
@@ -55,10 +118,15 @@ def _counted(eng, files, pool, batch_bytes):
 
 
 def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=0, rank=0, world=1, batch_bytes=None,
-                    io_threads=8, engine=None, verbose=False, weights=None):
+                    io_threads=8, engine=None, verbose=False, weights=None, fragments=False, fragment_length=150,
+                    min_bp=50000, max_bp=None, seeds=None):
     """This rank's share of FASTA `files`, each imaged whole.  Returns {sample: OrderedDict(stats)} with the reference's
     keys `<k>mer_counting_time` and `k<k>_img_time`, or `failed_step` for a sample that does not begin with '>', holds
-    no base, or could not be read."""
+    no base, or could not be read.
+
+    fragments: every sample is imaged as a subsample ladder between min_bp and max_bp instead (fasta_ladder; seeds:
+    {sample: int}, default 0), drawn from fragments of fragment_length bases; the stats also carry `splitting_time` and
+    `splitting_bp_per_file`, and a sample whose ladder is empty gets `failed_step` = "split"."""
     files = [Path(f) for f in files]
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded)
@@ -66,7 +134,11 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
     stats = OrderedDict()
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, {}, 0)
-        for batch, hist, st, bases, t0, t1 in _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES):
+        if fragments:
+            for batch, _, t0 in batches(mine, batch_bytes or DEFAULT_BATCH_BYTES, size=text_bytes):
+                _fragment_images(eng, pool, batch, t0, sink, stats, seeds or {}, fragment_length, min_bp, max_bp, verbose)
+        whole = () if fragments else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
+        for batch, hist, st, bases, t0, t1 in whole:
             nz = (hist != 0).any(dim=1).cpu().numpy()
             imgs = eng.images(hist).cpu().numpy()
             for j, f in enumerate(batch):
@@ -82,6 +154,47 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
                 eprint(f"batch of {len(batch)} FASTA files: upload+count {t1 - t0:.3f}s")
         sink.finish(stats)
     return stats
+
+
+def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp, max_bp, verbose):
+    """One batch of fasta_to_images(fragments=True): upload, the ladders (one fasta_ladder call per seed), the images."""
+    import torch
+    k = sink.k
+    dev, offs, lens = eng.upload_files(batch, pool)
+    unread = getattr(eng, "last_upload_status", None)
+    names = [sample_of(f) for f in batch]
+    recs = [None] * len(batch)
+    for seed, idx in _seed_groups(names, seeds).items():
+        for j, r in zip(idx, fasta_ladder(eng, dev, offs[idx], lens[idx], frag_len, seed, min_bp, max_bp)):
+            recs[j] = r
+    flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
+    nz = torch.stack([h for _, _, h in flat]).ne(0).any(dim=1).cpu().numpy() if flat else []
+    t1 = time.perf_counter()
+    imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
+    for j, f in enumerate(batch):
+        s = stats.setdefault(names[j], OrderedDict())
+        # (a file that could not be read or inflated is not an empty sample)
+        if recs[j]["status"] or recs[j]["nsites"] == 0 or (unread is not None and unread[j]):
+            eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
+            s["failed_step"] = "image"
+            recs[j]["steps"] = []
+        elif not recs[j]["steps"]:
+            eprint("SPLIT FAIL:", f, "-", recs[j]["error"] or "Input file has less than minimum data.")
+            s["failed_step"] = "split"
+        else:
+            s["splitting_time"] = (t1 - t0) / len(batch)
+            s["splitting_bp_per_file"] = ",".join(str(bp) for bp, _, _ in recs[j]["steps"])
+            s[str(k) + "mer_counting_time"] = (t1 - t0) / len(batch)
+    for n, (j, bp, _) in enumerate(flat):
+        if not recs[j]["steps"]:
+            continue
+        if not nz[n]:
+            eprint("IMAGE FAIL:", split_name(names[j], bp))
+            stats[names[j]]["failed_step"] = "image"
+            continue
+        sink.submit(names[j], names[j], image_name(names[j], bp, k, sink.mapping_code), imgs[n])
+    if verbose:
+        eprint(f"batch of {len(batch)} FASTA files: upload+ladder {t1 - t0:.3f}s")
 
 
 def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batch_bytes=None, io_threads=8):
