@@ -406,6 +406,43 @@ int vk_count_fasta_sampled_device(vk_ctx* ctx, const void* d_fasta, const uint64
 int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k, uint32_t* hist, uint32_t* status,
                         uint64_t* bases);
 
+#define VK_FA_NAME_BYTES 128u        /* bytes kept of a record's name, zero-padded */
+#define VK_FA_NO_SLOT 0xFFFFFFFFu    /* a record without a row: not counted */
+
+/* Replaces: dsk on a FASTA input (commands/image.py:771-796), once per RECORD instead of once per file -- `image / query
+ * --from-fasta --per-record`.  The rule is this project's ("--from-fasta --per-record";
+ * tests/fasta_records_ref.py); lines, headers and bases are vk_count_fasta_device's.  A sample without VK_ST_BAD_START has
+ * one record per header line, in order, those without sequence bytes included; a sample with it, or an empty one, has
+ * none.  d_nrec[nsamples] (u32, device) = the records of each sample; d_status[nsamples] as vk_count_fasta_device's.  The
+ * batch is laid out as for vk_count_fasta_device.  VKIMG_FASTA_UNIT_BYTES shrinks the units here as well.  No
+ * synchronisation. */
+int vk_fasta_records_count_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                                  uint32_t nsamples, uint32_t* d_nrec, uint32_t* d_status);
+
+/* Replaces: the sequence names and lengths dsk's FASTA reader sees (commands/image.py:771-796) -- the record table of a
+ * batch whose record counts the caller has read back: rec_first[nsamples + 1] (host) = prefix sums of d_nrec, total =
+ * rec_first[nsamples].  Record g = rec_first[s] + r (r: its ordinal in sample s): d_rec_start[g] (u64) = the offset of its
+ * '>' within the sample; d_rec_bases[g] (u64) = its joined bytes, every class (their sum over a sample is
+ * vk_count_fasta_device's d_bases); d_rec_name[g][VK_FA_NAME_BYTES] = the bytes of its header line behind the '>' up to,
+ * not including, the '\n' or the sample's end, at most VK_FA_NAME_BYTES of them, zero-padded (a trailing '\r' is kept).
+ * All three are zeroed by the call; a record past rec_first's count is not written.  VK_EINVAL, before anything is
+ * launched, for a null pointer or a rec_first that does not start at 0 or decreases.  No synchronisation. */
+int vk_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                            uint32_t nsamples, const uint64_t* rec_first, uint64_t* d_rec_start, uint64_t* d_rec_bases,
+                            uint8_t* d_rec_name);
+
+/* Replaces: dsk on one FASTA file per record (commands/image.py:771-796).  d_slot[total] (u32, device): the row of every
+ * record of the batch, or VK_FA_NO_SLOT; the slots are distinct, in [0, nslots), and increase with the record's position
+ * in the batch.  d_hist[nslots][4^k] (u32, wrapping; zeroed by the call): the row of record g's slot = what
+ * vk_count_fasta_device gives for a sample that holds this record alone; the rows of a sample's records sum to its
+ * vk_count_fasta_device row.  A record without a slot is not counted and touches no row; a row no record names comes back
+ * zero; a workgroup none of whose records has a slot does not read its text.  VK_EINVAL, before anything is launched,
+ * for a null pointer, k outside 5..9, nslots == 0, or a rec_first that does not start at 0 or decreases.  No
+ * synchronisation. */
+int vk_count_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                                  uint32_t nsamples, int k, const uint64_t* rec_first, const uint32_t* d_slot, uint32_t nslots,
+                                  uint32_t* d_hist);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -98,6 +98,7 @@ def setup_parser():
                         "bases of the assembly (rule: INTEGRATION.md, \"--from-fasta --fragments\")")
     p.add_argument("--fragment-length", type=int, default=argparse.SUPPRESS, metavar="N",
                    help="with --from-fasta --fragments: bases of a fragment, 16 to 1000000 (150 when absent)")
+    add_record_flags(p)
     p.add_argument("--write-splits", action="store_true", default=argparse.SUPPRESS,   # (absent = off, as the adapter flags)
                    help="with --from-raw / --from-clean and -i INT: also write every subsample's reads to "
                         "`INT/split_fastqs/<sample>@<bp>K.fq.gz`, the files the default entry takes (kept unless -x "
@@ -151,6 +152,7 @@ def setup_parser():
     q.add_argument("--from-fasta", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`), one sample each: counted whole "
                         "on the GPU, imaged and predicted")
+    add_record_flags(q)
     q.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-raw and -i INT: compress the cleaned reads on the GPU, as BGZF, and copy back the "
                         "compressed bytes only")
@@ -216,6 +218,19 @@ def setup_parser():
     return main
 
 
+MIN_RECORD_LENGTH_DEFAULT = 1000
+
+
+def add_record_flags(p):
+    p.add_argument("--per-record", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-fasta: every RECORD of a FASTA file is a sample of its own, `<file sample>__<id>`, id "
+                        "= its header up to the first blank (a reference collection in one multi-FASTA; the contigs of "
+                        "an assembly, each on its own; rule: INTEGRATION.md, \"--from-fasta --per-record\")")
+    p.add_argument("--min-record-length", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --from-fasta --per-record: records of fewer than N bases are passed over, N >= k "
+                        f"({MIN_RECORD_LENGTH_DEFAULT} when absent)")
+
+
 ADAPTER_FLAGS = (("detect_adapters", "--detect-adapters"), ("adapter_sequence", "--adapter-sequence"),
                  ("adapter_sequence_r2", "--adapter-sequence-r2"))
 
@@ -236,6 +251,16 @@ def parse_args(argv=None):
         for name, flag in (("write_splits", "--write-splits"), ("gpu_gzip", "--gpu-gzip")):
             if getattr(args, name, False):
                 parser.error(f"--from-fasta: not with {flag}")
+    if args.command in ("image", "query"):
+        for name, flag in (("per_record", "--per-record"), ("min_record_length", "--min-record-length")):
+            if hasattr(args, name) and not getattr(args, "from_fasta", False):
+                parser.error(f"{flag}: only with --from-fasta")
+        if hasattr(args, "min_record_length") and not getattr(args, "per_record", False):
+            parser.error("--min-record-length: only with --per-record")
+        if getattr(args, "per_record", False) and getattr(args, "fragments", False):
+            parser.error("--per-record: not with --fragments")
+        if hasattr(args, "min_record_length") and args.min_record_length < args.kmer_size:
+            parser.error("--min-record-length: at least the k-mer size")
     if args.command == "image":
         for name, flag in (("fragments", "--fragments"), ("fragment_length", "--fragment-length")):
             if hasattr(args, name) and not getattr(args, "from_fasta", False):
@@ -419,8 +444,18 @@ def run_query(args):
             if mine:
                 eng = state["eng"] = ImageEngine(k=args.kmer_size, mapping=args.kmer_mapping, device=device)
                 wanted = [(i, sample_of(inputs[i])) for i in mine]
+                record_opts, origin = {}, {}
+                if getattr(args, "per_record", False):
+                    record_opts = dict(per_record=True, origin=origin,
+                                       min_record_length=getattr(args, "min_record_length", MIN_RECORD_LENGTH_DEFAULT))
                 found = fasta_to_query([(s, inputs[i]) for i, s in wanted], engine=eng, k=args.kmer_size,
-                                       mapping_code=args.kmer_mapping, io_threads=io_threads_per_rank(args.n_threads))
+                                       mapping_code=args.kmer_mapping, io_threads=io_threads_per_rank(args.n_threads),
+                                       **record_opts)
+                if record_opts:   # a row per record, in the order of the files and of the records within each
+                    of_file = {s: [] for _, s in wanted}
+                    for rs in found:
+                        of_file[origin[rs]].append(rs)
+                    wanted = [(i, rs) for i, s in wanted for rs in of_file[s]]
                 images = found_images(found, wanted, {})
         else:
             # cleaned reads, a sample per file: no labels and no base-frequency sd, as images written with neither read back
@@ -608,6 +643,11 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
     labels = read_labels(args.labels_csv)
     eprint("Counting kmers and creating images for", len(files), "FASTA samples")
     ladder = {}
+    per_record = getattr(args, "per_record", False)
+    if per_record:   # a label by record sample first, then by the sample of its file
+        from .fasta import RecordLabels
+        labels = RecordLabels(labels, samples)
+        ladder = dict(per_record=True, min_record_length=getattr(args, "min_record_length", MIN_RECORD_LENGTH_DEFAULT))
     if getattr(args, "fragments", False):   # -m, -M and -R as for --from-clean
         ladder = dict(fragments=True, fragment_length=getattr(args, "fragment_length", FRAGMENT_LENGTH_DEFAULT),
                       min_bp=parse_size(args.min_bp), max_bp=max_bp_of(args), seeds=draw_seeds(samples, args.seed))
@@ -622,7 +662,8 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
             v["base_frequencies_sd"] = 0   # (no cleaning report: the flag is False, as for any sample without one)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
         error = e
-    finish_image_job(args, outdir, rank, world, per_sample, error, samples, labels, {})
+    # (per record: the samples are the imaged records, known once the ranks' stats are merged)
+    finish_image_job(args, outdir, rank, world, per_sample, error, None if per_record else samples, labels, {})
 
 
 def run_image_from_raw(args, outdir, rank, world, local_rank):
@@ -684,6 +725,8 @@ def finish_image_job(args, outdir, rank, world, per_sample, error, samples, labe
         try:
             rows = [OrderedDict([("sample", s)] + list(v.items())) for s, v in merged.items()]
             pd.DataFrame(rows).to_csv(args.stats_file, index=False)
+            if samples is None:   # `--from-fasta --per-record`: one row per imaged record
+                samples = [s for s, v in merged.items() if "failed_step" not in v]
             if args.label_table and not errors:                               # image.py:1172-1185
                 # (a sample of another rank whose figure only travelled with the stats: --from-raw computes it there)
                 sd = {s: base_sd.get(s, merged.get(s, {}).get("base_frequencies_sd", 0)) for s in samples}

@@ -27,6 +27,7 @@
 //     windows through wave-private queues into 16 streams (vk_bucket_kernel<K, 1>, vk_bucket_count_kernel).
 //   vk_remap_kernel / vk_preprocess_kernel: `convert`'s remap and the input side of `query`.
 //   vk_fa_*_kernel (vk_fasta.h): the count straight from FASTA text (`--from-fasta`): cut by bytes, header state by a scan.
+//   vk_far_*_kernel (vk_fasta_records.h): the same per FASTA record (`--per-record`): record ordinal by a second scan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,6 +59,7 @@
 #include "vk_deflate.h"
 #include "vk_fasta.h"
 #include "vk_fasta_ladder.h"
+#include "vk_fasta_records.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -2589,6 +2591,132 @@ int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k,
     if (status) *status = st;
     if (bases) *bases = nb;
     return st ? VK_EFORMAT : VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- FASTA records (vk_fasta_records.h) ---------------
+
+namespace {
+
+// What the three per-record calls share: the plan on the device, the header state and the header count that enter every
+// unit (d_carry, d_uhdr), the samples' status words and record counts.  `extra` states the call's own pieces.
+struct FarState {
+    FaPlan pl;
+    FaMeta m;
+    uint32_t *d_ukey = nullptr, *d_carry = nullptr, *d_uhdr = nullptr, *d_status = nullptr, *d_nrec = nullptr;
+    uint64_t* d_rec_first = nullptr;
+};
+
+// rec_first: null (the counting call) or host u64[nsamples + 1], checked by the caller.  d_status, d_nrec: the caller's,
+// or null for pieces of the workspace.
+int far_prepare(vk_ctx* ctx, const uint8_t* text, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                const uint64_t* rec_first, uint32_t* d_status, uint32_t* d_nrec, FarState* st) {
+    int rc = fa_plan(ctx, offsets, lengths, nsamples, &st->pl);
+    if (rc) return rc;
+    const FaPlan& pl = st->pl;
+    uint64_t* d_meta = nullptr;
+    uint32_t *ws_status = nullptr, *ws_nrec = nullptr;
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
+        take(d_meta, pl.meta.size());
+        take(st->d_rec_first, nsamples + 1ull);
+        take(st->d_ukey, pl.nunits + 1);
+        take(st->d_carry, pl.nunits + 1);
+        take(st->d_uhdr, pl.nunits + 1);
+        take(ws_status, nsamples);
+        take(ws_nrec, nsamples);
+    });
+    if (rc) return rc;
+    st->d_status = d_status ? d_status : ws_status;
+    st->d_nrec = d_nrec ? d_nrec : ws_nrec;
+    // (pageable sources: the copies have read them on return)
+    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (rec_first)
+        VK_HIP(ctx, hipMemcpyAsync(st->d_rec_first, rec_first, (nsamples + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    st->m = pl.on_device(d_meta);
+    if (pl.nwg) {
+        hipLaunchKernelGGL(vk_far_summary_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st->m,
+                           st->d_ukey, st->d_uhdr);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(vk_far_scan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, st->m, st->d_ukey, st->d_carry,
+                       st->d_uhdr, st->d_status, st->d_nrec);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+bool far_rec_first_ok(const uint64_t* rec_first, uint32_t nsamples) {
+    if (rec_first[0] != 0) return false;
+    for (uint32_t i = 0; i < nsamples; ++i)
+        if (rec_first[i + 1] < rec_first[i]) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_fasta_records_count_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                                  uint32_t* d_nrec, uint32_t* d_status) {
+    if (!ctx || !offsets || !lengths || !d_nrec || !d_status) return VK_EINVAL;
+    if (nsamples == 0) return VK_OK;
+    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    FarState st;
+    return far_prepare(ctx, static_cast<const uint8_t*>(d_fasta), offsets, lengths, nsamples, nullptr, d_status, d_nrec, &st);
+}
+
+int vk_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                            const uint64_t* rec_first, uint64_t* d_rec_start, uint64_t* d_rec_bases, uint8_t* d_rec_name) {
+    if (!ctx || !offsets || !lengths || !rec_first || !d_rec_start || !d_rec_bases || !d_rec_name) return VK_EINVAL;
+    if (!far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
+    if (nsamples == 0) return VK_OK;
+    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    FarState st;
+    int rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
+    if (rc) return rc;
+    const uint64_t total = rec_first[nsamples];
+    if (total == 0) return VK_OK;
+    VK_HIP(ctx, hipMemsetAsync(d_rec_start, 0, total * sizeof(uint64_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rec_bases, 0, total * sizeof(uint64_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rec_name, 0, total * kFaNameBytes, ctx->stream));
+    if (st.pl.nwg) {
+        hipLaunchKernelGGL(vk_far_table_kernel, dim3(static_cast<uint32_t>(st.pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m,
+                           st.d_carry, st.d_uhdr, FaRecs{st.d_rec_first}, reinterpret_cast<unsigned long long*>(d_rec_start),
+                           reinterpret_cast<unsigned long long*>(d_rec_bases), d_rec_name);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    return VK_OK;
+}
+
+int vk_count_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                                  int k, const uint64_t* rec_first, const uint32_t* d_slot, uint32_t nslots, uint32_t* d_hist) {
+    if (!ctx || !offsets || !lengths || !rec_first || !d_slot || !d_hist || k < 5 || k > 9 || nslots == 0) return VK_EINVAL;
+    if (nslots == kFaNoSlot || !far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
+    if (nsamples && (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0)) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    for (uint32_t i = 0; i < nsamples; ++i)
+        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nslots * ncode * sizeof(uint32_t), ctx->stream));
+    if (nsamples == 0 || rec_first[nsamples] == 0) return VK_OK;
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    FarState st;
+    int rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
+    if (rc) return rc;
+    if (st.pl.nwg) {
+        rc = with_k(k, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            hipLaunchKernelGGL(vk_far_count_kernel<K>, dim3(static_cast<uint32_t>(st.pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text,
+                               st.m, st.d_carry, st.d_uhdr, st.d_nrec, FaRecs{st.d_rec_first}, d_slot, nslots, d_hist);
+            VK_HIP(ctx, hipGetLastError());
+            return VK_OK;
+        });
+        if (rc) return rc;
+    }
+    return VK_OK;
 }
 
 }  // extern "C"

@@ -583,6 +583,50 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_fasta_sampled_device")
         return hist, status, bases, taken
 
+    def fasta_records(self, fasta, offsets, lengths):
+        """The records of FASTA samples in HBM (vk_fasta_records_count_device, vk_fasta_records_device; the rule:
+        INTEGRATION.md, "--from-fasta --per-record"): (rec_first uint64 [n + 1] = prefix sums of the samples' record
+        counts, start uint64 [total], bases uint64 [total], names = [bytes] of at most VK_FA_NAME_BYTES, status uint32
+        [n]), all on the host; synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        nrec = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        status = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        st = self.L.vk_fasta_records_count_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, self._ptr(nrec),
+                                                  self._ptr(status))
+        _capi.check(self.ctx, st, "vk_fasta_records_count_device")
+        rec_first = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(nrec.cpu().numpy().view(np.uint32), out=rec_first[1:])
+        total = int(rec_first[n])
+        start = torch.zeros((max(total, 1),), dtype=torch.int64, device=self.device)
+        bases = torch.zeros((max(total, 1),), dtype=torch.int64, device=self.device)
+        name = torch.zeros((max(total, 1), _capi.VK_FA_NAME_BYTES), dtype=torch.uint8, device=self.device)
+        st = self.L.vk_fasta_records_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, _u64(rec_first),
+                                            self._ptr(start), self._ptr(bases), self._ptr(name))
+        _capi.check(self.ctx, st, "vk_fasta_records_device")
+        raw = name.cpu().numpy()[:total]
+        names = [bytes(row).rstrip(b"\0") for row in raw]
+        return (rec_first, start.cpu().numpy().view(np.uint64)[:total], bases.cpu().numpy().view(np.uint64)[:total], names,
+                status.cpu().numpy().view(np.uint32))
+
+    def count_fasta_records(self, fasta, offsets, lengths, rec_first, slot, nslots):
+        """One histogram per selected record (vk_count_fasta_records_device): slot uint32 [total] names the row of every
+        record of the batch or VK_FA_NO_SLOT.  Returns hist [nslots, 4^k] on the device."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        rec_first = np.ascontiguousarray(rec_first, dtype=np.uint64)
+        slot = np.ascontiguousarray(slot, dtype=np.uint32)
+        if rec_first.shape != (n + 1,) or slot.shape != (int(rec_first[n]),):
+            raise ValueError("rec_first must hold n + 1 prefix sums and slot one entry per record")
+        d_slot = torch.from_numpy(slot.view(np.int32) if slot.size else np.zeros(1, dtype=np.int32)).to(self.device)
+        hist = torch.empty((int(nslots), self.ncode), dtype=torch.int32, device=self.device)
+        st = self.L.vk_count_fasta_records_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, self.k, _u64(rec_first),
+                                                  self._ptr(d_slot), int(nslots), self._ptr(hist))
+        _capi.check(self.ctx, st, "vk_count_fasta_records_device")
+        return hist
+
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):
         """K1 over a pseudo-random subset of each sample's reads (vk_count_sampled_device):

@@ -7,7 +7,11 @@ INTEGRATION.md, "--from-fasta --fragments"): the joined bases of a sample are ti
 bases, shifted per step; a step of `bp` bases takes each fragment with probability bp / bases (sample_hash of the step's
 seed and the fragment's number) and counts the k-mers inside the taken fragments (ImageEngine.count_fasta_sampled).
 fasta_plan is the plan (names, seeds, thresholds, shifts: host arithmetic), fasta_ladder runs it on a batch in HBM, and
-fasta_to_images(fragments=True) images every step as `<sample>@<bp>K+<mapping>+k<k>.png`, bp the step's size."""
+fasta_to_images(fragments=True) images every step as `<sample>@<bp>K+<mapping>+k<k>.png`, bp the step's size.
+
+`image / query --from-fasta --per-record` make every record of a file a sample of its own (the rule: INTEGRATION.md,
+"--from-fasta --per-record"): ImageEngine.fasta_records gives the record table of a batch, record_names the samples'
+names, record_plan the calls of ImageEngine.count_fasta_records, a row per selected record."""
 import time
 from collections import OrderedDict
 from pathlib import Path
@@ -105,6 +109,109 @@ def fasta_ladder(engine, dev, offs, lens, frag_len, seed=0, min_bp=50000, max_bp
     return recs
 
 
+RECORD_HIST_BYTES = 1 << 30    # histograms of one count_fasta_records call
+RECORD_ID_BYTES = 100
+
+
+def record_names(file_sample, names):
+    """The sample names of a file's records from their header lines (the bytes behind the '>'): (sample names, indices of
+    the duplicates).  The id is the name up to the first blank, tab or \\r, every byte outside [A-Za-z0-9._-] replaced by
+    '_', cut to RECORD_ID_BYTES, `record<ordinal + 1>` when empty; the sample name is `<file sample>__<id>`.  A later
+    record whose sample name equals an earlier one's is a duplicate: the first stands."""
+    out, dup, seen = [], [], set()
+    for i, raw in enumerate(names):
+        rid = bytes(raw)
+        for sep in (b" ", b"\t", b"\r"):
+            rid = rid.split(sep, 1)[0]
+        rid = "".join(chr(b) if (48 <= b <= 57 or 65 <= b <= 90 or 97 <= b <= 122 or b in b"._-") else "_"
+                      for b in rid[:RECORD_ID_BYTES])
+        name = f"{file_sample}__{rid or 'record%d' % (i + 1)}"
+        if name in seen:
+            dup.append(i)
+        seen.add(name)
+        out.append(name)
+    return out, dup
+
+
+def record_plan(bases, min_len, hist_bytes=RECORD_HIST_BYTES, ncode=4 ** 7):
+    """The count_fasta_records calls of a batch: the records with bases >= min_len (indices into `bases`, the batch's
+    record table), in order, in runs whose rows (4 * ncode bytes each) fit in hist_bytes; a single row always fits."""
+    per_call = max(1, int(hist_bytes) // (4 * int(ncode)))
+    chosen = [i for i, b in enumerate(bases) if int(b) >= min_len]
+    return [chosen[at:at + per_call] for at in range(0, len(chosen), per_call)]
+
+
+class RecordLabels:
+    """--labels-csv for records: a record's sample name first, then the sample of its file (`<file sample>__<id>`; the
+    longest file sample that fits), so that a collection file labelled once labels all of its records."""
+
+    def __init__(self, table, file_samples):
+        self.table = dict(table or {})
+        self.file_samples = sorted(file_samples, key=len, reverse=True)
+
+    def get(self, sample, default=None):
+        if sample in self.table:
+            return self.table[sample]
+        for fs in self.file_samples:
+            if sample.startswith(fs + "__") and fs in self.table:
+                return self.table[fs]
+        return default
+
+
+def _record_batches(eng, files, pool, batch_bytes, min_len):
+    """Per batch of files, per record: (batch, first, status, rec_first, bases, samples, dups, rows, hist, t0, t1) -- the
+    files' status words, the batch's record table (prefix sums of the files' record counts, bases and sample name of
+    every record, the indices of the duplicates), rows = {record: its row in hist} and hist on the device, the time the
+    batch was begun and the time after the count.  One yield per call of record_plan, `first` on a batch's first, so
+    that a batch whose rows pass RECORD_HIST_BYTES is imaged in pieces; a batch without a selected record yields once
+    with hist None.  Records shorter than min_len and duplicates get no row."""
+    import torch
+    for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
+        dev, offs, lens = eng.upload_files(batch, pool)
+        unread = getattr(eng, "last_upload_status", None)
+        rec_first, _, bases, names, status = eng.fasta_records(dev, offs, lens)
+        status = status.copy()
+        if unread is not None:
+            status[unread != 0] |= 0x100   # (a file that could not be read or inflated is not an empty sample)
+        samples, dups = [], set()
+        for j, f in enumerate(batch):
+            a, b = int(rec_first[j]), int(rec_first[j + 1])
+            got, dup = record_names(sample_of(f), names[a:b])
+            samples += got
+            dups.update(a + i for i in dup)
+        wanted = [-1 if g in dups else int(b) for g, b in enumerate(bases)]
+        calls = record_plan(wanted, min_len, RECORD_HIST_BYTES, eng.ncode) or [[]]
+        for n, call in enumerate(calls):
+            hist = None
+            if call:
+                slot = np.full(len(bases), 0xFFFFFFFF, dtype=np.uint32)
+                slot[call] = np.arange(len(call), dtype=np.uint32)
+                hist = eng.count_fasta_records(dev, offs, lens, rec_first, slot, len(call))
+                torch.cuda.current_stream(eng.device).synchronize()   # (the time after the count is the batch's)
+            yield (batch, n == 0, status, rec_first, bases, samples, dups, {g: j for j, g in enumerate(call)}, hist, t0,
+                   time.perf_counter())
+
+
+def _record_reports(batch, status, rec_first, bases, samples, dups, min_len, stats=None):
+    """What a batch's first yield says on stderr, per file: a file without records, the duplicates (each with a stats
+    row `<name>#<ordinal + 1>`), how many records were passed over as too short."""
+    for j, f in enumerate(batch):
+        a, b = int(rec_first[j]), int(rec_first[j + 1])
+        if status[j] or a == b:
+            eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
+            if stats is not None:
+                stats.setdefault(sample_of(f), OrderedDict())["failed_step"] = "image"
+            continue
+        short = sum(1 for g in range(a, b) if int(bases[g]) < min_len)
+        if short:
+            eprint(f"{f}: {short} of {b - a} records shorter than {min_len} bases passed over")
+        for g in range(a, b):
+            if g in dups and int(bases[g]) >= min_len:
+                eprint("DUPLICATE RECORD ID, SKIPPING:", f"{samples[g]} (record {g - a + 1} of {f})")
+                if stats is not None:
+                    stats.setdefault(f"{samples[g]}#{g - a + 1}", OrderedDict())["failed_step"] = "image"
+
+
 def _counted(eng, files, pool, batch_bytes):
     """Per batch of files: (batch, histograms on the device, status, bases, the time the batch was begun, after the count)."""
     for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
@@ -119,14 +226,19 @@ def _counted(eng, files, pool, batch_bytes):
 
 def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, fragments=False, fragment_length=150,
-                    min_bp=50000, max_bp=None, seeds=None):
+                    min_bp=50000, max_bp=None, seeds=None, per_record=False, min_record_length=1000):
     """This rank's share of FASTA `files`, each imaged whole.  Returns {sample: OrderedDict(stats)} with the reference's
     keys `<k>mer_counting_time` and `k<k>_img_time`, or `failed_step` for a sample that does not begin with '>', holds
     no base, or could not be read.
 
     fragments: every sample is imaged as a subsample ladder between min_bp and max_bp instead (fasta_ladder; seeds:
     {sample: int}, default 0), drawn from fragments of fragment_length bases; the stats also carry `splitting_time` and
-    `splitting_bp_per_file`, and a sample whose ladder is empty gets `failed_step` = "split"."""
+    `splitting_bp_per_file`, and a sample whose ladder is empty gets `failed_step` = "split".
+
+    per_record: every record of min_record_length bases or more is a sample of its own (record_names; the rule:
+    INTEGRATION.md, "--from-fasta --per-record"), imaged as `image_name(<record sample>, its bases, k, mapping)`; the
+    stats are keyed by record sample, `<k>mer_counting_time` is the batch's upload plus count time shared over its
+    imaged records, and a record with a row but no non-zero bin gets `failed_step` = "image"."""
     files = [Path(f) for f in files]
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded)
@@ -137,7 +249,9 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
         if fragments:
             for batch, _, t0 in batches(mine, batch_bytes or DEFAULT_BATCH_BYTES, size=text_bytes):
                 _fragment_images(eng, pool, batch, t0, sink, stats, seeds or {}, fragment_length, min_bp, max_bp, verbose)
-        whole = () if fragments else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
+        if per_record:
+            _record_images(eng, pool, mine, batch_bytes or DEFAULT_BATCH_BYTES, min_record_length, sink, stats, verbose)
+        whole = () if fragments or per_record else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
         for batch, hist, st, bases, t0, t1 in whole:
             nz = (hist != 0).any(dim=1).cpu().numpy()
             imgs = eng.images(hist).cpu().numpy()
@@ -154,6 +268,29 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
                 eprint(f"batch of {len(batch)} FASTA files: upload+count {t1 - t0:.3f}s")
         sink.finish(stats)
     return stats
+
+
+def _record_images(eng, pool, files, batch_bytes, min_len, sink, stats, verbose):
+    """fasta_to_images(per_record=True): the record table and the selected records' rows of every batch, the images."""
+    k = sink.k
+    for batch, first, st, rec_first, bases, samples, dups, rows, hist, t0, t1 in _record_batches(eng, files, pool, batch_bytes, min_len):
+        if first:
+            _record_reports(batch, st, rec_first, bases, samples, dups, min_len, stats)
+        if hist is None:
+            continue
+        nz = (hist != 0).any(dim=1).cpu().numpy()
+        imgs = eng.images(hist).cpu().numpy()
+        imaged = max(1, int(nz.sum()))
+        for g, row in rows.items():
+            s = stats.setdefault(samples[g], OrderedDict())
+            if not nz[row]:
+                eprint("K-MER COUNTING FAIL, SKIPPING RECORD:", samples[g])
+                s["failed_step"] = "image"
+                continue
+            s[str(k) + "mer_counting_time"] = (t1 - t0) / imaged
+            sink.submit(samples[g], samples[g], image_name(samples[g], int(bases[g]), k, sink.mapping_code), imgs[row])
+        if verbose:
+            eprint(f"batch of {len(batch)} FASTA files, {len(rows)} records: upload+count {t1 - t0:.3f}s")
 
 
 def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp, max_bp, verbose):
@@ -197,12 +334,33 @@ def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp,
         eprint(f"batch of {len(batch)} FASTA files: upload+ladder {t1 - t0:.3f}s")
 
 
-def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batch_bytes=None, io_threads=8):
+def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batch_bytes=None, io_threads=8, per_record=False,
+                   min_record_length=1000, origin=None):
     """{sample: (bp, histogram uint32[4^k] on the device, 0)} for samples = [(sample, its FASTA file)] (this rank's
-    share): what pipeline.clean_to_query returns for cleaned reads.  A sample that fails is reported and left out."""
+    share): what pipeline.clean_to_query returns for cleaned reads.  A sample that fails is reported and left out.
+
+    per_record: the same tuples keyed by record sample, one per record of min_record_length bases or more
+    (fasta_to_images' rule); origin (a dict) receives {record sample: the sample of its file}."""
     by_file = {Path(f): s for s, f in samples}
     found = OrderedDict()
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        if per_record:
+            for batch, first, st, rec_first, bases, names, dups, rows, hist, _, _ in _record_batches(
+                    eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES, min_record_length):
+                if first:
+                    _record_reports(batch, st, rec_first, bases, names, dups, min_record_length)
+                if hist is None:
+                    continue
+                nz = (hist != 0).any(dim=1).cpu().numpy()
+                file_of = np.searchsorted(rec_first, np.fromiter(rows, dtype=np.uint64, count=len(rows)), side="right") - 1
+                for (g, row), j in zip(rows.items(), file_of):
+                    if not nz[row]:
+                        eprint("K-MER COUNTING FAIL, SKIPPING RECORD:", names[g])
+                        continue
+                    found[names[g]] = (int(bases[g]), hist[row], 0)
+                    if origin is not None:
+                        origin[names[g]] = by_file[batch[int(j)]]
+            return found
         for batch, hist, st, bases, _, _ in _counted(eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES):
             nz = (hist != 0).any(dim=1).cpu().numpy()
             for j, f in enumerate(batch):
