@@ -443,6 +443,32 @@ int vk_count_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64
                                   uint32_t nsamples, int k, const uint64_t* rec_first, const uint32_t* d_slot, uint32_t nslots,
                                   uint32_t* d_hist);
 
+#define VK_FA_NO_WINDOW 0xFFFFFFFFFFFFFFFFull   /* a record without rows: none of its windows is counted */
+
+/* Replaces: dsk on one FASTA file per WINDOW of a record (commands/image.py:771-796, once per window) -- `image / query
+ * --from-fasta --windows`.  The rule is this project's ("--from-fasta --windows";
+ * tests/fasta_windows_ref.py); lines, headers, records and bases are vk_count_fasta_records_device's.  rec_first (host) and
+ * d_rec_bases[total] (u64, device) are what vk_fasta_records_device takes and returns.  A window has win_len bytes and the
+ * next one starts win_step behind it: win_step | win_len, m = win_len / win_step <= 64.  Window w of a record covers its
+ * ordinals [w * win_step, w * win_step + win_len), exists iff it lies within the record, and holds the record's counted
+ * k-mers whose FIRST byte lies in it (a k-mer may reach k - 1 bytes past the window's end, never past the record): what
+ * vk_count_fasta_device gives for a record made of the window's bytes and the k - 1 behind them.  d_win_first[total]
+ * (u64, device): the row of every record's window 0, or VK_FA_NO_WINDOW; window w has row d_win_first[g] + w; the rows of
+ * different records are disjoint and increase with the record's position in the batch.  The call counts the rows of
+ * [row_lo, row_lo + nrows) into d_hist[nrows][4^k] (u32, wrapping; zeroed by the call), row R at d_hist[R - row_lo];
+ * every other window touches nothing, a row of the range no window names comes back zero, and a workgroup none of whose
+ * bytes falls in a row of the range does not read its text.  m > 1: the call counts tiles of win_step bytes into
+ * tile_rows rows of 4^k u32 in the context's workspace and sums m of them into each window; the caller states
+ * tile_rows, at least the sum, over the records with a row in the range, of (their rows in the range + m - 1) (rows
+ * whose tiles do not fit come back zero); m == 1: tile_rows is not used.  Ordinals, d_win_first and row numbers are
+ * bounds-checked on the device.  VK_EINVAL, before anything is launched, for a null pointer, k outside 5..9, win_step < k,
+ * win_len % win_step != 0, win_len / win_step > 64, win_len >= 2^31, nrows == 0, tile_rows == 0 with m > 1, or a rec_first
+ * that does not start at 0 or decreases.  VKIMG_FASTA_UNIT_BYTES shrinks the units here as well.  No synchronisation. */
+int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                                  uint32_t nsamples, int k, const uint64_t* rec_first, const uint64_t* d_rec_bases,
+                                  const uint64_t* d_win_first, uint32_t win_len, uint32_t win_step, uint64_t row_lo,
+                                  uint32_t nrows, uint32_t tile_rows, uint32_t* d_hist);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -15,6 +15,7 @@ VK_CL_BAD_FRAMING, VK_CL_RAGGED = 1, 2
 VK_CL_NSTAT = 202
 VK_CL_MAX_ADAPTER, VK_CL_DETECT_RECORDS = 64, 262144
 VK_FA_NAME_BYTES, VK_FA_NO_SLOT = 128, 0xFFFFFFFF
+VK_FA_NO_WINDOW = 0xFFFFFFFFFFFFFFFF
 VK_GZ_BAD_HEADER, VK_GZ_BAD_DATA, VK_GZ_TRUNCATED, VK_GZ_OVERFLOW, VK_GZ_BAD_SIZE, VK_GZ_BAD_CRC = 1, 2, 4, 8, 16, 32
 
 # every symbol include/vkimg.h declares
@@ -27,7 +28,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device", "vk_ladder_emit_workspace_size",
            "vk_ladder_emit_device", "vk_train_batch_device", "vk_deflate_bound", "vk_deflate_workspace_size", "vk_deflate_device",
            "vk_count_fasta_device", "vk_count_fasta_host", "vk_count_fasta_sampled_device", "vk_fasta_records_count_device",
-           "vk_fasta_records_device", "vk_count_fasta_records_device")
+           "vk_fasta_records_device", "vk_count_fasta_records_device", "vk_count_fasta_windows_device")
 
 _lib = None
 
@@ -99,6 +100,8 @@ def lib():
     L.vk_fasta_records_count_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, vp, vp]
     L.vk_fasta_records_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, u64p, vp, vp, vp]
     L.vk_count_fasta_records_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, u64p, vp, C.c_uint32, vp]
+    L.vk_count_fasta_windows_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, u64p, vp, vp, C.c_uint32, C.c_uint32,
+                                                C.c_uint64, C.c_uint32, C.c_uint32, vp]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]
     L.vk_preprocess_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float, vp]

@@ -219,6 +219,7 @@ def setup_parser():
 
 
 MIN_RECORD_LENGTH_DEFAULT = 1000
+WINDOW_LENGTH_DEFAULT = 10000
 
 
 def add_record_flags(p):
@@ -229,6 +230,24 @@ def add_record_flags(p):
     p.add_argument("--min-record-length", type=int, default=argparse.SUPPRESS, metavar="N",
                    help="with --from-fasta --per-record: records of fewer than N bases are passed over, N >= k "
                         f"({MIN_RECORD_LENGTH_DEFAULT} when absent)")
+    p.add_argument("--windows", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-fasta: every WINDOW of --window-length bases of a record, one every --window-step "
+                        "bases, is a sample of its own, `<file sample>__<id>__<start>-<end>` (where along a chromosome a "
+                        "foreign stretch lies; fixed-length pieces to train on; no partial windows; rule: "
+                        "INTEGRATION.md, \"--from-fasta --windows\")")
+    p.add_argument("--window-length", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help=f"with --from-fasta --windows: bases of a window, 100 <= N < 2^31 ({WINDOW_LENGTH_DEFAULT} when absent)")
+    p.add_argument("--window-step", type=int, default=argparse.SUPPRESS, metavar="S",
+                   help="with --from-fasta --windows: bases from one window's start to the next, k <= S <= N, a divisor of N "
+                        "with N / S <= 64 (N when absent: windows side by side)")
+
+
+def window_options(args):
+    """fasta_to_images' / fasta_to_query's options of `--windows`, {} without the flag."""
+    if not getattr(args, "windows", False):
+        return {}
+    n = getattr(args, "window_length", WINDOW_LENGTH_DEFAULT)
+    return dict(windows=True, window_length=n, window_step=getattr(args, "window_step", n))
 
 
 ADAPTER_FLAGS = (("detect_adapters", "--detect-adapters"), ("adapter_sequence", "--adapter-sequence"),
@@ -252,7 +271,8 @@ def parse_args(argv=None):
             if getattr(args, name, False):
                 parser.error(f"--from-fasta: not with {flag}")
     if args.command in ("image", "query"):
-        for name, flag in (("per_record", "--per-record"), ("min_record_length", "--min-record-length")):
+        for name, flag in (("per_record", "--per-record"), ("min_record_length", "--min-record-length"), ("windows", "--windows"),
+                           ("window_length", "--window-length"), ("window_step", "--window-step")):
             if hasattr(args, name) and not getattr(args, "from_fasta", False):
                 parser.error(f"{flag}: only with --from-fasta")
         if hasattr(args, "min_record_length") and not getattr(args, "per_record", False):
@@ -261,6 +281,18 @@ def parse_args(argv=None):
             parser.error("--per-record: not with --fragments")
         if hasattr(args, "min_record_length") and args.min_record_length < args.kmer_size:
             parser.error("--min-record-length: at least the k-mer size")
+        for name, flag in (("window_length", "--window-length"), ("window_step", "--window-step")):
+            if hasattr(args, name) and not getattr(args, "windows", False):
+                parser.error(f"{flag}: only with --windows")
+        if getattr(args, "windows", False):
+            for name, flag in (("fragments", "--fragments"), ("per_record", "--per-record")):
+                if getattr(args, name, False):
+                    parser.error(f"--windows: not with {flag}")
+            from .fasta import window_limits
+            opts = window_options(args)
+            why = window_limits(opts["window_length"], opts["window_step"], args.kmer_size)
+            if why:
+                parser.error(f"--window-length, --window-step: {why}")
     if args.command == "image":
         for name, flag in (("fragments", "--fragments"), ("fragment_length", "--fragment-length")):
             if hasattr(args, name) and not getattr(args, "from_fasta", False):
@@ -448,10 +480,12 @@ def run_query(args):
                 if getattr(args, "per_record", False):
                     record_opts = dict(per_record=True, origin=origin,
                                        min_record_length=getattr(args, "min_record_length", MIN_RECORD_LENGTH_DEFAULT))
+                if getattr(args, "windows", False):
+                    record_opts = dict(origin=origin, **window_options(args))
                 found = fasta_to_query([(s, inputs[i]) for i, s in wanted], engine=eng, k=args.kmer_size,
                                        mapping_code=args.kmer_mapping, io_threads=io_threads_per_rank(args.n_threads),
                                        **record_opts)
-                if record_opts:   # a row per record, in the order of the files and of the records within each
+                if record_opts:   # a row per record (or window), in the order of the files and of the records within each
                     of_file = {s: [] for _, s in wanted}
                     for rs in found:
                         of_file[origin[rs]].append(rs)
@@ -648,6 +682,11 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
         from .fasta import RecordLabels
         labels = RecordLabels(labels, samples)
         ladder = dict(per_record=True, min_record_length=getattr(args, "min_record_length", MIN_RECORD_LENGTH_DEFAULT))
+    if getattr(args, "windows", False):   # a label by window sample first, then by record sample, then by the sample of its file
+        from .fasta import RecordLabels
+        labels = RecordLabels(labels, samples, windows=True)
+        ladder = window_options(args)
+        per_record = True   # (a row per imaged window, as per imaged record)
     if getattr(args, "fragments", False):   # -m, -M and -R as for --from-clean
         ladder = dict(fragments=True, fragment_length=getattr(args, "fragment_length", FRAGMENT_LENGTH_DEFAULT),
                       min_bp=parse_size(args.min_bp), max_bp=max_bp_of(args), seeds=draw_seeds(samples, args.seed))
@@ -725,7 +764,7 @@ def finish_image_job(args, outdir, rank, world, per_sample, error, samples, labe
         try:
             rows = [OrderedDict([("sample", s)] + list(v.items())) for s, v in merged.items()]
             pd.DataFrame(rows).to_csv(args.stats_file, index=False)
-            if samples is None:   # `--from-fasta --per-record`: one row per imaged record
+            if samples is None:   # `--from-fasta --per-record`, `--windows`: one row per imaged record or window
                 samples = [s for s, v in merged.items() if "failed_step" not in v]
             if args.label_table and not errors:                               # image.py:1172-1185
                 # (a sample of another rank whose figure only travelled with the stats: --from-raw computes it there)

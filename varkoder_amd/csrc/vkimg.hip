@@ -28,6 +28,7 @@
 //   vk_remap_kernel / vk_preprocess_kernel: `convert`'s remap and the input side of `query`.
 //   vk_fa_*_kernel (vk_fasta.h): the count straight from FASTA text (`--from-fasta`): cut by bytes, header state by a scan.
 //   vk_far_*_kernel (vk_fasta_records.h): the same per FASTA record (`--per-record`): record ordinal by a second scan.
+//   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +61,7 @@
 #include "vk_fasta.h"
 #include "vk_fasta_ladder.h"
 #include "vk_fasta_records.h"
+#include "vk_fasta_windows.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -145,6 +147,8 @@ struct vk_ctx {
     bool no_read_index = false;    // VKIMG_NO_READ_INDEX=1: subsampled counts always stream the text, whatever index the context holds (tests, A/B timing)
     uint8_t* d_fasta = nullptr;    // vk_count_fasta_device: descriptors | unit summaries | the state that enters every unit
     size_t fasta_cap = 0;
+    uint8_t* d_fawin = nullptr;    // vk_count_fasta_windows_device: ordinal index | record table | tile rows (beside d_fasta, which far_prepare carves)
+    size_t fawin_cap = 0;
     uint32_t fasta_unit_bytes = 0; // VKIMG_FASTA_UNIT_BYTES=n: bytes of a unit of the FASTA count, a multiple of 64 up to 16384, one unit per workgroup (tests: many seams in little text; 0 = 16384, 32 units per workgroup)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
@@ -677,7 +681,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -2715,6 +2719,72 @@ int vk_count_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64
             return VK_OK;
         });
         if (rc) return rc;
+    }
+    return VK_OK;
+}
+
+int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                                  int k, const uint64_t* rec_first, const uint64_t* d_rec_bases, const uint64_t* d_win_first,
+                                  uint32_t win_len, uint32_t win_step, uint64_t row_lo, uint32_t nrows, uint32_t tile_rows,
+                                  uint32_t* d_hist) {
+    if (!ctx || !offsets || !lengths || !rec_first || !d_rec_bases || !d_win_first || !d_hist || k < 5 || k > 9) return VK_EINVAL;
+    if (win_step < static_cast<uint32_t>(k) || win_len >= (1u << 31) || win_len < win_step || win_len % win_step != 0) return VK_EINVAL;
+    const uint32_t steps = win_len / win_step;
+    if (steps > kFaMaxSteps || nrows == 0 || (steps > 1 && tile_rows == 0)) return VK_EINVAL;
+    if (!far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
+    if (nsamples && (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0)) return VK_EINVAL;
+    for (uint32_t i = 0; i < nsamples; ++i)
+        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    const uint64_t sum_wgs = steps > 1 ? static_cast<uint64_t>(tile_rows) * (ncode / kFawSumCodes) : 0;
+    if (sum_wgs >= (1ull << 31)) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nrows * ncode * sizeof(uint32_t), ctx->stream));
+    const uint64_t total = nsamples ? rec_first[nsamples] : 0;
+    if (total == 0) return VK_OK;
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    FarState st;
+    int rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
+    if (rc) return rc;
+    const FaPlan& pl = st.pl;
+    if (pl.nwg == 0) return VK_OK;
+    const uint32_t lanes = pl.unit / kFaLaneBytes;
+    uint32_t *d_lane = nullptr, *d_used = nullptr, *d_tiles = nullptr;
+    unsigned long long *d_unit_ord = nullptr, *d_bases = nullptr;
+    FawRec* d_recs = nullptr;
+    rc = ws_carve(ctx, &ctx->d_fawin, &ctx->fawin_cap, [&](WsTake& take) {
+        take(d_lane, pl.nunits * lanes + 1);   // the index: a word per lane of text, 1/16 of it
+        take(d_unit_ord, pl.nunits + 1);
+        take(d_bases, nsamples);
+        take(d_recs, total + 1);
+        take(d_used, 1);
+        take(d_tiles, steps > 1 ? tile_rows * ncode : 1);
+    });
+    if (rc) return rc;
+    if (steps > 1) VK_HIP(ctx, hipMemsetAsync(d_tiles, 0, tile_rows * ncode * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(vk_fa_ord_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m, st.d_carry,
+                       d_lane, d_unit_ord);
+    VK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(vk_fa_ordscan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, st.m, d_unit_ord, d_bases);
+    VK_HIP(ctx, hipGetLastError());
+    const uint32_t cap = steps > 1 ? tile_rows : nrows;
+    hipLaunchKernelGGL(vk_faw_plan_kernel, dim3(1), dim3(kFaThreads), 0, ctx->stream, reinterpret_cast<const unsigned long long*>(d_rec_bases),
+                       reinterpret_cast<const unsigned long long*>(d_win_first), total, win_len, win_step, row_lo, nrows, cap, d_recs, d_used);
+    VK_HIP(ctx, hipGetLastError());
+    rc = with_k(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL(vk_faw_count_kernel<K>, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m,
+                           st.d_carry, st.d_uhdr, st.d_nrec, FaRecs{st.d_rec_first}, d_lane, d_unit_ord, d_recs, win_step,
+                           steps > 1 ? d_tiles : d_hist, cap);
+        VK_HIP(ctx, hipGetLastError());
+        return VK_OK;
+    });
+    if (rc) return rc;
+    if (steps > 1) {
+        hipLaunchKernelGGL(vk_faw_sum_kernel, dim3(static_cast<uint32_t>(sum_wgs)), dim3(kFaThreads), 0, ctx->stream, d_recs,
+                           reinterpret_cast<const unsigned long long*>(d_win_first), total, d_used, d_tiles, static_cast<uint32_t>(ncode),
+                           steps, row_lo, nrows, d_hist);
+        VK_HIP(ctx, hipGetLastError());
     }
     return VK_OK;
 }

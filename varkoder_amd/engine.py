@@ -627,6 +627,37 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_fasta_records_device")
         return hist
 
+    def count_fasta_windows(self, fasta, offsets, lengths, rec_first, rec_bases, win_first, win_len, win_step, row_lo, nrows,
+                            tile_rows=0, hist=None):
+        """One histogram per window of the selected records (vk_count_fasta_windows_device; the rule: INTEGRATION.md,
+        "--from-fasta --windows"): rec_bases uint64 [total] as fasta_records gives them, win_first uint64 [total] = the row
+        of every record's window 0 or VK_FA_NO_WINDOW (both on the host or already on the device as int64 tensors).  The
+        rows of [row_lo, row_lo + nrows) are counted; tile_rows: with win_step < win_len, the tile rows the range needs
+        (fasta.window_plan states them).  Returns hist [nrows, 4^k] on the device."""
+        torch = _torch()
+        offs, lens = self._desc(offsets, lengths)
+        n = len(offs)
+        rec_first = np.ascontiguousarray(rec_first, dtype=np.uint64)
+        if rec_first.shape != (n + 1,):
+            raise ValueError("rec_first must hold n + 1 prefix sums")
+        total = int(rec_first[n])
+
+        def on_device(a, what):
+            if not isinstance(a, torch.Tensor):
+                a = np.ascontiguousarray(a, dtype=np.uint64)
+                a = torch.from_numpy(a.view(np.int64) if a.size else np.zeros(1, dtype=np.int64)).to(self.device)
+            if a.dtype != torch.int64 or a.numel() < max(total, 1):
+                raise ValueError(f"{what} must hold one 64-bit entry per record")
+            return a
+        d_bases, d_first = on_device(rec_bases, "rec_bases"), on_device(win_first, "win_first")
+        if hist is None:
+            hist = torch.empty((int(nrows), self.ncode), dtype=torch.int32, device=self.device)
+        st = self.L.vk_count_fasta_windows_device(self.ctx, self._ptr(fasta), _u64(offs), _u64(lens), n, self.k, _u64(rec_first),
+                                                  self._ptr(d_bases), self._ptr(d_first), int(win_len), int(win_step), int(row_lo),
+                                                  int(nrows), int(tile_rows), self._ptr(hist))
+        _capi.check(self.ctx, st, "vk_count_fasta_windows_device")
+        return hist
+
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):
         """K1 over a pseudo-random subset of each sample's reads (vk_count_sampled_device):

@@ -11,7 +11,13 @@ fasta_to_images(fragments=True) images every step as `<sample>@<bp>K+<mapping>+k
 
 `image / query --from-fasta --per-record` make every record of a file a sample of its own (the rule: INTEGRATION.md,
 "--from-fasta --per-record"): ImageEngine.fasta_records gives the record table of a batch, record_names the samples'
-names, record_plan the calls of ImageEngine.count_fasta_records, a row per selected record."""
+names, record_plan the calls of ImageEngine.count_fasta_records, a row per selected record.
+
+`image / query --from-fasta --windows` make every window of `--window-length` bases of a record, one every
+`--window-step` bases, a sample of its own (the rule: INTEGRATION.md, "--from-fasta --windows"): window_counts gives the
+windows of every record, window_names their sample names, window_plan the first row of every record and the row ranges
+of the ImageEngine.count_fasta_windows calls."""
+import re
 import time
 from collections import OrderedDict
 from pathlib import Path
@@ -141,21 +147,114 @@ def record_plan(bases, min_len, hist_bytes=RECORD_HIST_BYTES, ncode=4 ** 7):
     return [chosen[at:at + per_call] for at in range(0, len(chosen), per_call)]
 
 
+WINDOW_HIST_BYTES = 1 << 30    # histograms of one count_fasta_windows call, tile rows included
+NO_WINDOW = 0xFFFFFFFFFFFFFFFF  # VK_FA_NO_WINDOW
+MAX_WINDOW_STEPS = 64           # window length / window step
+_WINDOW_NAME = re.compile(r"(.+)__[0-9]+-[0-9]+$")
+
+
+def window_limits(n, s, k):
+    """Why (n, s) is no window length and step for k-mers of k bases (a sentence), or None: 100 <= n < 2^31 for the
+    command line, k <= s <= n, s | n, n / s <= 64 (vk_count_fasta_windows_device's conditions)."""
+    if not 100 <= n < 2 ** 31:
+        return "the window length must be at least 100 and below 2^31"
+    if not k <= s <= n:
+        return f"the window step must lie between k = {k} and the window length"
+    if n % s:
+        return "the window length must be a multiple of the window step"
+    if n // s > MAX_WINDOW_STEPS:
+        return f"the window length must be at most {MAX_WINDOW_STEPS} window steps"
+    return None
+
+
+def window_counts(bases, n, s):
+    """The windows of records of `bases` joined bytes: window w covers [w * s, w * s + n) and exists iff it lies within
+    the record; no partial windows (int64 array; a negative entry, a passed-over record, has none)."""
+    b = np.asarray(bases).astype(np.int64)
+    return np.where(b >= n, (b - n) // s + 1, 0)
+
+
+def window_name(record_sample, n, s, w):
+    """`<record sample>__<start>-<end>` of a record's window w: 1-based, inclusive, decimal."""
+    return f"{record_sample}__{w * s + 1}-{w * s + n}"
+
+
+def window_names(record_sample, n, s, nwin):
+    return [window_name(record_sample, n, s, w) for w in range(int(nwin))]
+
+
+def window_plan(bases, n, s, hist_bytes=WINDOW_HIST_BYTES, ncode=4 ** 7):
+    """The count_fasta_windows calls of a batch: (win_first, ranges).  Every record with bases >= n (indices into
+    `bases`, the batch's record table; -1 marks a record to pass over, a duplicate) gets consecutive rows, one per
+    window, from win_first[g] on (uint64; NO_WINDOW for the others).  ranges = [(row_lo, nrows, tile_rows)] cuts the
+    rows into consecutive ranges whose histograms (4 * ncode bytes a row) fit in hist_bytes; with s < n that includes
+    the tile rows a range needs: per record with a row in it, its rows there + n / s - 1 (0 when s == n).  A range may
+    begin and end inside a record; a single row always fits."""
+    m = n // s
+    counts = window_counts(bases, n, s)
+    win_first = np.full(len(counts), NO_WINDOW, dtype=np.uint64)
+    ends = np.cumsum(counts)
+    win_first[counts > 0] = (ends - counts)[counts > 0].astype(np.uint64)
+    budget = max(1, int(hist_bytes) // (4 * int(ncode)))
+    ranges, lo, nrows, tiles = [], 0, 0, 0
+    for c in counts[counts > 0]:
+        left = int(c)
+        while left:
+            room = budget - nrows - tiles
+            fit = room if m == 1 else (room - (m - 1)) // 2   # a row of a record new to the range: itself, its tile, m - 1 more
+            if fit <= 0 and nrows:
+                ranges.append((lo, nrows, tiles))
+                lo, nrows, tiles = lo + nrows, 0, 0
+                continue
+            take = min(left, max(fit, 1))
+            nrows += take
+            tiles += take + m - 1 if m > 1 else 0
+            left -= take
+    if nrows:
+        ranges.append((lo, nrows, tiles))
+    return win_first, ranges
+
+
 class RecordLabels:
     """--labels-csv for records: a record's sample name first, then the sample of its file (`<file sample>__<id>`; the
-    longest file sample that fits), so that a collection file labelled once labels all of its records."""
+    longest file sample that fits), so that a collection file labelled once labels all of its records.  windows: the
+    samples are windows (`<record sample>__<start>-<end>`); between the two, the window's record sample is looked up."""
 
-    def __init__(self, table, file_samples):
+    def __init__(self, table, file_samples, windows=False):
         self.table = dict(table or {})
         self.file_samples = sorted(file_samples, key=len, reverse=True)
+        self.windows = windows
 
     def get(self, sample, default=None):
         if sample in self.table:
             return self.table[sample]
+        if self.windows:
+            record = _WINDOW_NAME.match(sample)
+            if record and record.group(1) in self.table:
+                return self.table[record.group(1)]
         for fs in self.file_samples:
             if sample.startswith(fs + "__") and fs in self.table:
                 return self.table[fs]
         return default
+
+
+def _record_table(eng, batch, pool):
+    """A batch of files in HBM and its record table: ((text, offsets, lengths), status, rec_first, bases, samples, dups,
+    wanted) -- the files' status words, prefix sums of their record counts, bases and sample name of every record, the
+    indices of the duplicates, and the bases again with -1 for a duplicate (what record_plan and window_plan take)."""
+    dev, offs, lens = eng.upload_files(batch, pool)
+    unread = getattr(eng, "last_upload_status", None)
+    rec_first, _, bases, names, status = eng.fasta_records(dev, offs, lens)
+    status = status.copy()
+    if unread is not None:
+        status[unread != 0] |= 0x100   # (a file that could not be read or inflated is not an empty sample)
+    samples, dups = [], set()
+    for j, f in enumerate(batch):
+        a, b = int(rec_first[j]), int(rec_first[j + 1])
+        got, dup = record_names(sample_of(f), names[a:b])
+        samples += got
+        dups.update(a + i for i in dup)
+    return (dev, offs, lens), status, rec_first, bases, samples, dups, [-1 if g in dups else int(b) for g, b in enumerate(bases)]
 
 
 def _record_batches(eng, files, pool, batch_bytes, min_len):
@@ -167,19 +266,7 @@ def _record_batches(eng, files, pool, batch_bytes, min_len):
     with hist None.  Records shorter than min_len and duplicates get no row."""
     import torch
     for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
-        dev, offs, lens = eng.upload_files(batch, pool)
-        unread = getattr(eng, "last_upload_status", None)
-        rec_first, _, bases, names, status = eng.fasta_records(dev, offs, lens)
-        status = status.copy()
-        if unread is not None:
-            status[unread != 0] |= 0x100   # (a file that could not be read or inflated is not an empty sample)
-        samples, dups = [], set()
-        for j, f in enumerate(batch):
-            a, b = int(rec_first[j]), int(rec_first[j + 1])
-            got, dup = record_names(sample_of(f), names[a:b])
-            samples += got
-            dups.update(a + i for i in dup)
-        wanted = [-1 if g in dups else int(b) for g, b in enumerate(bases)]
+        (dev, offs, lens), status, rec_first, bases, samples, dups, wanted = _record_table(eng, batch, pool)
         calls = record_plan(wanted, min_len, RECORD_HIST_BYTES, eng.ncode) or [[]]
         for n, call in enumerate(calls):
             hist = None
@@ -192,9 +279,10 @@ def _record_batches(eng, files, pool, batch_bytes, min_len):
                    time.perf_counter())
 
 
-def _record_reports(batch, status, rec_first, bases, samples, dups, min_len, stats=None):
+def _record_reports(batch, status, rec_first, bases, samples, dups, min_len, stats=None, step=None):
     """What a batch's first yield says on stderr, per file: a file without records, the duplicates (each with a stats
-    row `<name>#<ordinal + 1>`), how many records were passed over as too short."""
+    row `<name>#<ordinal + 1>`), how many records were passed over as too short.  step: the records are cut into
+    windows of min_len bases every `step`; the line also says how many bases lie behind the records' last windows."""
     for j, f in enumerate(batch):
         a, b = int(rec_first[j]), int(rec_first[j + 1])
         if status[j] or a == b:
@@ -203,13 +291,41 @@ def _record_reports(batch, status, rec_first, bases, samples, dups, min_len, sta
                 stats.setdefault(sample_of(f), OrderedDict())["failed_step"] = "image"
             continue
         short = sum(1 for g in range(a, b) if int(bases[g]) < min_len)
-        if short:
+        if step is not None:
+            behind = sum(int(bases[g]) - (int(c) - 1) * step - min_len
+                         for g, c in zip(range(a, b), window_counts(bases[a:b], min_len, step)) if c)
+            eprint(f"{f}: {short} of {b - a} records shorter than {min_len} bases passed over, "
+                   f"{behind} bases behind the last windows of the others")
+        elif short:
             eprint(f"{f}: {short} of {b - a} records shorter than {min_len} bases passed over")
         for g in range(a, b):
             if g in dups and int(bases[g]) >= min_len:
                 eprint("DUPLICATE RECORD ID, SKIPPING:", f"{samples[g]} (record {g - a + 1} of {f})")
                 if stats is not None:
                     stats.setdefault(f"{samples[g]}#{g - a + 1}", OrderedDict())["failed_step"] = "image"
+
+
+def _window_batches(eng, files, pool, batch_bytes, n, s):
+    """Per batch of files, per row range: (batch, first, status, rec_first, bases, samples, dups, rows, hist, t0, t1) as
+    _record_batches, with rows = [(record, window, its row in hist)] in row order.  One yield per range of window_plan,
+    `first` on a batch's first; a batch without a window yields once with hist None.  Records shorter than n and
+    duplicates get no windows."""
+    import torch
+    for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
+        (dev, offs, lens), status, rec_first, bases, samples, dups, wanted = _record_table(eng, batch, pool)
+        win_first, ranges = window_plan(wanted, n, s, WINDOW_HIST_BYTES, eng.ncode)
+        chosen = np.nonzero(win_first != NO_WINDOW)[0]
+        d_bases = torch.from_numpy(np.ascontiguousarray(bases).view(np.int64) if len(bases) else np.zeros(1, dtype=np.int64)).to(eng.device)
+        d_first = torch.from_numpy(win_first.view(np.int64) if len(bases) else np.zeros(1, dtype=np.int64)).to(eng.device)
+        for i, (lo, nrows, tile_rows) in enumerate(ranges or [None]):
+            hist, rows = None, []
+            if ranges:
+                hist = eng.count_fasta_windows(dev, offs, lens, rec_first, d_bases, d_first, n, s, lo, nrows, tile_rows)
+                torch.cuda.current_stream(eng.device).synchronize()   # (the time after the count is the batch's)
+                rr = np.arange(lo, lo + nrows, dtype=np.uint64)
+                gs = chosen[np.searchsorted(win_first[chosen], rr, side="right") - 1]
+                rows = [(int(g), int(r - win_first[g]), j) for j, (g, r) in enumerate(zip(gs, rr))]
+            yield batch, i == 0, status, rec_first, bases, samples, dups, rows, hist, t0, time.perf_counter()
 
 
 def _counted(eng, files, pool, batch_bytes):
@@ -226,7 +342,8 @@ def _counted(eng, files, pool, batch_bytes):
 
 def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, fragments=False, fragment_length=150,
-                    min_bp=50000, max_bp=None, seeds=None, per_record=False, min_record_length=1000):
+                    min_bp=50000, max_bp=None, seeds=None, per_record=False, min_record_length=1000, windows=False,
+                    window_length=10000, window_step=None):
     """This rank's share of FASTA `files`, each imaged whole.  Returns {sample: OrderedDict(stats)} with the reference's
     keys `<k>mer_counting_time` and `k<k>_img_time`, or `failed_step` for a sample that does not begin with '>', holds
     no base, or could not be read.
@@ -238,7 +355,11 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
     per_record: every record of min_record_length bases or more is a sample of its own (record_names; the rule:
     INTEGRATION.md, "--from-fasta --per-record"), imaged as `image_name(<record sample>, its bases, k, mapping)`; the
     stats are keyed by record sample, `<k>mer_counting_time` is the batch's upload plus count time shared over its
-    imaged records, and a record with a row but no non-zero bin gets `failed_step` = "image"."""
+    imaged records, and a record with a row but no non-zero bin gets `failed_step` = "image".
+
+    windows: every window of window_length bases of a record, one every window_step (default: window_length), is a
+    sample of its own (window_names; the rule: INTEGRATION.md, "--from-fasta --windows"), imaged as
+    `image_name(<window sample>, window_length, k, mapping)`; stats and failures as for per_record, per window."""
     files = [Path(f) for f in files]
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded)
@@ -251,7 +372,10 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
                 _fragment_images(eng, pool, batch, t0, sink, stats, seeds or {}, fragment_length, min_bp, max_bp, verbose)
         if per_record:
             _record_images(eng, pool, mine, batch_bytes or DEFAULT_BATCH_BYTES, min_record_length, sink, stats, verbose)
-        whole = () if fragments or per_record else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
+        if windows:
+            _window_images(eng, pool, mine, batch_bytes or DEFAULT_BATCH_BYTES, window_length, window_step or window_length, sink, stats,
+                           verbose)
+        whole = () if fragments or per_record or windows else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
         for batch, hist, st, bases, t0, t1 in whole:
             nz = (hist != 0).any(dim=1).cpu().numpy()
             imgs = eng.images(hist).cpu().numpy()
@@ -291,6 +415,30 @@ def _record_images(eng, pool, files, batch_bytes, min_len, sink, stats, verbose)
             sink.submit(samples[g], samples[g], image_name(samples[g], int(bases[g]), k, sink.mapping_code), imgs[row])
         if verbose:
             eprint(f"batch of {len(batch)} FASTA files, {len(rows)} records: upload+count {t1 - t0:.3f}s")
+
+
+def _window_images(eng, pool, files, batch_bytes, n, s, sink, stats, verbose):
+    """fasta_to_images(windows=True): the record table and the window rows of every batch, range by range, the images."""
+    k = sink.k
+    for batch, first, st, rec_first, bases, samples, dups, rows, hist, t0, t1 in _window_batches(eng, files, pool, batch_bytes, n, s):
+        if first:
+            _record_reports(batch, st, rec_first, bases, samples, dups, n, stats, step=s)
+        if hist is None:
+            continue
+        nz = (hist != 0).any(dim=1).cpu().numpy()
+        imgs = eng.images(hist).cpu().numpy()
+        imaged = max(1, int(nz.sum()))
+        for g, w, row in rows:
+            name = window_name(samples[g], n, s, w)
+            stt = stats.setdefault(name, OrderedDict())
+            if not nz[row]:
+                eprint("K-MER COUNTING FAIL, SKIPPING WINDOW:", name)
+                stt["failed_step"] = "image"
+                continue
+            stt[str(k) + "mer_counting_time"] = (t1 - t0) / imaged
+            sink.submit(name, name, image_name(name, n, k, sink.mapping_code), imgs[row])
+        if verbose:
+            eprint(f"batch of {len(batch)} FASTA files, {len(rows)} windows: upload+count {t1 - t0:.3f}s")
 
 
 def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp, max_bp, verbose):
@@ -335,15 +483,37 @@ def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp,
 
 
 def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batch_bytes=None, io_threads=8, per_record=False,
-                   min_record_length=1000, origin=None):
+                   min_record_length=1000, origin=None, windows=False, window_length=10000, window_step=None):
     """{sample: (bp, histogram uint32[4^k] on the device, 0)} for samples = [(sample, its FASTA file)] (this rank's
     share): what pipeline.clean_to_query returns for cleaned reads.  A sample that fails is reported and left out.
 
     per_record: the same tuples keyed by record sample, one per record of min_record_length bases or more
-    (fasta_to_images' rule); origin (a dict) receives {record sample: the sample of its file}."""
+    (fasta_to_images' rule); origin (a dict) receives {record sample: the sample of its file}.
+
+    windows: the same keyed by window sample, one per window of window_length bases every window_step, bp =
+    window_length, in the order of the files, their records and the windows."""
     by_file = {Path(f): s for s, f in samples}
     found = OrderedDict()
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
+        if windows:
+            n, s = window_length, window_step or window_length
+            for batch, first, st, rec_first, bases, names, dups, rows, hist, _, _ in _window_batches(
+                    eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES, n, s):
+                if first:
+                    _record_reports(batch, st, rec_first, bases, names, dups, n, step=s)
+                if hist is None:
+                    continue
+                nz = (hist != 0).any(dim=1).cpu().numpy()
+                file_of = np.searchsorted(rec_first, np.array([g for g, _, _ in rows], dtype=np.uint64), side="right") - 1
+                for (g, w, row), j in zip(rows, file_of):
+                    name = window_name(names[g], n, s, w)
+                    if not nz[row]:
+                        eprint("K-MER COUNTING FAIL, SKIPPING WINDOW:", name)
+                        continue
+                    found[name] = (n, hist[row], 0)
+                    if origin is not None:
+                        origin[name] = by_file[batch[int(j)]]
+            return found
         if per_record:
             for batch, first, st, rec_first, bases, names, dups, rows, hist, _, _ in _record_batches(
                     eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES, min_record_length):
