@@ -469,6 +469,51 @@ int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64
                                   const uint64_t* d_win_first, uint32_t win_len, uint32_t win_step, uint64_t row_lo,
                                   uint32_t nrows, uint32_t tile_rows, uint32_t* d_hist);
 
+#define VK_BAM_BAD_RECORD 1u   /* a record's block_size is too small for its fields, its name is empty or not NUL-terminated */
+#define VK_BAM_TRUNCATED 2u    /* a record runs past the file's end (or first_record lies behind it) */
+#define VK_BAM_ALL 0u          /* a stream's `select`: every read of the file ... */
+#define VK_BAM_READ1 1u        /* ... those with flag & 0xC1 == 0x41 (paired, first of the pair) ... */
+#define VK_BAM_READ2 2u        /* ... with flag & 0xC1 == 0x81 (paired, second of the pair) ... */
+#define VK_BAM_SINGLE 3u       /* ... every other read */
+#define VK_BAM_NO_GUESS 1u     /* `flags`: no segment guesses its entry, the whole chain of records is walked in order */
+
+/* Replaces: `samtools fastq` on the host before varKoder sees a read (varKoder has no BAM input; the rule is this
+ * project's: INTEGRATION.md, "--from-bam: the rule"; tests/bam_ref.py) -- the framing of BAM files whose INFLATED bytes
+ * lie in HBM (a .bam is BGZF: vk_inflate_device).  File i is d_bam + offsets[i], lengths[i] bytes (no alignment is asked:
+ * every field is read by bytes); first_record[i] = the offset of its first record and n_ref[i] its reference count, as
+ * the caller parsed them from the header (SAM spec 4.2: magic, l_text, text, n_ref, references).  A record (SAM spec
+ * 4.2, "alignments") is a block_size word and block_size bytes; it is a read when l_seq > 0 and flag & exclude == 0
+ * (flag: SAM spec 1.4.2), of l_read_name + 2 * l_seq + 5 bytes of FASTQ text.  Stream s takes the reads
+ * stream_select[s] (VK_BAM_*) of file stream_file[s]; any number of streams may name a file.  out_records[nstreams],
+ * out_bytes[nstreams] (host) = the reads and text bytes of every stream; status[nfiles] (host) = 0 or VK_BAM_BAD_RECORD /
+ * VK_BAM_TRUNCATED, and the streams of such a file have neither reads nor bytes.  The files are cut into segments of
+ * VKIMG_BAM_SEG_BYTES (read when the context is made; 64 to 65536, the default), every segment guesses where its first record starts and the
+ * guesses are verified in order (vk_bam.h): the result does not depend on them, nor on VK_BAM_NO_GUESS in `flags`.
+ * Nothing is read outside a file's bytes.  VK_EINVAL, before anything is launched, for a null pointer, a stream_file of
+ * nfiles or more, a stream_select above VK_BAM_SINGLE or flags other than VK_BAM_NO_GUESS.  Synchronises. */
+int vk_bam_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                        const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file,
+                        const uint32_t* stream_select, uint32_t nstreams, uint32_t exclude, uint32_t flags,
+                        uint64_t* out_records, uint64_t* out_bytes, uint32_t* status);
+
+/* Replaces: `samtools fastq` (as above) -- the text.  The inputs are vk_bam_frame_device's; stream s is written to d_out +
+ * out_offsets[s], at most out_caps[s] bytes (host arrays; the caller sizes them from out_bytes).  A read's text (SAM spec
+ * 4.2 for the fields, 4.2.3 / 4.2.4 for bases and qualities): '@', read_name without its NUL, '\n', the bases ("=ACMGRSVTWYHKDBN",
+ * '=' written as N), "\n+\n", min(q, 93) + 33 per quality -- 'I' for every base when the first quality byte is 0xFF --
+ * and '\n'; with flag & 0x10 the bases are reverse-complemented (IUPAC codes included) and the qualities reversed.
+ * out_lengths[nstreams], status[nfiles] (host) as the framing call's bytes and status.  Nothing is written outside a
+ * stream's slot: a stream whose text does not fit gets none, out_lengths[s] = 0, and the call returns VK_ENOSPC once the
+ * other streams are written.  Synchronises. */
+int vk_bam_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                        const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file,
+                        const uint32_t* stream_select, uint32_t nstreams, uint32_t exclude, uint32_t flags, void* d_out,
+                        const uint64_t* out_offsets, const uint64_t* out_caps, uint64_t* out_lengths, uint32_t* status);
+
+/* Introspection (tests, tools/bam_time.py): of the last vk_bam_frame_device / vk_bam_fastq_device call, the segments its
+ * files (SAM spec 4.2) were cut into and how many of them the link pass walked again because their guess was wrong or
+ * missing. */
+int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -16,6 +16,9 @@ VK_CL_NSTAT = 202
 VK_CL_MAX_ADAPTER, VK_CL_DETECT_RECORDS = 64, 262144
 VK_FA_NAME_BYTES, VK_FA_NO_SLOT = 128, 0xFFFFFFFF
 VK_FA_NO_WINDOW = 0xFFFFFFFFFFFFFFFF
+VK_BAM_BAD_RECORD, VK_BAM_TRUNCATED = 1, 2
+VK_BAM_ALL, VK_BAM_READ1, VK_BAM_READ2, VK_BAM_SINGLE = 0, 1, 2, 3
+VK_BAM_NO_GUESS = 1
 VK_GZ_BAD_HEADER, VK_GZ_BAD_DATA, VK_GZ_TRUNCATED, VK_GZ_OVERFLOW, VK_GZ_BAD_SIZE, VK_GZ_BAD_CRC = 1, 2, 4, 8, 16, 32
 
 # every symbol include/vkimg.h declares
@@ -28,7 +31,8 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_clean_detect_device", "vk_clean_adapters_device", "vk_clean_heads_device", "vk_ladder_emit_workspace_size",
            "vk_ladder_emit_device", "vk_train_batch_device", "vk_deflate_bound", "vk_deflate_workspace_size", "vk_deflate_device",
            "vk_count_fasta_device", "vk_count_fasta_host", "vk_count_fasta_sampled_device", "vk_fasta_records_count_device",
-           "vk_fasta_records_device", "vk_count_fasta_records_device", "vk_count_fasta_windows_device")
+           "vk_fasta_records_device", "vk_count_fasta_records_device", "vk_count_fasta_windows_device", "vk_bam_frame_device",
+           "vk_bam_fastq_device", "vk_last_bam_frame")
 
 _lib = None
 
@@ -102,6 +106,12 @@ def lib():
     L.vk_count_fasta_records_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, u64p, vp, C.c_uint32, vp]
     L.vk_count_fasta_windows_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, u64p, vp, vp, C.c_uint32, C.c_uint32,
                                                 C.c_uint64, C.c_uint32, C.c_uint32, vp]
+    i32p = C.POINTER(C.c_int32)
+    L.vk_bam_frame_device.argtypes = [vp, vp, u64p, u64p, u64p, i32p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      u64p, u64p, u32p]
+    L.vk_bam_fastq_device.argtypes = [vp, vp, u64p, u64p, u64p, i32p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      vp, u64p, u64p, u64p, u32p]
+    L.vk_last_bam_frame.argtypes = [vp, u64p, u64p]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]
     L.vk_preprocess_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float, vp]

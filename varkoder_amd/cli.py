@@ -92,6 +92,11 @@ def setup_parser():
                        help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`: assemblies, contigs, "
                             "organelle genomes): each is counted whole on the GPU and becomes one image "
                             "`<sample>@<bp>K+<mapping>+k<k>.png`, bp = its bases (rule: INTEGRATION.md, \"--from-fasta\")")
+    entry.add_argument("--from-bam", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                       help="input is a folder of BAM files (`<sample>.bam`, unaligned or aligned): the records become "
+                            "FASTQ text on the GPU and the run goes on as --from-raw does, with its flags (rule: "
+                            "INTEGRATION.md, \"--from-bam: the rule\")")
+    add_bam_flags(p)
     p.add_argument("--fragments", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-fasta: image every sample as the 1-2-5 ladder of subsamples between --min-bp and "
                         "--max-bp, like --from-clean does for reads, each step drawn from fragments of --fragment-length "
@@ -152,6 +157,10 @@ def setup_parser():
     q.add_argument("--from-fasta", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="input is a folder of FASTA files (`<sample>.fa|.fasta|.fna[.gz]`), one sample each: counted whole "
                         "on the GPU, imaged and predicted")
+    q.add_argument("--from-bam", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="input is a folder of BAM files (`<sample>.bam`), one sample each: converted to reads on the GPU, "
+                        "then as --from-raw")
+    add_bam_flags(q)
     add_record_flags(q)
     q.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-raw and -i INT: compress the cleaned reads on the GPU, as BGZF, and copy back the "
@@ -222,6 +231,24 @@ MIN_RECORD_LENGTH_DEFAULT = 1000
 WINDOW_LENGTH_DEFAULT = 10000
 
 
+def add_bam_flags(p):
+    p.add_argument("--bam-pairs", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-bam: a file's first mates (flag & 0xC1 == 0x41), second mates (0x81) and other reads "
+                        "are the R1, R2 and unpaired files of its sample; mates must appear in the same order (unaligned "
+                        "or collated BAMs): a file sorted by coordinate is refused")
+    p.add_argument("--bam-exclude", type=lambda t: int(t, 0), default=argparse.SUPPRESS, metavar="INT",
+                   help="with --from-bam: records with any of these flag bits are passed over (0x900 when absent: "
+                        "secondary and supplementary, as `samtools fastq`; 0xF00 also drops QC-fail and duplicates)")
+
+
+def bam_options(args):
+    """raw_to_images' / raw_to_query's `bam` of `--from-bam`, None without the flag."""
+    if not getattr(args, "from_bam", False):
+        return None
+    from .bam import EXCLUDE_DEFAULT
+    return dict(pairs=getattr(args, "bam_pairs", False), exclude=getattr(args, "bam_exclude", EXCLUDE_DEFAULT))
+
+
 def add_record_flags(p):
     p.add_argument("--per-record", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-fasta: every RECORD of a FASTA file is a sample of its own, `<file sample>__<id>`, id "
@@ -264,6 +291,16 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
+    from_bam = args.command in ("image", "query") and getattr(args, "from_bam", False)
+    if from_bam:   # (image: the entry flags exclude each other in the parser)
+        if args.command == "query" and (args.images or args.from_raw or getattr(args, "from_fasta", False)):
+            parser.error("--from-bam: not with -I/--images, --from-raw or --from-fasta")
+        if hasattr(args, "bam_exclude") and not 0 <= args.bam_exclude <= 0xFFFF:
+            parser.error("--bam-exclude: 0 to 0xFFFF")
+    if args.command in ("image", "query") and not from_bam:
+        for name, flag in (("bam_pairs", "--bam-pairs"), ("bam_exclude", "--bam-exclude")):
+            if hasattr(args, name):
+                parser.error(f"{flag}: only with --from-bam")
     if getattr(args, "from_fasta", False):   # one image per file, nothing written but images: no ladder, no intermediates
         if args.command == "query" and (args.images or args.from_raw):
             parser.error("--from-fasta: not with -I/--images or --from-raw")
@@ -300,19 +337,20 @@ def parse_args(argv=None):
         if hasattr(args, "fragment_length") and not FRAGMENT_LENGTH_MIN <= args.fragment_length <= FRAGMENT_LENGTH_MAX:
             parser.error(f"--fragment-length: {FRAGMENT_LENGTH_MIN} to {FRAGMENT_LENGTH_MAX}")
     if args.command == "image" and getattr(args, "write_splits", False):
-        if not (args.from_raw or args.from_clean):
-            parser.error("--write-splits: only with --from-raw or --from-clean")
+        if not (args.from_raw or args.from_clean or from_bam):
+            parser.error("--write-splits: only with --from-raw or --from-clean (or --from-bam, which runs as --from-raw)")
         if not args.int_folder:
             parser.error("--write-splits: needs -i/--int-folder")
     if args.command in ("image", "query") and getattr(args, "gpu_gzip", False):
         # only where this run writes a .fq.gz: the cleaned reads of --from-raw -i INT, or --write-splits' files
-        if not ((args.from_raw and args.int_folder) or getattr(args, "write_splits", False)):
+        if not (((args.from_raw or from_bam) and args.int_folder) or getattr(args, "write_splits", False)):
             parser.error("--gpu-gzip: only with --from-raw and -i/--int-folder" +
-                         (", or with --write-splits" if args.command == "image" else ""))
+                         (", or with --write-splits" if args.command == "image" else "") +
+                         " (--from-bam counts as --from-raw)")
     if args.command in ("image", "query"):
         given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
-        if given and not args.from_raw:
-            parser.error(f"{', '.join(given)}: only with --from-raw")
+        if given and not (args.from_raw or from_bam):
+            parser.error(f"{', '.join(given)}: only with --from-raw (or --from-bam)")
         if given and args.no_adapter:
             parser.error(f"{', '.join(given)}: not with -a/--no-adapter")
         from .adapters import parse_adapter
@@ -387,7 +425,7 @@ def run_query(args):
     outdir = Path(args.outdir)
     if not args.overwrite and (outdir / "predictions.csv").exists():
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
-    from_raw = getattr(args, "from_raw", False)
+    from_raw = getattr(args, "from_raw", False) or getattr(args, "from_bam", False)   # (--from-bam: RawPlan lists BAM files)
     from_fasta = getattr(args, "from_fasta", False)
     if from_fasta:
         from .fasta import fasta_files, fasta_to_query, sample_of
@@ -563,7 +601,14 @@ class RawPlan:
             eprint("If your input directory contains pre-generated images, use the --images flag:")
             eprint("    varkoder_amd query --images " + str(src) + " " + str(args.outdir))
             raise Exception("Input directory contains PNG files. Use --images flag for pre-generated images.")
-        table = process_input(args.input, is_query=is_query)
+        self.bam = bam_options(args)
+        if self.bam is not None:   # every *.bam of the folder is one sample; labels as for --from-fasta
+            from .bam import bam_files, sample_of
+            files = bam_files(src)
+            labels = {} if is_query else read_labels(getattr(args, "labels_csv", None))
+            table = [(sample_of(f), ["query"] if is_query else labels.get(sample_of(f), []), [f]) for f in files]
+        else:
+            table = process_input(args.input, is_query=is_query)
         self.args = args
         self.samples = [s for s, _, _ in table]
         self.labels = {s: lab for s, lab, _ in table}   # (a query's: ["query"])
@@ -602,7 +647,7 @@ class RawPlan:
         found = {}
         if self.raw:
             found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
-                                      verbose=args.verbose, gpu_gzip=getattr(args, "gpu_gzip", False),
+                                      verbose=args.verbose, gpu_gzip=getattr(args, "gpu_gzip", False), bam=self.bam,
                                       **clean_options(args), **common))
         mine = [self.reused[i] for i in shard_by_size(clean_weights, rank, world)]
         if mine:
@@ -724,7 +769,8 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
                       gpu_gzip=getattr(args, "gpu_gzip", False))
         if plan.raw:
-            got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, **cleaning, **common)
+            got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, bam=plan.bam, **cleaning,
+                                     **common)
             per_sample.update(got)
             base_sd.update(sds)
         if plan.reused:
@@ -820,7 +866,7 @@ def run_image(args):
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
     if args.from_clean:
         return run_image_from_clean(args, outdir, rank, world, local_rank)
-    if args.from_raw:
+    if args.from_raw or getattr(args, "from_bam", False):   # (--from-bam: RawPlan lists BAM files, the run is the same)
         return run_image_from_raw(args, outdir, rank, world, local_rank)
     if getattr(args, "from_fasta", False):
         return run_image_from_fasta(args, outdir, rank, world, local_rank)
@@ -875,6 +921,13 @@ def main(argv=None):
     args = parse_args(argv)
     if not Path(args.input).exists():                                       # cli.py:503-505
         raise Exception("Input path", args.input, "does not exist. Please check.")
+    if args.command in ("image", "query") and getattr(args, "from_bam", False) and getattr(args, "bam_pairs", False):
+        # refused before anything is made or uploaded: mates of a file sorted by coordinate are not in the same order
+        from .bam import bam_files, check_pairs
+        why = check_pairs(bam_files(args.input)) if Path(args.input).is_dir() else None
+        if why:
+            eprint("error:", why)
+            raise SystemExit(2)
     if args.command == "image":
         run_image(args)
     elif args.command == "convert":

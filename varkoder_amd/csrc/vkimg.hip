@@ -29,6 +29,7 @@
 //   vk_fa_*_kernel (vk_fasta.h): the count straight from FASTA text (`--from-fasta`): cut by bytes, header state by a scan.
 //   vk_far_*_kernel (vk_fasta_records.h): the same per FASTA record (`--per-record`): record ordinal by a second scan.
 //   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
+//   vk_bam_*_kernel (vk_bam.h): BAM records to FASTQ text (`--from-bam`): record starts guessed per segment, verified in order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,6 +63,7 @@
 #include "vk_fasta_ladder.h"
 #include "vk_fasta_records.h"
 #include "vk_fasta_windows.h"
+#include "vk_bam.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -150,6 +152,10 @@ struct vk_ctx {
     uint8_t* d_fawin = nullptr;    // vk_count_fasta_windows_device: ordinal index | record table | tile rows (beside d_fasta, which far_prepare carves)
     size_t fawin_cap = 0;
     uint32_t fasta_unit_bytes = 0; // VKIMG_FASTA_UNIT_BYTES=n: bytes of a unit of the FASTA count, a multiple of 64 up to 16384, one unit per workgroup (tests: many seams in little text; 0 = 16384, 32 units per workgroup)
+    uint8_t* d_bamws = nullptr;    // vk_bam_frame_device, vk_bam_fastq_device: descriptors | segments | per-file results | link counters
+    size_t bamws_cap = 0;
+    uint32_t bam_seg_bytes = 0;    // VKIMG_BAM_SEG_BYTES=n: bytes of a segment of the BAM framing, 64 .. 65536 (tests: many seams in little data; 0 = 65536)
+    uint64_t bam_segments = 0, bam_rewalked = 0;   // of the last of those calls (vk_last_bam_frame)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -659,6 +665,9 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
         if (ctx->fasta_unit_bytes < kFaLaneBytes) ctx->fasta_unit_bytes = kFaLaneBytes;
         if (ctx->fasta_unit_bytes > kFaUnitBytes) ctx->fasta_unit_bytes = kFaUnitBytes;
     }
+    env_uint("VKIMG_BAM_SEG_BYTES", &ctx->bam_seg_bytes);
+    if (ctx->bam_seg_bytes && ctx->bam_seg_bytes < 64) ctx->bam_seg_bytes = 64;
+    if (ctx->bam_seg_bytes > kBamSegBytes) ctx->bam_seg_bytes = kBamSegBytes;
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return VK_EHIP; }
     {
@@ -681,7 +690,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin, ctx->d_bamws};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -2786,6 +2795,181 @@ int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64
                            steps, row_lo, nrows, d_hist);
         VK_HIP(ctx, hipGetLastError());
     }
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- BAM to FASTQ (vk_bam.h) --------------------------
+
+namespace {
+
+// What the two BAM calls share: the descriptors on the device, the segments, the link pass's results on the host.
+struct BamState {
+    BamMeta m;
+    BamStreams ss;
+    BamSeg* d_segs = nullptr;
+    uint16_t* d_starts = nullptr;   // bam_starts_cap per segment
+    BamFile* d_files = nullptr;
+    unsigned long long* d_link = nullptr;
+    uint64_t segs = 0, stream_segs = 0;
+    std::vector<BamFile> files;   // (host) once bam_finish has run
+};
+
+bool bam_args_ok(const vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
+                 const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select, uint32_t nstreams,
+                 uint32_t flags) {
+    if (!ctx || (flags & ~kBamNoGuess)) return false;
+    if (nfiles && (!d_bam || !offsets || !lengths || !first_record || !n_ref)) return false;
+    if (nstreams && (!stream_file || !stream_select)) return false;
+    for (uint32_t s = 0; s < nstreams; ++s)
+        if (stream_file[s] >= nfiles || stream_select[s] > kBamSingle) return false;
+    return true;
+}
+
+// Segment pass and link pass (out_offsets, out_caps: null for the framing call).
+int bam_frame(vk_ctx* ctx, const uint8_t* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
+              const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select, uint32_t nstreams,
+              const uint64_t* out_offsets, const uint64_t* out_caps, uint32_t exclude, uint32_t flags, BamState* st) {
+    const uint32_t seg = ctx->bam_seg_bytes ? ctx->bam_seg_bytes : kBamSegBytes;
+    // u64 descriptors: offsets | lengths | first records | files' segment sums | streams' segment sums | slots | caps
+    std::vector<uint64_t> h64(3ull * nfiles + (nfiles + 1ull) + (nstreams + 1ull) + 2ull * nstreams);
+    uint64_t* h_offs = h64.data();
+    uint64_t* h_lens = h_offs + nfiles;
+    uint64_t* h_first = h_lens + nfiles;
+    uint64_t* h_seg_first = h_first + nfiles;
+    uint64_t* h_sseg_first = h_seg_first + nfiles + 1;
+    uint64_t* h_out_offs = h_sseg_first + nstreams + 1;
+    uint64_t* h_out_caps = h_out_offs + nstreams;
+    h_seg_first[0] = 0;
+    for (uint32_t i = 0; i < nfiles; ++i) {
+        h_offs[i] = offsets[i];
+        h_lens[i] = lengths[i];
+        h_first[i] = first_record[i];
+        const uint64_t n = (lengths[i] + seg - 1) / seg;
+        h_seg_first[i + 1] = h_seg_first[i] + (n ? n : 1);
+    }
+    h_sseg_first[0] = 0;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        const uint32_t f = stream_file[s];
+        h_sseg_first[s + 1] = h_sseg_first[s] + (h_seg_first[f + 1] - h_seg_first[f]);
+        h_out_offs[s] = out_offsets ? out_offsets[s] : 0;
+        h_out_caps[s] = out_caps ? out_caps[s] : 0;
+    }
+    st->segs = h_seg_first[nfiles];
+    st->stream_segs = h_sseg_first[nstreams];
+    if (st->segs >= (1ull << 31) || st->stream_segs >= (1ull << 31)) return VK_EINVAL;
+    // u32 descriptors: reference counts | streams' files | streams' selections
+    std::vector<uint32_t> h32(nfiles + 2ull * nstreams + 1);
+    for (uint32_t i = 0; i < nfiles; ++i) h32[i] = static_cast<uint32_t>(n_ref[i]);
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        h32[nfiles + s] = stream_file[s];
+        h32[nfiles + nstreams + s] = stream_select[s];
+    }
+    uint64_t* d64 = nullptr;
+    uint32_t* d32 = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_bamws, &ctx->bamws_cap, [&](WsTake& take) {
+        take(d64, h64.size());
+        take(d32, h32.size());
+        take(st->d_segs, st->segs);
+        take(st->d_starts, st->segs * (seg / kBamMinRecord + 2));   // (bam_starts_cap)
+        take(st->d_files, nfiles);
+        take(st->d_link, 2);
+    });
+    if (rc) return rc;
+    // (pageable sources: the copies have read them on return)
+    VK_HIP(ctx, hipMemcpyAsync(d64, h64.data(), h64.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d32, h32.data(), h32.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(st->d_link, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    st->m = BamMeta{d64, d64 + nfiles, d64 + 2ull * nfiles, d64 + 3ull * nfiles, reinterpret_cast<const int32_t*>(d32), nfiles, seg};
+    const uint64_t* d_sseg = d64 + 3ull * nfiles + nfiles + 1;
+    st->ss = BamStreams{d32 + nfiles, d32 + nfiles + nstreams, d_sseg, d_sseg + nstreams + 1, d_sseg + nstreams + 1 + nstreams, nstreams};
+    hipLaunchKernelGGL(vk_bam_segment_kernel, dim3(static_cast<uint32_t>(st->segs)), dim3(64), 0, ctx->stream, d_bam, st->m, exclude, flags,
+                       st->d_segs, st->d_starts);
+    VK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(vk_bam_link_kernel, dim3(nfiles), dim3(64), 0, ctx->stream, d_bam, st->m, exclude, st->d_segs, st->d_starts,
+                       st->d_files, st->d_link);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// The link pass's results on the host; synchronises.
+int bam_finish(vk_ctx* ctx, uint32_t nfiles, BamState* st) {
+    st->files.resize(nfiles);
+    unsigned long long link[2] = {0, 0};
+    VK_HIP(ctx, hipMemcpyAsync(st->files.data(), st->d_files, nfiles * sizeof(BamFile), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(link, st->d_link, sizeof(link), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->bam_segments = link[0];
+    ctx->bam_rewalked = link[1];
+    return VK_OK;
+}
+
+uint64_t bam_host_pick(const uint64_t* v, uint32_t select) { return select == kBamAll ? v[0] + v[1] + v[2] : v[select - 1]; }
+
+}  // namespace
+
+extern "C" {
+
+int vk_bam_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
+                        const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select,
+                        uint32_t nstreams, uint32_t exclude, uint32_t flags, uint64_t* out_records, uint64_t* out_bytes,
+                        uint32_t* status) {
+    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
+        return VK_EINVAL;
+    if ((nstreams && (!out_records || !out_bytes)) || (nfiles && !status)) return VK_EINVAL;
+    ctx->bam_segments = ctx->bam_rewalked = 0;
+    if (nfiles == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    BamState st;
+    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select,
+                       nstreams, nullptr, nullptr, exclude, flags, &st);
+    if (rc) return rc;
+    rc = bam_finish(ctx, nfiles, &st);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st.files[i].status;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        out_records[s] = bam_host_pick(st.files[stream_file[s]].recs, stream_select[s]);
+        out_bytes[s] = bam_host_pick(st.files[stream_file[s]].bytes, stream_select[s]);
+    }
+    return VK_OK;
+}
+
+int vk_bam_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
+                        const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select,
+                        uint32_t nstreams, uint32_t exclude, uint32_t flags, void* d_out, const uint64_t* out_offsets,
+                        const uint64_t* out_caps, uint64_t* out_lengths, uint32_t* status) {
+    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
+        return VK_EINVAL;
+    if ((nstreams && (!d_out || !out_offsets || !out_caps || !out_lengths)) || (nfiles && !status)) return VK_EINVAL;
+    ctx->bam_segments = ctx->bam_rewalked = 0;
+    if (nfiles == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    BamState st;
+    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select,
+                       nstreams, out_offsets, out_caps, exclude, flags, &st);
+    if (rc) return rc;
+    if (st.stream_segs) {
+        hipLaunchKernelGGL(vk_bam_emit_kernel, dim3(static_cast<uint32_t>(st.stream_segs)), dim3(kBamEmitThreads), 0, ctx->stream,
+                           static_cast<const uint8_t*>(d_bam), st.m, st.ss, exclude, st.d_segs, st.d_starts, st.d_files,
+                           static_cast<uint8_t*>(d_out));
+        VK_HIP(ctx, hipGetLastError());
+    }
+    rc = bam_finish(ctx, nfiles, &st);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st.files[i].status;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        const uint64_t n = bam_host_pick(st.files[stream_file[s]].bytes, stream_select[s]);
+        out_lengths[s] = n <= out_caps[s] ? n : 0;
+        if (n > out_caps[s]) rc = VK_ENOSPC;
+    }
+    return rc;
+}
+
+int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked) {
+    if (!ctx || !segments || !rewalked) return VK_EINVAL;
+    *segments = ctx->bam_segments;
+    *rewalked = ctx->bam_rewalked;
     return VK_OK;
 }
 

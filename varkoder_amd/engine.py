@@ -658,6 +658,71 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_count_fasta_windows_device")
         return hist
 
+    # -- BAM ---------------------------------------------------------------------
+    def _bam_args(self, offsets, lengths, first_record, n_ref, stream_file, stream_select):
+        offs, lens = self._desc(offsets, lengths)
+        first = np.ascontiguousarray(first_record, dtype=np.uint64)
+        nref = np.ascontiguousarray(n_ref, dtype=np.int32)
+        sf = np.ascontiguousarray(stream_file, dtype=np.uint32)
+        sel = np.ascontiguousarray(stream_select, dtype=np.uint32)
+        if first.shape != offs.shape or nref.shape != offs.shape or sf.ndim != 1 or sf.shape != sel.shape:
+            raise ValueError("first_record and n_ref: one per file; stream_file and stream_select: one per stream")
+        return offs, lens, first, nref, sf, sel
+
+    def bam_frame(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude=0x900, flags=0):
+        """The reads of BAM files whose inflated bytes lie in HBM (vk_bam_frame_device; the rule: INTEGRATION.md,
+        "--from-bam: the rule"): stream s takes the reads stream_select[s] (VK_BAM_ALL / READ1 / READ2 / SINGLE) of file
+        stream_file[s].  Returns (records uint64 [nstreams], text bytes uint64 [nstreams], status uint32 [nfiles] of
+        VK_BAM_* bits) on the host; synchronises."""
+        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
+        recs = np.zeros(len(sf), dtype=np.uint64)
+        nbytes = np.zeros(len(sf), dtype=np.uint64)
+        status = np.zeros(len(offs), dtype=np.uint32)
+        st = self.L.vk_bam_frame_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
+                                        nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(sf), _u32(sel), len(sf),
+                                        int(exclude), int(flags), _u64(recs), _u64(nbytes), _u32(status))
+        _capi.check(self.ctx, st, "vk_bam_frame_device")
+        return recs, nbytes, status
+
+    def bam_fastq(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, out, out_offsets, out_caps,
+                  exclude=0x900, flags=0):
+        """The FASTQ text of those streams (vk_bam_fastq_device) into `out` (uint8 device tensor) at out_offsets, at most
+        out_caps bytes each.  Returns (text lengths uint64 [nstreams], status uint32 [nfiles]) on the host;
+        synchronises."""
+        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
+        oo, oc = self._desc(out_offsets, out_caps)
+        if oo.shape != sf.shape:
+            raise ValueError("out_offsets and out_caps: one per stream")
+        got = np.zeros(len(sf), dtype=np.uint64)
+        status = np.zeros(len(offs), dtype=np.uint32)
+        st = self.L.vk_bam_fastq_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
+                                        nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(sf), _u32(sel), len(sf),
+                                        int(exclude), int(flags), self._ptr(out), _u64(oo), _u64(oc), _u64(got), _u32(status))
+        _capi.check(self.ctx, st, "vk_bam_fastq_device")
+        return got, status
+
+    def bam_to_fastq(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude=0x900, flags=0):
+        """bam_frame, a text buffer sized by it (every stream at a multiple of 16 bytes, as upload() lays samples out), and
+        bam_fastq: (text uint8 device tensor, offsets uint64 [nstreams], lengths uint64 [nstreams], status uint32
+        [nfiles]).  `bam` stays the caller's."""
+        torch = _torch()
+        _, nbytes, _ = self.bam_frame(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags)
+        oo = np.zeros(len(nbytes), dtype=np.uint64)
+        pos = 0
+        for i, n in enumerate(nbytes):
+            oo[i] = pos
+            pos += (int(n) + 15) // 16 * 16
+        out = torch.zeros(pos + 16, dtype=torch.uint8, device=self.device)
+        got, status = self.bam_fastq(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, out, oo, nbytes,
+                                     exclude, flags)
+        return out, oo, got, status
+
+    def last_bam_frame(self):
+        """(segments, segments walked again) of the last bam_frame / bam_fastq call (vk_last_bam_frame)."""
+        seg, re = C.c_uint64(), C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_last_bam_frame(self.ctx, C.byref(seg), C.byref(re)), "vk_last_bam_frame")
+        return seg.value, re.value
+
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):
         """K1 over a pseudo-random subset of each sample's reads (vk_count_sampled_device):

@@ -14,6 +14,8 @@ from contextlib import contextmanager
 from dataclasses import dataclass
 from pathlib import Path
 
+import numpy as np
+
 from .config import QUAL_THRESH, SAMPLE_BP_SEP
 from .image import counts_name, eprint, png_name, shard_folder, stem, write_png
 from .shard import TailQueue, agreed_weights, file_weights, gz_text_bytes, shard_by_size, split_head_tail
@@ -522,12 +524,17 @@ def _budget(avgs, lines, sample_files, max_bp):
     return [int(take.get(f, 0)) for f, _ in sample_files]
 
 
-def _raw_plans(samples, weights, rank, world):
+def _raw_plans(samples, weights, rank, world, bam=None):
     """This rank's share of raw samples [(sample, [files])] as [(sample, [(file, role)])], dealt by weight (per sample:
-    the sum of its files' weights; None: agreed on here, a collective when sharded)."""
-    plans = [(s, _sample_files(files)) for s, files in samples]
+    the sum of its files' weights; None: agreed on here, a collective when sharded).  bam (the options of `--from-bam`):
+    a sample is one BAM file and its plan [(file, role, select)] (bam.sample_plan)."""
+    if bam is not None:
+        from .bam import sample_plan
+        plans = [(s, sample_plan(files[0], bam.get("pairs", False))) for s, files in samples]
+    else:
+        plans = [(s, _sample_files(files)) for s, files in samples]
     if weights is None:
-        weights = sample_weights([(s, [f for f, _ in sf]) for s, sf in plans], world)
+        weights = sample_weights([(s, list(dict.fromkeys(e[0] for e in sf))) for s, sf in plans], world)
     return [plans[i] for i in shard_by_size(weights, rank, world)]
 
 
@@ -543,6 +550,47 @@ class Cleaning:
     clean_dir: object
     max_bp: int
     gpu_gzip: bool = False
+    bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int}; the plans then hold (file, role, select)
+
+
+def _bam_texts(eng, batch, pool, bam):
+    """`--from-bam`'s step between the upload and the cleaning, for a batch [(sample, [(file, role, select)])]: the
+    files' headers are read on the host (bam.bam_header), their bytes uploaded and inflated in HBM
+    (ImageEngine.upload_files), converted to one FASTQ text per (file, role) there (ImageEngine.bam_to_fastq) and
+    released.  Returns (text, offsets, lengths, {index in the batch: why it failed}): a file that is not BAM, whose
+    header does not parse or whose records give a status fails its sample; its texts are empty."""
+    from .bam import BamError, file_info
+    files = list(dict.fromkeys(Path(f) for _, plan in batch for f, _, _ in plan))
+    heads, why = {}, {}
+    for f in files:
+        try:
+            heads[f] = file_info(f)[1]   # (read when the batch was sized: not again)
+        except (BamError, OSError) as e:
+            why[f] = str(e) or type(e).__name__
+    good = [f for f in files if f in heads]
+    at = {f: i for i, f in enumerate(good)}
+    streams = [(j, Path(f), sel) for j, (_, plan) in enumerate(batch) for f, _, sel in plan]
+    offs = np.zeros(len(streams), dtype=np.uint64)
+    lens = np.zeros(len(streams), dtype=np.uint64)
+    text, failed = None, {}
+    if good:
+        dev, doffs, dlens = eng.upload_files(good, pool)
+        live = [i for i, (_, f, _) in enumerate(streams) if f in at]
+        text, oo, ol, status = eng.bam_to_fastq(dev, doffs, dlens, [heads[f][0] for f in good], [heads[f][1] for f in good],
+                                                [at[streams[i][1]] for i in live], [streams[i][2] for i in live],
+                                                exclude=bam.get("exclude", 0x900))
+        del dev
+        offs[live], lens[live] = oo, ol
+        inflate = getattr(eng, "last_upload_status", None)   # (a member that does not inflate or fails its CRC: no bytes)
+        for f in good:
+            if inflate is not None and inflate[at[f]]:
+                why[f] = "inflate status %d" % int(inflate[at[f]])
+            elif status[at[f]]:
+                why[f] = "BAM status %d" % int(status[at[f]])
+    for j, f, _ in streams:
+        if f in why:
+            failed[j] = why[f]
+    return text, offs, lens, failed
 
 
 def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, verbose):
@@ -579,11 +627,42 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
         with open(clean_dir / (sample + "_fastp_gpu.json"), "w") as fh:
             json.dump(report, fh)
 
-    for batch, nbytes, t0 in batches(mine, batch_bytes, size=lambda plan: sum(text_bytes(f) for f, _ in plan[1])):
-        paths = [Path(f) for _, sf in batch for f, _ in sf]
-        dev, offs, lens = eng.upload_files(paths, pool)
+    if opt.bam is not None:
+        from .bam import batch_bytes as bam_bytes
+
+        def size(plan):
+            return sum(bam_bytes(f) for f in dict.fromkeys(f for f, _, _ in plan[1]))
+    else:
+        def size(plan):
+            return sum(text_bytes(f) for f, _ in plan[1])
+
+    for batch, nbytes, t0 in batches(mine, batch_bytes, size=size):
+        if opt.bam is not None:   # BAM bytes in, one FASTQ text per (file, role) out; from here on the run is --from-raw's
+            dev, offs, lens, bad = _bam_texts(eng, batch, pool, opt.bam)
+            for j, why in bad.items():
+                eprint("CLEAN FAIL:", sorted({str(f) for f, _, _ in batch[j][1]}), "-", why)
+                stats.setdefault(batch[j][0], OrderedDict())["failed_step"] = "clean"
+            nstreams = [len(plan) for _, plan in batch]
+            first = np.concatenate(([0], np.cumsum(nstreams)))
+            keep = [j for j in range(len(batch)) if j not in bad]
+            # A stream without reads (--bam-pairs on a file of mates only, or of single reads only) is no file of the
+            # sample, as a role without files is none of a raw sample's; a sample without any read keeps one empty
+            # stream and fails where a raw sample of an empty file fails.  A stream per role of ONE file: named
+            # apart, the read budget is kept by name.
+            rows, plans = [], []
+            for j in keep:
+                mine = [i for i in range(first[j], first[j + 1]) if lens[i]] or [int(first[j])]
+                rows += mine
+                plans.append((batch[j][0], [(f"{f}:{('single', 'R1', 'R2')[role]}", role)
+                                            for f, role, _ in (batch[j][1][i - first[j]] for i in mine)]))
+            offs, lens, batch = offs[rows], lens[rows], plans
+            if not batch:
+                continue
+        else:
+            paths = [Path(f) for _, sf in batch for f, _ in sf]
+            dev, offs, lens = eng.upload_files(paths, pool)
         lines = eng.clean_lines(dev, offs, lens)
-        avgs = [0] * len(paths)
+        avgs = [0] * len(lines)
         if opt.max_bp is not None:   # (the mean length of each file's first 10,000 reads: estimate_read_lengths, commands/image.py:90-115)
             totals, counted = eng.clean_heads(dev, offs, lens, 10000)
             avgs = [round(int(t) / int(n)) if n else 0 for t, n in zip(totals, counted)]
@@ -649,7 +728,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
-                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False):
+                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -663,11 +742,14 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     split_dir, overwrite, no_image: as clean_to_images takes them.  gpu_gzip: the .fq.gz files of clean_dir and split_dir
     are compressed on the GPU (ImageEngine.deflate: BGZF) and only their bytes are copied back.
 
+    bam = {"pairs": bool, "exclude": int}: `--from-bam` -- every sample is ONE BAM file, converted to FASTQ text in HBM
+    between the upload and the cleaning (_bam_texts; the rule: INTEGRATION.md, "--from-bam: the rule").
+
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
-    mine = _raw_plans(samples, weights, rank, world)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip)
+    mine = _raw_plans(samples, weights, rank, world, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, bam)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels)
@@ -698,14 +780,15 @@ def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, 
 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
                  seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
-                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False):
+                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None):
     """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
     cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
-    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU)."""
-    mine = _raw_plans(samples, weights, rank, world)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip)
+    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU).  bam: as
+    raw_to_images takes it."""
+    mine = _raw_plans(samples, weights, rank, world, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, bam)
     stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
