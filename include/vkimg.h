@@ -368,6 +368,30 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
                       uint8_t* d_out, uint64_t out_capacity, void* d_work, uint64_t work_bytes, uint64_t* out_offsets,
                       uint64_t* out_lengths);
 
+/* The PNG files' image data: replaces PIL's zlib pass behind every image file (commands/image.py: `img.save(..., optimize=True)`)
+ * for a batch of images resident in HBM, d_img[nimg][side][side] bytes (8-bit greyscale).  Image i becomes one complete
+ * IDAT chunk: the data's length (big-endian), "IDAT", a zlib stream, the chunk's CRC-32.  The stream's text is the
+ * image's rows with the filter byte 0 in front of each, side * (side + 1) bytes, cut into pieces of at most 65,280; each
+ * piece is one DEFLATE block as vk_deflate_device makes them (LZ77 tokens, the literals alone when that is smaller, stored
+ * when no code pays) with two additions: the byte one row up (side + 1 back) is a match candidate of every position, and
+ * the block takes RFC 1951's fixed codes where they are smaller than a lengths table and its codes.  A piece that is not
+ * the last is followed by an empty stored block where it does not end on a byte;
+ * the header is 78 01, the trailer the Adler-32 of the text.  Pixels are what any PNG reader gives back; the bytes are
+ * not PIL's and are not pinned between versions.  The same images give the same bytes.
+ *
+ * vk_png_bound: *out_bound = nimg * (16 + 2 + side * (side + 1) + 9 * pieces, rounded up to 16), pieces =
+ * ceil(side * (side + 1) / 65280): the bytes d_out must hold.  Host arithmetic.  vk_png_workspace_size: the bytes of
+ * d_work (per piece a slot of min(side * (side + 1), 65280) + 11 bytes rounded up to 16, and tables).
+ * vk_png_device: every argument is checked before anything is launched: VK_EINVAL for a null pointer, nimg 0, side 0 or
+ * above 512, or a workspace that is too small; VK_ENOSPC when out_capacity is below the bound (d_out untouched).  Chunk i
+ * is written to d_out[out_offsets[i] .. +out_lengths[i]) (host arrays out; offsets multiples of 16, the chunks in image
+ * order, packed: the last one ends below the bound; the bytes up to a chunk's 16-byte rounded end are zeroed).  The
+ * number of launches does not depend on nimg.  The call synchronises. */
+int vk_png_bound(uint32_t side, uint32_t nimg, uint64_t* out_bound);
+int vk_png_workspace_size(uint32_t side, uint32_t nimg, uint64_t* out_bytes);
+int vk_png_device(vk_ctx* ctx, const void* d_img, uint32_t nimg, uint32_t side, uint8_t* d_out, uint64_t out_capacity,
+                  void* d_work, uint64_t work_bytes, uint64_t* out_offsets, uint64_t* out_lengths);
+
 /* Replaces: dsk on a FASTA input, `dsk -kmer-size k -abundance-min 1 -file IN.fa` (commands/image.py:771-796; the real dsk
  * reads FASTA as well as FASTQ), for a batch of samples resident in HBM, laid out as for vk_count_device (offsets multiples
  * of 16, readable up to the last sample's 16-byte rounded end).  The rule is this project's ("--from-fasta";

@@ -32,7 +32,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_ladder_emit_device", "vk_train_batch_device", "vk_deflate_bound", "vk_deflate_workspace_size", "vk_deflate_device",
            "vk_count_fasta_device", "vk_count_fasta_host", "vk_count_fasta_sampled_device", "vk_fasta_records_count_device",
            "vk_fasta_records_device", "vk_count_fasta_records_device", "vk_count_fasta_windows_device", "vk_bam_frame_device",
-           "vk_bam_fastq_device", "vk_last_bam_frame")
+           "vk_bam_fastq_device", "vk_last_bam_frame", "vk_png_bound", "vk_png_workspace_size", "vk_png_device")
 
 _lib = None
 
@@ -97,6 +97,9 @@ def lib():
     L.vk_deflate_bound.argtypes = [u64p, C.c_uint32, u64p]
     L.vk_deflate_workspace_size.argtypes = [u64p, C.c_uint32, u64p]
     L.vk_deflate_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
+    L.vk_png_bound.argtypes = [C.c_uint32, C.c_uint32, u64p]
+    L.vk_png_workspace_size.argtypes = [C.c_uint32, C.c_uint32, u64p]
+    L.vk_png_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, u64p, u64p]
     L.vk_count_fasta_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, vp, vp, vp]
     L.vk_count_fasta_sampled_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u32p, u64p, u64p, u64p,
                                                 vp, vp, vp, vp]

@@ -112,6 +112,10 @@ def setup_parser():
                    help="compress the .fq.gz files that this run writes (`INT/clean_reads/` with --from-raw and -i INT, "
                         "`INT/split_fastqs/` with --write-splits) on the GPU, as BGZF, and copy back the compressed bytes "
                         "only; without it the host's gzip (level 1) compresses them")
+    p.add_argument("--gpu-png", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="encode the image files on the GPU (filter 0, the project's own DEFLATE blocks) and leave the host "
+                        "only the writing; pixels and text chunks are the same as without it, the files' bytes are not. "
+                        "Not with -X")
     add_adapter_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
@@ -165,6 +169,9 @@ def setup_parser():
     q.add_argument("--gpu-gzip", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
                    help="with --from-raw and -i INT: compress the cleaned reads on the GPU, as BGZF, and copy back the "
                         "compressed bytes only")
+    q.add_argument("--gpu-png", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with -m/--keep-images: encode the kept images on the GPU; pixels and text chunks are the same as "
+                        "without it, the files' bytes are not")
     add_adapter_flags(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
@@ -347,6 +354,13 @@ def parse_args(argv=None):
             parser.error("--gpu-gzip: only with --from-raw and -i/--int-folder" +
                          (", or with --write-splits" if args.command == "image" else "") +
                          " (--from-bam counts as --from-raw)")
+    if getattr(args, "gpu_png", False):
+        if args.command == "query" and not args.keep_images:
+            parser.error("--gpu-png: only with -m/--keep-images")
+        if args.command == "query" and args.images:
+            parser.error("--gpu-png: not with -I/--images (no image is made)")
+        if args.command == "image" and args.no_image:
+            parser.error("--gpu-png: not with -X/--no-image")
     if args.command in ("image", "query"):
         given = [flag for name, flag in ADAPTER_FLAGS if hasattr(args, name)]
         if given and not (args.from_raw or from_bam):
@@ -417,7 +431,7 @@ def run_query(args):
     from . import query as Q
     from .convert import get_metadata_from_img_filename
     from .engine import ImageEngine
-    from .image import stem, write_png
+    from .image import png_head, stem, write_png, write_png_parts
     from .pipeline import clean_to_query
     from .shard import agreed_weights, io_threads_per_rank, shard_by_size, world_info
     from .subsample import split_name
@@ -483,9 +497,14 @@ def run_query(args):
             images = eng.images(torch.stack(hists))
             if args.keep_images:
                 (outdir / "query_images").mkdir(parents=True, exist_ok=True)
-                host = images.cpu().numpy()
+                gpu_png = getattr(args, "gpu_png", False)
+                host = eng.png(images) if gpu_png else images.cpu().numpy()
                 for j, (name, sample, sd) in enumerate(keep):
-                    write_png(host[j], outdir / "query_images" / name, labels.get(sample, []), sd, QUAL_THRESH, args.kmer_mapping)
+                    text = (labels.get(sample, []), sd, QUAL_THRESH, args.kmer_mapping)
+                    if gpu_png:
+                        write_png_parts(outdir / "query_images" / name, png_head(eng.side, *text), host[j])
+                    else:
+                        write_png(host[j], outdir / "query_images" / name, *text)
             return images
 
         if from_raw:
@@ -703,7 +722,7 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
                                      min_bp=parse_size(args.min_bp), max_bp=max_bp, seeds=seeds, labels=labels,
                                      base_sd=base_sd, **split_options(args), gpu_gzip=getattr(args, "gpu_gzip", False),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
-                                     verbose=args.verbose)
+                                     verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False))
         for s, v in per_sample.items():
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
@@ -741,7 +760,7 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
         failpoint(rank)
         per_sample = fasta_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
                                      labels=labels, device=local_rank, rank=rank, world=world,
-                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **ladder)
+                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), **ladder)
         for v in per_sample.values():
             v["base_frequencies_sd"] = 0   # (no cleaning report: the flag is False, as for any sample without one)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
@@ -767,7 +786,7 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
-                      gpu_gzip=getattr(args, "gpu_gzip", False))
+                      gpu_gzip=getattr(args, "gpu_gzip", False), gpu_png=getattr(args, "gpu_png", False))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, bam=plan.bam, **cleaning,
                                      **common)
@@ -895,7 +914,8 @@ def run_image(args):
         failpoint(rank)
         per_file = fastqs_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping, labels=labels,
                                     base_sd=base_sd, overwrite=True, subfolder_levels=levels, device=local_rank, rank=rank,
-                                    world=world, io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose)
+                                    world=world, io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose,
+                                    gpu_png=getattr(args, "gpu_png", False))
         # fold the per-file stats into per-sample stats like run_clean2img does (image.py:1057-1125); files are dealt by
         # size, so other ranks may hold further files of the same sample: shard.merge_stats adds the ranks' shares up
         ck, ik = f"{args.kmer_size}mer_counting_time", f"k{args.kmer_size}_img_time"

@@ -23,6 +23,10 @@
 // Then vk_cl_scan_* runs over the members' sizes and vk_df_gather_kernel packs every file's members and bgzip's empty
 // EOF member contiguously, every file at a multiple of 16 bytes.
 //
+// Steps 2 to 4 up to the block's last bit are df_block, which takes the bit offset at which the block starts and
+// BFINAL: the member (df_member) is staging, CRC-32 and the gzip/BGZF header and trailer around it, and vk_png.h frames
+// the same block as a piece of a PNG's zlib stream.
+//
 // The member compressor is written in PHASES: DF_LANES(t) ... DF_END is "every lane t runs this, then all wait".  No
 // value lives in a register across a phase: what one phase hands to the next lies in DfLds.  For the GPU a phase is
 // the lane's own code and a barrier; for the host (tests/emul/deflate_emul.cpp) it is a loop over the lanes, one after
@@ -71,7 +75,7 @@ struct DfFile {
 };
 
 // uniform values of a member (DfLds::u)
-enum { kDfCarry0 = 0, kDfCarry1, kDfSlen0, kDfSlen1, kDfCrc, kDfRes = 8, kDfU = 20 };   // kDfRes: three result slots of df_codes
+enum { kDfCarry0 = 0, kDfCarry1, kDfSlen0, kDfSlen1, kDfCrc, kDfFixed = 7, kDfRes = 8, kDfU = 20 };   // kDfRes: three result slots of df_codes
 
 struct DfLds {
     uint32_t text[kDfTextWords];          // the member's text (zero behind its end); later the member as it is written
@@ -200,6 +204,10 @@ DF_FN uint32_t df_rev(uint32_t code, uint32_t len) {
     for (uint32_t i = 0; i < len; ++i) r |= ((code >> i) & 1u) << (len - 1u - i);
     return r;
 }
+
+// DEFLATE's fixed literal/length code (RFC 1951, 3.2.6); the fixed distance code is the symbol in 5 bits
+DF_FN uint32_t df_fixed_len(uint32_t s) { return s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : 8u; }
+DF_FN uint32_t df_fixed_code(uint32_t s) { return s < 144u ? 0x30u + s : s < 256u ? 0x190u + (s - 144u) : s < 280u ? s - 256u : 0xC0u + (s - 280u); }
 
 // One alphabet's code, by one lane: S.sorted[base .. base+nsym) ascending -> S.clen / S.code[base ..).  An alphabet
 // with fewer than two used symbols gets two codes of one bit (a complete code, whatever reads it).
@@ -350,34 +358,18 @@ DF_FN void df_all_literals(DfLds& S, uint32_t n) {
     DF_END
 }
 
-// One member: text[0 .. n) (global, at a multiple of 4 bytes), 1 <= n <= kDfMemberText -> slot[0 .. *size), *size <= 65,311.
-DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, uint64_t* size) {
-    const uint32_t words = n >> 2;
+// The CRC-32 register after bytes [0, m) of S.text, started from `init`, into S.sorted[0] (not inverted); the byte table
+// lies in S.head[0 .. 256).  Lane t takes bytes [t C - pad, (t + 1) C - pad): zero bytes in front of a register that
+// is 0 change nothing, and the register of the lane that holds byte 0 starts at `init`.
+DF_FN void df_crc_lanes(DfLds& S, uint32_t m, uint32_t init) {
     uint32_t* const scan0 = S.sorted;
-    uint32_t* const scan1 = S.work;
-    // -- stage the text; the CRC's byte table
-    DF_LANES(t)
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(text);
-        for (uint32_t i = t; i < kDfTextWords; i += kDfThreads) {
-            uint32_t w = 0;
-            if (i < words) w = src[i];
-            else if (i == words)
-                for (uint32_t b = 0; b < (n & 3u); ++b) w |= static_cast<uint32_t>(text[4u * i + b]) << (8u * b);
-            S.text[i] = w;
-        }
-        uint32_t c = t;
-        for (uint32_t k = 0; k < 8u; ++k) c = (c & 1u) ? (c >> 1) ^ kDfPoly : c >> 1;
-        S.head[t] = c;
-        if (t < kDfU) S.u[t] = 0;
-    DF_END
-    // -- CRC-32: lane t takes bytes [t C - pad, (t + 1) C - pad) of the text, zero bytes in front of it change nothing
-    const uint32_t C = (n + kDfThreads - 1u) / kDfThreads, pad = kDfThreads * C - n;
+    const uint32_t C = (m + kDfThreads - 1u) / kDfThreads, pad = kDfThreads * C - m;
     DF_LANES(t)
         const uint8_t* tb = reinterpret_cast<const uint8_t*>(S.text);
         uint32_t c = 0;
         for (uint32_t v = t * C; v < (t + 1u) * C; ++v) {
             if (v < pad) continue;
-            if (v == pad) c = 0xFFFFFFFFu;
+            if (v == pad) c = init;
             c = S.head[(c ^ tb[v - pad]) & 0xFFu] ^ (c >> 8);
         }
         scan0[t] = c;
@@ -391,10 +383,22 @@ DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, u
             f = df_mulmod(f, f);
         }
     }
-    DF_LANES(t)
-        if (t == 0u) S.u[kDfCrc] = ~scan0[0];
-        for (uint32_t i = t; i < (1u << kDfHashBits); i += kDfThreads) S.head[i] = 0;
-    DF_END
+}
+
+// One DEFLATE block of the text staged in S.text[0 .. n) (zero behind its end), 1 <= n <= kDfMemberText, with S.head and
+// S.u's carries, stream lengths and result slots zero.  The block is the cheaper of the tokens' and the literals'
+// dynamic blocks; its bits are ORed into S.text (which they replace) from bit `bit0` on, with `bfinal` in its first
+// bit, everything else zero up to `tail` bytes behind the block's last byte: the caller's framing goes there and in
+// front of bit0.  Returns the bit behind the block's last one -- or 0 when no code pays: then S.text still holds the
+// text and the caller writes it as a stored block.  (bit0 / 8 + tail <= 26: the output fits S.text.)
+// fixed != 0: the chosen tokens are also priced with DEFLATE's fixed codes (BTYPE 1) and written with them where that
+// is smaller -- a text of a few hundred bytes, where the lengths table is most of a dynamic block; S.u[kDfFixed] zero.
+// above != 0: a third candidate beside the hash table's and distance 1, the position `above` bytes back (an image's
+// row above; the table only knows earlier rounds, and a small image's first round is half of it).
+// The BGZF members ask for neither: their bytes are recorded.
+DF_FN uint32_t df_block(DfLds& S, uint32_t n, uint32_t bit0, uint32_t bfinal, uint32_t tail, uint32_t fixed, uint32_t above) {
+    uint32_t* const scan0 = S.sorted;
+    uint32_t* const scan1 = S.work;
     // -- what the literals alone would cost (greedy matches can cost more than the bytes they stand for)
     df_all_literals(S, n);
     df_codes(S, n, 0u);
@@ -417,6 +421,10 @@ DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, u
                     if (p >= 1u && dist != 1u) {
                         const uint32_t l1 = df_match_len(S.text, p, p - 1u, maxlen);
                         if (l1 >= len) { len = l1; dist = 1u; }
+                    }
+                    if (above && p >= above && dist != above) {   // (the text itself: the same whatever order lanes run in)
+                        const uint32_t l2 = df_match_len(S.text, p, p - above, maxlen);
+                        if (l2 > len) { len = l2; dist = above; }
                     }
                     if (len < kDfMinMatch || (len == kDfMinMatch && dist > kDfFar)) len = 0;
                 }
@@ -486,11 +494,114 @@ DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, u
     const uint32_t slen = use == 1u ? mslen : n;
     const uint32_t SC = (slen + kDfThreads - 1u) / kDfThreads;   // stream bytes a lane walks
     const uint32_t hlit = S.u[kDfRes + 4u * use + 2u], hdist = S.u[kDfRes + 4u * use + 3u];
-    const uint32_t tabbits = S.u[kDfRes + 4u * use + 1u] + hlit + hdist;
-    const uint32_t dynbits = df_code_bits(S, use);
+    // S.freq and the codes are the chosen stream's, unless the literals were chosen and not coded again (stored follows)
+    const bool coded = use == 1u || (litbits + 7u) / 8u < n + 5u;
+    if (fixed && coded) {
+        DF_LANES(t)
+            uint32_t bits = 0;
+            for (uint32_t i = t; i < kDfSyms; i += kDfThreads) {
+                const bool ll = i < kDfDBase;
+                const uint32_t s = ll ? i : i - kDfDBase;
+                if (s < (ll ? kDfLL : kDfD)) bits += S.freq[i] * (ll ? df_fixed_len(s) + df_ll_extra_bits(s) : 5u + df_d_extra_bits(s));
+            }
+            if (bits) df_add(&S.u[kDfFixed], bits);
+        DF_END
+    }
+    const bool fix = fixed && coded && 3u + S.u[kDfFixed] < df_code_bits(S, use);
+    if (fix) {
+        DF_LANES(t)
+            for (uint32_t i = t; i < kDfSyms; i += kDfThreads) {
+                const bool ll = i < kDfDBase;
+                const uint32_t s = ll ? i : i - kDfDBase;
+                S.clen[i] = static_cast<uint8_t>(ll ? df_fixed_len(s) : 5u);
+                S.code[i] = static_cast<uint16_t>(ll ? df_rev(df_fixed_code(s), df_fixed_len(s)) : df_rev(s, 5u));
+            }
+        DF_END
+    }
+    const uint32_t tabbits = fix ? 0u : S.u[kDfRes + 4u * use + 1u] + hlit + hdist;
+    const uint32_t preamble = fix ? 3u : kDfPreamble;
+    const uint32_t dynbits = fix ? 3u + S.u[kDfFixed] : df_code_bits(S, use);
     const uint32_t dynbytes = (dynbits + 7u) / 8u;
+    if (dynbytes >= n + 5u) return 0u;   // a stored block is no larger
+    // -- dynamic block: every lane's first bit, then the bits
+    const uint32_t owords = (bit0 / 8u + dynbytes + tail + 3u) / 4u;
+    DF_LANES(t)
+        const uint32_t o1 = (t + 1u) * SC < slen ? (t + 1u) * SC : slen;
+        uint32_t bits = 0;
+        for (uint32_t o = t * SC; o < o1; ++o) {
+            const uint32_t kind = df_kind(S.mbits, o);
+            uint64_t v;
+            if (kind != 2u) bits += df_token_bits(S, o, kind, v);
+        }
+        scan0[t] = bits;
+        for (uint32_t i = t; i < owords + 2u; i += kDfThreads) S.text[i] = 0;   // (dynbytes < n + 5: owords + 2 <= kDfTextWords)
+    DF_END
+    for (uint32_t k = 0; k < 8u; ++k) {   // inclusive scan, doubling
+        DF_LANES(t)
+            const uint32_t d = 1u << k;
+            (k & 1u ? scan0 : scan1)[t] = (k & 1u ? scan1 : scan0)[t] + (t >= d ? (k & 1u ? scan1 : scan0)[t - d] : 0u);
+        DF_END
+    }
+    const uint32_t tok0 = bit0 + preamble + tabbits;   // of the first token
+    DF_LANES(t)
+        uint32_t* out = S.text;
+        const uint32_t o1 = (t + 1u) * SC < slen ? (t + 1u) * SC : slen;
+        uint32_t at = tok0 + (t ? scan0[t - 1u] : 0u);
+        for (uint32_t o = t * SC; o < o1; ++o) {
+            const uint32_t kind = df_kind(S.mbits, o);
+            if (kind == 2u) continue;
+            uint64_t v;
+            const uint32_t nb = df_token_bits(S, o, kind, v);
+            df_put(out, at, v, nb);
+            at += nb;
+        }
+        if (t == kDfThreads - 1u) {   // block preamble, the lengths, end of block
+            uint32_t b = bit0;
+            df_put(out, b, bfinal | ((fix ? 1u : 2u) << 1), 3u); b += 3u;      // BFINAL, BTYPE 2 (1: the fixed codes, no table)
+            if (!fix) {
+                df_put(out, b, hlit - 257u, 5u); b += 5u;
+                df_put(out, b, hdist - 1u, 5u); b += 5u;
+                df_put(out, b, 15u, 4u); b += 4u;                     // all 19 lengths of the code-length code
+                // in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15: symbol 0 one bit, 1..16 five bits, 17 and 18 unused
+                for (uint32_t i = 0; i < 19u; ++i) { df_put(out, b, i == 3u ? 1u : (i == 1u || i == 2u ? 0u : 5u), 3u); b += 3u; }
+                for (uint32_t i = 0; i < hlit + hdist; ++i) {
+                    const uint32_t l = S.clen[i < hlit ? i : kDfDBase + (i - hlit)];
+                    if (l) { df_put(out, b, df_rev(15u + l, 5u), 5u); b += 5u; } else b += 1u;   // (code 0, one bit)
+                }
+            }
+            df_put(out, at, S.code[256], S.clen[256]);
+        }
+    DF_END
+    return bit0 + dynbits;
+}
+
+// One member: text[0 .. n) (global, at a multiple of 4 bytes), 1 <= n <= kDfMemberText -> slot[0 .. *size), *size <= 65,311.
+DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, uint64_t* size) {
+    const uint32_t words = n >> 2;
+    // -- stage the text; the CRC's byte table
+    DF_LANES(t)
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(text);
+        for (uint32_t i = t; i < kDfTextWords; i += kDfThreads) {
+            uint32_t w = 0;
+            if (i < words) w = src[i];
+            else if (i == words)
+                for (uint32_t b = 0; b < (n & 3u); ++b) w |= static_cast<uint32_t>(text[4u * i + b]) << (8u * b);
+            S.text[i] = w;
+        }
+        uint32_t c = t;
+        for (uint32_t k = 0; k < 8u; ++k) c = (c & 1u) ? (c >> 1) ^ kDfPoly : c >> 1;
+        S.head[t] = c;
+        if (t < kDfU) S.u[t] = 0;
+    DF_END
+    df_crc_lanes(S, n, 0xFFFFFFFFu);
+    DF_LANES(t)
+        if (t == 0u) S.u[kDfCrc] = ~S.sorted[0];
+        for (uint32_t i = t; i < (1u << kDfHashBits); i += kDfThreads) S.head[i] = 0;
+    DF_END
+    // -- the block, behind the header
+    const uint32_t end = df_block(S, n, kDfHeader * 8u, 1u, kDfTrailer, 0u, 0u);
     const uint32_t crc = S.u[kDfCrc];
-    if (dynbytes >= n + 5u) {
+    if (end == 0u) {
         // -- stored block
         const uint32_t total = kDfHeader + 5u + n + kDfTrailer;
         DF_LANES(t)
@@ -515,53 +626,14 @@ DF_FN void df_member(DfLds& S, const uint8_t* text, uint32_t n, uint8_t* slot, u
         DF_END
         return;
     }
-    // -- dynamic block: every lane's first bit, then the bits
+    // -- dynamic block: the header and the trailer around it
+    const uint32_t dynbytes = (end - kDfHeader * 8u + 7u) / 8u;
     const uint32_t total = kDfHeader + dynbytes + kDfTrailer, owords = (total + 3u) / 4u;
     DF_LANES(t)
-        const uint32_t o1 = (t + 1u) * SC < slen ? (t + 1u) * SC : slen;
-        uint32_t bits = 0;
-        for (uint32_t o = t * SC; o < o1; ++o) {
-            const uint32_t kind = df_kind(S.mbits, o);
-            uint64_t v;
-            if (kind != 2u) bits += df_token_bits(S, o, kind, v);
-        }
-        scan0[t] = bits;
-        for (uint32_t i = t; i < owords + 2u; i += kDfThreads) S.text[i] = 0;   // (total < n + 31: owords + 2 <= kDfTextWords)
-    DF_END
-    for (uint32_t k = 0; k < 8u; ++k) {   // inclusive scan, doubling
-        DF_LANES(t)
-            const uint32_t d = 1u << k;
-            (k & 1u ? scan0 : scan1)[t] = (k & 1u ? scan1 : scan0)[t] + (t >= d ? (k & 1u ? scan1 : scan0)[t - d] : 0u);
-        DF_END
-    }
-    const uint32_t bit0 = kDfHeader * 8u + kDfPreamble + tabbits;   // of the first token
-    DF_LANES(t)
-        uint32_t* out = S.text;
-        const uint32_t o1 = (t + 1u) * SC < slen ? (t + 1u) * SC : slen;
-        uint32_t at = bit0 + (t ? scan0[t - 1u] : 0u);
-        for (uint32_t o = t * SC; o < o1; ++o) {
-            const uint32_t kind = df_kind(S.mbits, o);
-            if (kind == 2u) continue;
-            uint64_t v;
-            const uint32_t nb = df_token_bits(S, o, kind, v);
-            df_put(out, at, v, nb);
-            at += nb;
-        }
-        if (t == kDfThreads - 1u) {   // header, block preamble, the lengths, end of block, trailer
+        if (t == 0u) {
+            uint32_t* out = S.text;
             for (uint32_t i = 0; i < 4u; ++i) df_put(out, 32u * i, df_head_word(i), 32u);
             df_put(out, 128u, total - 1u, 16u);
-            uint32_t b = kDfHeader * 8u;
-            df_put(out, b, 1u | (2u << 1), 3u); b += 3u;          // BFINAL, BTYPE 2
-            df_put(out, b, hlit - 257u, 5u); b += 5u;
-            df_put(out, b, hdist - 1u, 5u); b += 5u;
-            df_put(out, b, 15u, 4u); b += 4u;                     // all 19 lengths of the code-length code
-            // in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15: symbol 0 one bit, 1..16 five bits, 17 and 18 unused
-            for (uint32_t i = 0; i < 19u; ++i) { df_put(out, b, i == 3u ? 1u : (i == 1u || i == 2u ? 0u : 5u), 3u); b += 3u; }
-            for (uint32_t i = 0; i < hlit + hdist; ++i) {
-                const uint32_t l = S.clen[i < hlit ? i : kDfDBase + (i - hlit)];
-                if (l) { df_put(out, b, df_rev(15u + l, 5u), 5u); b += 5u; } else b += 1u;   // (code 0, one bit)
-            }
-            df_put(out, at, S.code[256], S.clen[256]);
             const uint32_t tr = (kDfHeader + dynbytes) * 8u;
             df_put(out, tr, crc, 32u);
             df_put(out, tr + 32u, n, 32u);

@@ -59,6 +59,7 @@
 #include "vk_adapter.h"
 #include "vk_emit.h"
 #include "vk_deflate.h"
+#include "vk_png.h"
 #include "vk_fasta.h"
 #include "vk_fasta_ladder.h"
 #include "vk_fasta_records.h"
@@ -2408,6 +2409,89 @@ int vk_deflate_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, 
     VK_HIP(ctx, hipGetLastError());
     VK_HIP(ctx, hipMemcpyAsync(out_offsets, L.fprefix, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.flens, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- IDAT chunks (vk_png.h) ------
+
+namespace {
+
+// the pieces of a vk_png_device workspace
+struct PngLayout {
+    uint8_t* slots;
+    PngPiece* psums;
+    uint64_t *sizes, *pprefix, *sums, *ilens, *isizes, *iprefix;
+    uint32_t* itail;
+    size_t total;
+    uint64_t npieces;
+    uint32_t ppi, slot;
+};
+
+PngLayout png_layout(void* d_work, uint32_t side, uint32_t nimg) {
+    PngLayout L{};
+    L.ppi = png_pieces(side);
+    L.slot = png_slot(side);
+    L.npieces = static_cast<uint64_t>(nimg) * L.ppi;
+    const uint64_t nb = (L.npieces + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_work), 0};
+    take(L.slots, L.npieces * L.slot);
+    take(L.psums, L.npieces);
+    take(L.sizes, L.npieces);
+    take(L.pprefix, L.npieces + 1);
+    take(L.sums, nb + 1);
+    take(L.ilens, nimg);
+    take(L.isizes, nimg);
+    take(L.iprefix, nimg + 1ull);
+    take(L.itail, 2ull * nimg);
+    L.total = take.at;
+    return L;
+}
+
+bool png_shape_ok(uint32_t side, uint32_t nimg) { return nimg != 0 && side != 0 && side <= kPngMaxSide; }
+
+}  // namespace
+
+extern "C" {
+
+int vk_png_bound(uint32_t side, uint32_t nimg, uint64_t* out_bound) {
+    if (!out_bound || !png_shape_ok(side, nimg)) return VK_EINVAL;
+    *out_bound = png_chunk_bound(side) * nimg;
+    return VK_OK;
+}
+
+int vk_png_workspace_size(uint32_t side, uint32_t nimg, uint64_t* out_bytes) {
+    if (!out_bytes || !png_shape_ok(side, nimg)) return VK_EINVAL;
+    *out_bytes = png_layout(nullptr, side, nimg).total;
+    return VK_OK;
+}
+
+int vk_png_device(vk_ctx* ctx, const void* d_img, uint32_t nimg, uint32_t side, uint8_t* d_out, uint64_t out_capacity, void* d_work,
+                  uint64_t work_bytes, uint64_t* out_offsets, uint64_t* out_lengths) {
+    if (!ctx || !d_img || !d_out || !d_work || !out_offsets || !out_lengths || !png_shape_ok(side, nimg)) return VK_EINVAL;
+    const PngLayout L = png_layout(d_work, side, nimg);
+    if (work_bytes < L.total || L.npieces + nimg > 0x7FFFFFFFull) return VK_EINVAL;
+    if (out_capacity < png_chunk_bound(side) * nimg) return VK_ENOSPC;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(vk_png_piece_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(sizeof(DfLds))));
+    hipLaunchKernelGGL(vk_png_piece_kernel, dim3(static_cast<uint32_t>(L.npieces)), dim3(kDfThreads), sizeof(DfLds), ctx->stream,
+                       static_cast<const uint8_t*>(d_img), side, L.ppi, L.slot, L.slots, L.sizes, L.psums);
+    VK_HIP(ctx, hipGetLastError());
+    int rc = cl_scan(ctx, L.sizes, L.npieces, L.sums, L.pprefix);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_png_image_kernel, dim3((nimg + kDfThreads - 1) / kDfThreads), dim3(kDfThreads), 0, ctx->stream, nimg, L.ppi,
+                       L.psums, L.sizes, L.pprefix, L.ilens, L.isizes, L.itail);
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.isizes, nimg, L.sums, L.iprefix);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_png_gather_kernel, dim3(static_cast<uint32_t>(L.npieces + nimg)), dim3(kDfThreads), 0, ctx->stream,
+                       L.npieces, L.ppi, L.slot, L.slots, L.pprefix, L.ilens, L.iprefix, L.itail, d_out);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(out_offsets, L.iprefix, nimg * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.ilens, nimg * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
     return VK_OK;
 }

@@ -84,6 +84,9 @@ GZ_MAX_FIRST_RATIO = 64
 # VARKODER_AMD_MMAP=1 / 0 forces one or the other; unset: mapped when the rank has fewer than MAPPED_BELOW_THREADS.
 USE_MAPPED_UPLOAD = {"1": True, "0": False}.get(os.environ.get("VARKODER_AMD_MMAP", ""))
 MAPPED_BELOW_THREADS = 16
+# ImageEngine.png: output and workspace of one vk_png_device call at most (a --windows batch of 100,000 images of
+# 16 KiB would otherwise ask for 3.4 GB at once)
+PNG_CALL_BYTES = 512 << 20
 
 
 def plain_route(threads, engine=None):
@@ -949,6 +952,34 @@ class ImageEngine:
                                                        self._ptr(ws), ws.numel(), _u64(out_offs), _u64(out_lens)),
                     "vk_deflate_device")
         return out, out_offs, out_lens
+
+    def png(self, img):
+        """The IDAT chunks of the images img [n, side, side] (a uint8 device tensor), encoded where they lie
+        (vk_png_device): a list of n bytes objects, each a complete chunk (length, "IDAT", zlib stream, CRC-32) that
+        image.write_png_parts puts between a file's head and IEND.  The images are taken in calls whose output and
+        workspace stay within PNG_CALL_BYTES; each call is one copy back of the bytes it wrote.  Synchronises."""
+        torch = _torch()
+        n, side = int(img.shape[0]), int(img.shape[1])
+        if n == 0:
+            return []
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == side and img.is_contiguous()
+        bound, ws_bytes = C.c_uint64(), C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_png_bound(side, 1, C.byref(bound)), "vk_png_bound")
+        _capi.check(self.ctx, self.L.vk_png_workspace_size(side, 1, C.byref(ws_bytes)), "vk_png_workspace_size")
+        per_call = max(1, min(n, PNG_CALL_BYTES // int(bound.value + ws_bytes.value)))
+        _capi.check(self.ctx, self.L.vk_png_bound(side, per_call, C.byref(bound)), "vk_png_bound")
+        _capi.check(self.ctx, self.L.vk_png_workspace_size(side, per_call, C.byref(ws_bytes)), "vk_png_workspace_size")
+        out = torch.empty(int(bound.value), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        offs, lens = np.zeros(per_call, dtype=np.uint64), np.zeros(per_call, dtype=np.uint64)
+        chunks = []
+        for i0 in range(0, n, per_call):
+            m = min(per_call, n - i0)
+            _capi.check(self.ctx, self.L.vk_png_device(self.ctx, self._ptr(img[i0:i0 + m]), m, side, self._ptr(out), out.numel(),
+                                                       self._ptr(ws), ws.numel(), _u64(offs), _u64(lens)), "vk_png_device")
+            host = out[:int(offs[m - 1] + lens[m - 1])].cpu().numpy()
+            chunks.extend(host[int(o):int(o + ln)].tobytes() for o, ln in zip(offs[:m], lens[:m]))
+        return chunks
 
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""

@@ -343,7 +343,7 @@ def _counted(eng, files, pool, batch_bytes):
 def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, fragments=False, fragment_length=150,
                     min_bp=50000, max_bp=None, seeds=None, per_record=False, min_record_length=1000, windows=False,
-                    window_length=10000, window_step=None):
+                    window_length=10000, window_step=None, gpu_png=False):
     """This rank's share of FASTA `files`, each imaged whole.  Returns {sample: OrderedDict(stats)} with the reference's
     keys `<k>mer_counting_time` and `k<k>_img_time`, or `failed_step` for a sample that does not begin with '>', holds
     no base, or could not be read.
@@ -359,14 +359,16 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
 
     windows: every window of window_length bases of a record, one every window_step (default: window_length), is a
     sample of its own (window_names; the rule: INTEGRATION.md, "--from-fasta --windows"), imaged as
-    `image_name(<window sample>, window_length, k, mapping)`; stats and failures as for per_record, per window."""
+    `image_name(<window sample>, window_length, k, mapping)`; stats and failures as for per_record, per window.
+
+    gpu_png: the images' IDAT chunks are made on the GPU (PngSink's encoder), in every one of these modes."""
     files = [Path(f) for f in files]
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded)
     mine = [files[i] for i in shard_by_size(weights, rank, world)]
     stats = OrderedDict()
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
-        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, {}, 0)
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, {}, 0, eng if gpu_png else None)
         if fragments:
             for batch, _, t0 in batches(mine, batch_bytes or DEFAULT_BATCH_BYTES, size=text_bytes):
                 _fragment_images(eng, pool, batch, t0, sink, stats, seeds or {}, fragment_length, min_bp, max_bp, verbose)
@@ -378,7 +380,7 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
         whole = () if fragments or per_record or windows else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
         for batch, hist, st, bases, t0, t1 in whole:
             nz = (hist != 0).any(dim=1).cpu().numpy()
-            imgs = eng.images(hist).cpu().numpy()
+            imgs = sink.rows(eng.images(hist))
             for j, f in enumerate(batch):
                 sample = sample_of(f)
                 s = stats.setdefault(sample, OrderedDict())
@@ -403,7 +405,7 @@ def _record_images(eng, pool, files, batch_bytes, min_len, sink, stats, verbose)
         if hist is None:
             continue
         nz = (hist != 0).any(dim=1).cpu().numpy()
-        imgs = eng.images(hist).cpu().numpy()
+        imgs = sink.rows(eng.images(hist))
         imaged = max(1, int(nz.sum()))
         for g, row in rows.items():
             s = stats.setdefault(samples[g], OrderedDict())
@@ -426,7 +428,7 @@ def _window_images(eng, pool, files, batch_bytes, n, s, sink, stats, verbose):
         if hist is None:
             continue
         nz = (hist != 0).any(dim=1).cpu().numpy()
-        imgs = eng.images(hist).cpu().numpy()
+        imgs = sink.rows(eng.images(hist))
         imaged = max(1, int(nz.sum()))
         for g, w, row in rows:
             name = window_name(samples[g], n, s, w)
@@ -455,7 +457,7 @@ def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp,
     flat = [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
     nz = torch.stack([h for _, _, h in flat]).ne(0).any(dim=1).cpu().numpy() if flat else []
     t1 = time.perf_counter()
-    imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
+    imgs = sink.rows(eng.images(torch.stack([h for _, _, h in flat]))) if flat else []
     for j, f in enumerate(batch):
         s = stats.setdefault(names[j], OrderedDict())
         # (a file that could not be read or inflated is not an empty sample)

@@ -10,6 +10,7 @@ import gzip
 import hashlib
 import struct
 import sys
+import zlib
 from collections import OrderedDict
 from pathlib import Path
 
@@ -130,10 +131,8 @@ def shard_folder(outfolder, outfile, subfolder_levels):
     return outfolder
 
 
-def write_png(arr, path, labels, base_sd, base_sd_thresh, mapping_code):
-    """8-bit "L" PNG, optimize=True, with the four varkoder* text chunks in the reference's order
-    (image.py:920-930)."""
-    from PIL import Image
+def _text_chunks(labels, base_sd, base_sd_thresh, mapping_code):
+    """The four varkoder* text chunks in the reference's order (image.py:920-930), as PIL's PngInfo."""
     from PIL.PngImagePlugin import PngInfo
     chunks = PngInfo()
     for key, value in (("varkoderKeywords", LABELS_SEP.join(labels)),
@@ -141,7 +140,39 @@ def write_png(arr, path, labels, base_sd, base_sd_thresh, mapping_code):
                        ("varkoderLowQualityFlag", str(base_sd > base_sd_thresh)),
                        ("varkoderMapping", mapping_code)):
         chunks.add_text(key, value)
-    Image.fromarray(arr).save(path, optimize=True, pnginfo=chunks)
+    return chunks
+
+
+def write_png(arr, path, labels, base_sd, base_sd_thresh, mapping_code):
+    """8-bit "L" PNG, optimize=True, with the four varkoder* text chunks in the reference's order
+    (image.py:920-930)."""
+    from PIL import Image
+    Image.fromarray(arr).save(path, optimize=True, pnginfo=_text_chunks(labels, base_sd, base_sd_thresh, mapping_code))
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def png_chunk(kind, data):
+    """One PNG chunk: length, type, data, CRC-32 of type and data."""
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+
+PNG_IEND = png_chunk(b"IEND", b"")
+
+
+def png_head(side, labels, base_sd, base_sd_thresh, mapping_code):
+    """Everything of write_png's file in front of the image data, for a side x side image: the signature, IHDR (8-bit
+    greyscale, no interlace) and the four text chunks.  The text chunks are PngInfo.add_text's own (its choice of tEXt
+    or iTXt and its encoding), framed here."""
+    head = PNG_SIGNATURE + png_chunk(b"IHDR", struct.pack(">IIBBBBB", side, side, 8, 0, 0, 0, 0))
+    return head + b"".join(png_chunk(c[0], c[1]) for c in _text_chunks(labels, base_sd, base_sd_thresh, mapping_code).chunks)
+
+
+def write_png_parts(path, head, idat):
+    """A PNG file from png_head's bytes and a complete IDAT chunk (ImageEngine.png)."""
+    with open(path, "wb") as f:
+        f.write(head + idat + PNG_IEND)
 
 
 def _seconds_since(t0):

@@ -17,7 +17,7 @@ from pathlib import Path
 import numpy as np
 
 from .config import QUAL_THRESH, SAMPLE_BP_SEP
-from .image import counts_name, eprint, png_name, shard_folder, stem, write_png
+from .image import counts_name, eprint, png_head, png_name, shard_folder, stem, write_png, write_png_parts
 from .shard import TailQueue, agreed_weights, file_weights, gz_text_bytes, shard_by_size, split_head_tail
 
 
@@ -145,24 +145,39 @@ def engine_scope(engine, k, mapping_code, device, io_threads):
 
 class PngSink:
     """Where an entry point's images go: the output folder (made here) with its md5 sub-folders, the text chunks'
-    sources (labels and base_sd by sample; base_sd may still be filling), the pool that writes and what it has pending."""
+    sources (labels and base_sd by sample; base_sd may still be filling), the pool that writes and what it has pending.
+    encoder: None, or the engine whose png() makes the files' IDAT chunks on the GPU (--gpu-png): the pool's job is then
+    the file's head (image.png_head) and the write."""
 
-    def __init__(self, outdir, pool, k, mapping_code, labels, base_sd, subfolder_levels):
+    def __init__(self, outdir, pool, k, mapping_code, labels, base_sd, subfolder_levels, encoder=None):
         self.outdir, self.pool, self.k, self.mapping_code = Path(outdir), pool, k, mapping_code
-        self.labels, self.base_sd, self.subfolder_levels = labels, base_sd, subfolder_levels
+        self.labels, self.base_sd, self.subfolder_levels, self.encoder = labels, base_sd, subfolder_levels, encoder
         self.pending = []
         self.outdir.mkdir(parents=True, exist_ok=True)
 
     def path(self, name):
         return shard_folder(self.outdir, name, self.subfolder_levels) / name
 
+    def rows(self, img):
+        """What submit takes for each image of a batch's device tensor img [n, side, side], handed over once: the host
+        arrays, or with an encoder the images' IDAT chunks (rows of failed samples are encoded and never asked for)."""
+        if len(img) == 0:
+            return []
+        return self.encoder.png(img) if self.encoder is not None else img.cpu().numpy()
+
     def submit(self, key, sample, name, arr):
-        """Queue image `arr` of `sample` as file `name`; its writing time goes to stats row `key` (finish)."""
+        """Queue image `arr` (a row of rows()) of `sample` as file `name`; its writing time goes to stats row `key` (finish)."""
         path = self.path(name)
         path.parent.mkdir(parents=True, exist_ok=True)
-        self.pending.append((key, time.perf_counter(),
-                             self.pool.submit(write_png, arr.copy(), path, self.labels.get(sample, []),
-                                              self.base_sd.get(sample, 0), QUAL_THRESH, self.mapping_code)))
+        text = (self.labels.get(sample, []), self.base_sd.get(sample, 0), QUAL_THRESH, self.mapping_code)
+        if isinstance(arr, bytes):
+            job = self.pool.submit(self._write_parts, path, arr, *text)
+        else:
+            job = self.pool.submit(write_png, arr.copy(), path, *text)
+        self.pending.append((key, time.perf_counter(), job))
+
+    def _write_parts(self, path, idat, *text):
+        write_png_parts(path, png_head(self.encoder.side, *text), idat)
 
     def finish(self, stats):
         """Wait for every image (a failed write raises here) and add `k<k>_img_time` to its stats row."""
@@ -186,7 +201,7 @@ def sample_weights(samples, world):
 
 def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_sd=None, overwrite=False,
                      subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None, io_threads=8,
-                     engine=None, verbose=False, timings=None, weights=None, tail_frac=0.1):
+                     engine=None, verbose=False, timings=None, weights=None, tail_frac=0.1, gpu_png=False):
     """Process this rank's share of `files`.  Returns {sample_file_stem: OrderedDict(stats)}
     with the reference's stats keys `<k>mer_counting_time` and `k<k>_img_time` (per-file
     share of the batch wall time) or `failed_step` for files whose FASTQ framing is bad.
@@ -196,7 +211,8 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
     timings: optional dict that receives where this thread's wall time went (seconds): waiting for the
     staging thread (`stage_wait_s`), the copy to the device and the inflate (`upload_s`, of which
     `inflate_s`), kernels + copies back (`kernels_s`) and waiting for the last hand-overs and PNGs (`png_tail_s`);
-    `png_submit_s` = handing images to the PNG pool, on a thread of its own since round 5 (not this thread's time); `batches`."""
+    `png_submit_s` = handing images to the PNG pool, on a thread of its own since round 5 (not this thread's time); `batches`.
+    gpu_png: the files' IDAT chunks are made on the GPU (ImageEngine.png) and the pool only writes."""
     files = [Path(f) for f in files]
     if weights is None:   # (a collective only when this call itself is one rank's share of a job: bench.py's per-rank legs call with world = 1 inside a group)
         weights = agreed_weights(files) if world > 1 else file_weights(files)
@@ -217,7 +233,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
     for key in ("stage_wait_s", "upload_s", "inflate_s", "kernels_s", "png_submit_s", "png_tail_s"):
         tm.setdefault(key, 0.0)
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
-        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels, eng if gpu_png else None)
 
         def wanted(fs):
             out = []
@@ -275,7 +291,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
                 tm["upload_s"] += t1 - tu
                 img, hist, status = eng.fastq_to_images(dev, offs, lens)
                 st = status.cpu().numpy()
-                imgs = img.cpu().numpy()
+                imgs = sink.rows(img)
                 nz = (hist != 0).any(dim=1).cpu().numpy()
                 t2 = time.perf_counter()
                 tm["kernels_s"] += t2 - t1
@@ -318,7 +334,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False,
-                    gpu_gzip=False):
+                    gpu_gzip=False, gpu_png=False):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
@@ -327,7 +343,7 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     split_dir: also write every step's reads to `split_dir/<sample>@<bp>K.fq.gz` (SplitSink), as the reference's
     split_fastq leaves them; overwrite: also where a sample's files are all there.  no_image (with split_dir: the
     reference's -X, :1055): stop after step C -- no counting, no PNG.  gpu_gzip: the files are compressed on the GPU
-    (SplitSink).
+    (SplitSink).  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -339,7 +355,7 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     if batch_bytes is None:
         batch_bytes = DEFAULT_GZ_BATCH_BYTES if mine and all(f.suffix == ".gz" for f in mine) else DEFAULT_BATCH_BYTES
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
-        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels)
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels, eng if gpu_png else None)
         splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
         for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
@@ -478,7 +494,7 @@ def _ladder_images(eng, text, offs, lens, names, sources, t0, sink, stats, seeds
         splits.emit(eng, text, offs, lens, names, recs, seeds, **ladder)
     t1 = time.perf_counter()
     flat = [] if no_image else [(j, bp, h) for j, r in enumerate(recs) for bp, h, _ in r["steps"]]
-    imgs = eng.images(torch.stack([h for _, _, h in flat])).cpu().numpy() if flat else []
+    imgs = sink.rows(eng.images(torch.stack([h for _, _, h in flat]))) if flat else []
     nz = [bool((h != 0).any().item()) for _, _, h in flat]
     t2 = time.perf_counter()
     for j, s in enumerate(names):
@@ -728,7 +744,8 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
 def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, trim=(10, 10), adapter=True,
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
-                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None):
+                  detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None,
+                  gpu_png=False):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -740,7 +757,7 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     batch (ImageEngine.detect_adapters) after the read budget.  The JSON then holds `adapter_cutting`.
 
     split_dir, overwrite, no_image: as clean_to_images takes them.  gpu_gzip: the .fq.gz files of clean_dir and split_dir
-    are compressed on the GPU (ImageEngine.deflate: BGZF) and only their bytes are copied back.
+    are compressed on the GPU (ImageEngine.deflate: BGZF) and only their bytes are copied back.  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).
 
     bam = {"pairs": bool, "exclude": int}: `--from-bam` -- every sample is ONE BAM file, converted to FASTQ text in HBM
     between the upload and the cleaning (_bam_texts; the rule: INTEGRATION.md, "--from-bam: the rule").
@@ -752,7 +769,7 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, bam)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
-        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels)
+        sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels, eng if gpu_png else None)
         splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
         for out, ooffs, olens, names, tc in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
                                                            batch_bytes or DEFAULT_BATCH_BYTES, verbose):
