@@ -392,7 +392,31 @@ int vk_png_workspace_size(uint32_t side, uint32_t nimg, uint64_t* out_bytes);
 int vk_png_device(vk_ctx* ctx, const void* d_img, uint32_t nimg, uint32_t side, uint8_t* d_out, uint64_t out_capacity,
                   void* d_work, uint64_t work_bytes, uint64_t* out_offsets, uint64_t* out_lengths);
 
-/* Replaces: dsk on a FASTA input, `dsk -kmer-size k -abundance-min 1 -file IN.fa` (commands/image.py:771-796; the real dsk
+/* PNG files read back: replaces PIL's decode behind `Image.open` where a command starts from a folder of images
+ * (commands/train.py and commands/query.py: `np.array(Image.open(p))`, one host thread) for 8-bit greyscale files of
+ * side x side pixels.  Stream i is d_streams[offsets[i] .. +lengths[i]): the file's zlib stream (its IDAT payloads joined
+ * in file order) from its 2-byte header to its Adler-32, and behind that four bytes more that the caller appends:
+ * side * (side + 1), the bytes the stream must inflate to, as a little-endian u32.  offsets are multiples of 16; offsets and
+ * lengths are host arrays.  The header's two bytes are the caller's to judge (CM 8, no dictionary) and are skipped here.
+ * Image i is inflated by one wavefront (the decoder of vk_inflate_device) and un-filtered by one (filters 0 None, 1 Sub,
+ * 2 Up, 3 Average, 4 Paeth of the PNG specification, per row) into d_img[i][side][side]; the stream's Adler-32 is
+ * taken on the way and compared.  status[i] (a host array, out) is 0 or a sum of the bits below.  An image whose status
+ * is not 0 has unspecified pixels inside its own side * side bytes; nothing outside them is written.
+ *
+ * vk_unpng_workspace_size: the bytes of d_work (per image a slot of side * (side + 1) bytes rounded up to 16, and tables).
+ * vk_unpng_device: every argument is checked before anything is launched: VK_EINVAL for a null pointer, nimg 0, side 0 or
+ * above 512, an offset that is not a multiple of 16, a length below 2 + 4 + 4, or a workspace that is too small (d_img
+ * untouched).  The number of launches does not depend on nimg.  The call synchronises. */
+#define VK_UNPNG_BAD_STREAM 1u   /* a block the decoder refuses */
+#define VK_UNPNG_TRUNCATED  2u
+#define VK_UNPNG_BAD_SIZE   4u   /* does not inflate to side * (side + 1) bytes */
+#define VK_UNPNG_BAD_ADLER  8u
+#define VK_UNPNG_BAD_FILTER 16u  /* a row's filter byte above 4 */
+int vk_unpng_workspace_size(uint32_t side, uint32_t nimg, uint64_t* out_bytes);
+int vk_unpng_device(vk_ctx* ctx, const void* d_streams, const uint64_t* offsets, const uint64_t* lengths, uint32_t nimg,
+                    uint32_t side, uint8_t* d_img, uint32_t* status, void* d_work, uint64_t work_bytes);
+
+/* Replaces: dsk on a FASTA input,`dsk -kmer-size k -abundance-min 1 -file IN.fa` (commands/image.py:771-796; the real dsk
  * reads FASTA as well as FASTQ), for a batch of samples resident in HBM, laid out as for vk_count_device (offsets multiples
  * of 16, readable up to the last sample's 16-byte rounded end).  The rule is this project's ("--from-fasta";
  * tests/fasta_ref.py): a line ends at '\n', a '\r' directly before it or as the sample's last byte belongs to the line end;

@@ -60,6 +60,7 @@
 #include "vk_emit.h"
 #include "vk_deflate.h"
 #include "vk_png.h"
+#include "vk_unpng.h"
 #include "vk_fasta.h"
 #include "vk_fasta_ladder.h"
 #include "vk_fasta_records.h"
@@ -2493,6 +2494,64 @@ int vk_png_device(vk_ctx* ctx, const void* d_img, uint32_t nimg, uint32_t side, 
     VK_HIP(ctx, hipMemcpyAsync(out_offsets, L.iprefix, nimg * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipMemcpyAsync(out_lengths, L.ilens, nimg * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the tables above are the host's)
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- PNG files read (vk_unpng.h) ------
+
+namespace {
+
+// the pieces of a vk_unpng_device workspace
+struct UnpngLayout {
+    uint8_t* slots;
+    uint64_t *offs, *lens;
+    uint32_t *st, *adler, *status;
+    size_t total;
+};
+
+UnpngLayout unpng_layout(void* d_work, uint32_t side, uint32_t nimg) {
+    UnpngLayout L{};
+    WsTake take{static_cast<uint8_t*>(d_work), 0};
+    take(L.slots, static_cast<size_t>(nimg) * unpng_slot(side));
+    take(L.offs, nimg);
+    take(L.lens, nimg);
+    take(L.st, nimg);
+    take(L.adler, nimg);
+    take(L.status, nimg);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_unpng_workspace_size(uint32_t side, uint32_t nimg, uint64_t* out_bytes) {
+    if (!out_bytes || !png_shape_ok(side, nimg)) return VK_EINVAL;
+    *out_bytes = unpng_layout(nullptr, side, nimg).total;
+    return VK_OK;
+}
+
+int vk_unpng_device(vk_ctx* ctx, const void* d_streams, const uint64_t* offsets, const uint64_t* lengths, uint32_t nimg, uint32_t side,
+                    uint8_t* d_img, uint32_t* status, void* d_work, uint64_t work_bytes) {
+    if (!ctx || !d_streams || !offsets || !lengths || !d_img || !status || !d_work || !png_shape_ok(side, nimg)) return VK_EINVAL;
+    for (uint32_t i = 0; i < nimg; ++i)
+        if ((offsets[i] & 15u) || lengths[i] < kUpStreamMin) return VK_EINVAL;
+    const UnpngLayout L = unpng_layout(d_work, side, nimg);
+    if (work_bytes < L.total) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipMemcpyAsync(L.offs, offsets, nimg * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.lens, lengths, nimg * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(vk_unpng_inflate_kernel, dim3(nimg), dim3(64), 0, ctx->stream, static_cast<const uint8_t*>(d_streams), L.offs,
+                       L.lens, nimg, side, L.slots, L.st, L.adler);
+    VK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(vk_unpng_unfilter_kernel, dim3(nimg), dim3(kUpLanes), unpng_lds_words(side) * 4u, ctx->stream, L.slots, nimg, side,
+                       L.st, L.adler, d_img, L.status);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(status, L.status, nimg * 4ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (status is the host's)
     return VK_OK;
 }
 

@@ -981,6 +981,44 @@ class ImageEngine:
             chunks.extend(host[int(o):int(o + ln)].tobytes() for o, ln in zip(offs[:m], lens[:m]))
         return chunks
 
+    def unpng(self, streams, side):
+        """The images of n PNG files' zlib streams, decoded on the GPU (vk_unpng_device): a uint8 device tensor
+        [n, side, side] and the status array [n] (0, or VK_UNPNG_* bits: that image's pixels mean nothing).
+        streams = (buffer, offsets, lengths): a host uint8 tensor or array laid out as pngread.pack_streams does (every
+        stream at a multiple of 16, the four length bytes behind it, pngread.SLACK bytes behind the last).  The streams
+        are taken in calls whose bytes, images and workspace stay within PNG_CALL_BYTES.  Synchronises."""
+        torch = _torch()
+        buf, offs, lens = streams
+        buf = buf if torch.is_tensor(buf) else torch.from_numpy(buf)
+        offs, lens = np.ascontiguousarray(offs, dtype=np.uint64), np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(offs)
+        img = torch.empty((n, side, side), dtype=torch.uint8, device=self.device)
+        status = np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return img, status
+        ws1 = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_unpng_workspace_size(side, 1, C.byref(ws1)), "vk_unpng_workspace_size")
+        ends = np.append(offs[1:], np.uint64((int(offs[-1] + lens[-1]) + 15) // 16 * 16)).astype(np.int64)
+        i0 = 0
+        while i0 < n:
+            # as many images as fit the budget (at least one): their streams, and per image a workspace share
+            base = int(offs[i0])
+            cost = (ends[i0:] - base) + (np.arange(1, n - i0 + 1, dtype=np.int64) * int(ws1.value + 64))
+            m = max(1, int(np.searchsorted(cost, PNG_CALL_BYTES, side="right")))
+            ws_bytes = C.c_uint64()
+            _capi.check(self.ctx, self.L.vk_unpng_workspace_size(side, m, C.byref(ws_bytes)), "vk_unpng_workspace_size")
+            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+            end = int(ends[i0 + m - 1])
+            dev = torch.zeros(end - base + 1024, dtype=torch.uint8, device=self.device)
+            dev[:end - base].copy_(buf[base:end])
+            rel = offs[i0:i0 + m] - np.uint64(base)
+            st = status[i0:i0 + m].ctypes.data_as(C.POINTER(C.c_uint32))
+            _capi.check(self.ctx, self.L.vk_unpng_device(self.ctx, self._ptr(dev), _u64(rel), _u64(lens[i0:i0 + m]), m, side,
+                                                         self._ptr(img[i0:i0 + m]), st, self._ptr(ws), ws.numel()),
+                        "vk_unpng_device")
+            i0 += m
+        return img, status
+
     def images(self, hist, img=None):
         """K2: uint8 images [n, side, side] from histograms [n, 4^k]."""
         torch = _torch()

@@ -402,11 +402,29 @@ def refuse_early(args):
         raise Exception("Output directory exists, use --overwrite if you want to overwrite it.")
 
 
+def image_set(paths, eng=None):
+    """The training set's images, uint8 [n, side, side]: decoded by PIL on the host (a CPU tensor: the caller moves it),
+    or with an engine by pngread.read_images where they will stay (a device tensor; --gpu-png-read).  Both routes give
+    the same bytes and refuse the same sets with the same message."""
+    import torch
+    from PIL import Image
+    message = "Images of different sizes in one training run are not supported."
+    if eng is not None:
+        from .pngread import read_images
+        images = read_images(eng, paths, mixed=message)
+        if images.dim() != 3 or images.shape[1] != images.shape[2]:
+            raise Exception(message)
+        return images.to(torch.uint8)
+    arrays = [np.array(Image.open(p)) for p in paths]
+    if len({a.shape for a in arrays}) > 1 or arrays[0].ndim != 2 or arrays[0].shape[0] != arrays[0].shape[1]:
+        raise Exception(message)
+    return torch.from_numpy(np.stack(arrays).astype(np.uint8))
+
+
 def run_train(args):
     """The `train` sub-command; returns the per-epoch history (a list of dicts: phase, epoch, train_loss and, unless -M,
     valid_loss with accuracy or precision / recall)."""
     import torch
-    from PIL import Image
     from .engine import ImageEngine
     from .shard import world_info
     refuse_early(args)
@@ -425,28 +443,29 @@ def run_train(args):
     B = batch_size(len(train_rows), args.min_batch_size, args.max_batch_size)
     if B > len(train_rows):
         raise Exception(f"Batch size {B} exceeds the {len(train_rows)} training images (the last short batch is dropped).")
-    arrays = [np.array(Image.open(p)) for p in df["path"]]
-    if len({a.shape for a in arrays}) > 1 or arrays[0].ndim != 2 or arrays[0].shape[0] != arrays[0].shape[1]:
-        raise Exception("Images of different sizes in one training run are not supported.")
-    side = arrays[0].shape[0]
-
-    eprint("Setting up neural network model for training.")
-    seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(4), "little")
-    torch.manual_seed(seed)
-    gen = torch.Generator().manual_seed(seed)
-    model, out_size = build_model(args.architecture, len(vocab), side, getattr(args, "input_size", None))
-    if args.pretrained_model:
-        eprint("Loading pretrained model from file:", str(args.pretrained_model))
-        eprint(load_matching_weights(model, args.pretrained_model), "tensors taken from it.")
-    else:
-        eprint("Starting model with random weights.")
-    eprint("Model architecture:", args.architecture)
-
     device = world_info()[2]
-    eng = ImageEngine(k=int(df["img_kmer_size"].iloc[0]), mapping="cgr", device=device)
+    k = int(df["img_kmer_size"].iloc[0])
+    # --gpu-png-read: the engine decodes the files, so it exists before the model does
+    eng = ImageEngine(k=k, mapping="cgr", device=device) if getattr(args, "gpu_png_read", False) else None
     try:
-        images = torch.from_numpy(np.stack(arrays).astype(np.uint8)).to(eng.device)   # resident from here on
-        del arrays
+        images = image_set(df["path"], eng)
+        side = int(images.shape[1])
+
+        eprint("Setting up neural network model for training.")
+        seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(4), "little")
+        torch.manual_seed(seed)
+        gen = torch.Generator().manual_seed(seed)
+        model, out_size = build_model(args.architecture, len(vocab), side, getattr(args, "input_size", None))
+        if args.pretrained_model:
+            eprint("Loading pretrained model from file:", str(args.pretrained_model))
+            eprint(load_matching_weights(model, args.pretrained_model), "tensors taken from it.")
+        else:
+            eprint("Starting model with random weights.")
+        eprint("Model architecture:", args.architecture)
+
+        if eng is None:
+            eng = ImageEngine(k=k, mapping="cgr", device=device)
+        images = images.to(eng.device)   # resident from here on
         y_dev = torch.from_numpy(y_all).to(eng.device)
         model = model.to(eng.device)
         keep = [i for i, v in enumerate(vocab) if v != LOW_QUALITY_LABEL]
@@ -535,7 +554,8 @@ def run_train(args):
         phase("unfrozen", args.epochs, list(model.parameters()), args.base_learning_rate / 2.0, 5.0, 0.3)
         torch.cuda.synchronize(eng.device)
     finally:
-        eng.close()
+        if eng is not None:
+            eng.close()
 
     outdir = Path(args.outdir)
     outdir.mkdir(parents=True, exist_ok=True)
