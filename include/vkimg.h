@@ -562,6 +562,69 @@ int vk_bam_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets,
  * missing. */
 int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked);
 
+#define VK_BAM_BAD_AUX 3u               /* an aux field in front of a read's RG field does not parse (the grouped calls only) */
+#define VK_BAM_UNGROUPED 0xFFFFFFFFu    /* a stream's `group`: the reads that belong to no group of their file's table */
+#define VK_BAM_MAX_GROUPS 1024u         /* groups of one file */
+
+/* Replaces: `samtools split` (or `dorado demux`) and then `samtools fastq` on the host (the rule is this project's:
+ * INTEGRATION.md, "--from-bam --bam-read-groups: the rule"; tests/bam_groups_ref.py) -- vk_bam_frame_device with the reads
+ * of a file split by read group (SAM spec 1.3 for @RG, 4.2.4 for the aux fields).  The arguments of vk_bam_frame_device, and:
+ * file i has the groups group_first[i] .. group_first[i + 1] (at most VK_BAM_MAX_GROUPS) of the call's table, group g's ID
+ * is id_bytes[id_first[g] .. id_first[g + 1]) (1 to 255 bytes, no two equal within a file; all host arrays).  A read's
+ * group is the one whose ID equals, byte for byte, the value of the FIRST aux field with tag RG when its type is Z; a read
+ * whose first RG field has another type or a value that is no ID of the file (or runs to the block's end without NUL), or
+ * that has no RG field, is ungrouped.  The fields are walked in order from the end of the qualities (types A c C s S i I
+ * f Z H B, B's subtypes c C s S i I f); nothing behind the deciding field is looked at.  A field in front of it with
+ * another type or subtype, whose value or NUL lies past the block's end, or fewer than 3 bytes left over, give the file
+ * the status VK_BAM_BAD_AUX -- only when the framing is good (VK_BAM_BAD_RECORD and VK_BAM_TRUNCATED come first), and
+ * only for reads: a record that is no read is not walked.  Stream s takes the reads stream_select[s] of group
+ * stream_group[s] (an index into the file's groups, or VK_BAM_UNGROUPED) of file stream_file[s]; a read goes to at most
+ * one stream, and reads that no stream takes are passed over.  VK_EINVAL, before anything is launched, for what
+ * vk_bam_frame_device refuses, a stream_group at or past the file's count, a file of more than VK_BAM_MAX_GROUPS groups,
+ * an ID of 0 or more than 255 bytes or twice in a file, a (file, select, group) named twice, and a file whose streams mix
+ * VK_BAM_ALL with the class selects.  Nothing is read outside a file's bytes: every aux length is checked against the
+ * block's end before it is followed.  Synchronises. */
+int vk_bam_groups_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                               const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles,
+                               const uint32_t* group_first, const uint32_t* id_first, const uint8_t* id_bytes,
+                               const uint32_t* stream_file, const uint32_t* stream_select, const uint32_t* stream_group,
+                               uint32_t nstreams, uint32_t exclude, uint32_t flags, uint64_t* out_records,
+                               uint64_t* out_bytes, uint32_t* status);
+
+/* Replaces: `samtools split` and `samtools fastq` (as above) -- the text, as vk_bam_fastq_device writes it and under its
+ * slot rules: nothing is written outside a stream's slot, a stream whose text does not fit gets none (out_lengths[s] =
+ * 0), and VK_ENOSPC is returned once the other streams are written.  Reads keep the file's order within a stream.  The
+ * files are cut into PANELS of VKIMG_BAM_PANEL_SEGS segments (read when the context is made; 1 to 4096, 4 by default);
+ * the emit pass runs one workgroup per panel, whatever the number of streams (vk_bam_groups.h).  Synchronises. */
+int vk_bam_groups_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                               const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles,
+                               const uint32_t* group_first, const uint32_t* id_first, const uint8_t* id_bytes,
+                               const uint32_t* stream_file, const uint32_t* stream_select, const uint32_t* stream_group,
+                               uint32_t nstreams, uint32_t exclude, uint32_t flags, void* d_out,
+                               const uint64_t* out_offsets, const uint64_t* out_caps, uint64_t* out_lengths,
+                               uint32_t* status);
+
+/* Host only: the bytes of workspace a grouped call takes beyond those of the ungrouped calls, for segments of seg_bytes
+ * and panels of panel_segs segments (0: the defaults, 65536 and 4).  With S_i = max(1, ceil(lengths[i] / seg_bytes))
+ * segments, P_i = ceil(S_i / panel_segs) panels, G_i groups and L_i streams of file i, and every piece rounded up to 256
+ * bytes:
+ *     the ID bytes + 4 (4 nfiles + 2 + sum G_i + 1 + sum T_i + 3 nstreams) + 2 sum 3 (G_i + 1)
+ *     + 8 (2 nfiles + 1) + 16 nstreams          (tables; T_i = the power of two >= max(2, 2 G_i): the hash table)
+ *     + 4 nfiles + 8                            (aux statuses, counters)
+ *     + 2 (seg_bytes / 37 + 2) sum S_i          (a u16 note per record start)
+ *     + 16 sum P_i L_i + 16 nstreams            (a row of two u64 per panel and stream; the totals)
+ * A file of 1 GiB with 1024 groups x 3 classes: 16384 segments, 4096 panels, 3072 streams -- 58 MB of notes and 201 MB of
+ * rows; with 96 groups, 6 MB of rows.  VK_EINVAL for a null pointer, a stream_file of nfiles or more, seg_bytes outside 64 .. 65536, panel_segs above
+ * 4096. */
+int vk_bam_groups_workspace_size(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first,
+                                 const uint32_t* id_first, const uint32_t* stream_file, uint32_t nstreams,
+                                 uint32_t seg_bytes, uint32_t panel_segs, uint64_t* bytes);
+
+/* Introspection (tests, tools/bam_time.py): of the last vk_bam_groups_frame_device / vk_bam_groups_fastq_device call,
+ * the workgroups of its emit launch (0 for the framing call) and the records whose aux fields (SAM spec 4.2.4) were
+ * walked. */
+int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* walked);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

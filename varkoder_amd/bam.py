@@ -93,10 +93,8 @@ class _Head:
         return struct.unpack_from("<i", self.buf, at)[0]
 
 
-def bam_header(path):
-    """(first_record, n_ref, sort_order) of a BAM file: the offset of its first record in the inflated bytes, the
-    references its header names and what its `@HD` line says behind `SO:` ("unknown" without one).  Only the BGZF members
-    the header lies in are inflated (zlib).  BamError for a file that is not BAM or whose header does not parse."""
+def _header(path):
+    """(first_record, n_ref, the header's text) of a BAM file: bam_header and read_groups parse it."""
     size = os.path.getsize(path)
     with open(path, "rb") as fh:
         head = _Head(fh, size)
@@ -120,16 +118,90 @@ def bam_header(path):
                 raise BamError("negative l_name")
             head.need(at + 4 + l_name + 4)
             at += 8 + l_name
+    return at, n_ref, text
+
+
+def bam_header(path):
+    """(first_record, n_ref, sort_order) of a BAM file: the offset of its first record in the inflated bytes, the
+    references its header names and what its `@HD` line says behind `SO:` ("unknown" without one).  Only the BGZF members
+    the header lies in are inflated (zlib).  BamError for a file that is not BAM or whose header does not parse."""
+    at, n_ref, text = _header(path)
+    return at, n_ref, _sort_order(text)
+
+
+def _sort_order(text):
     order = "unknown"
     first = text.split(b"\n", 1)[0]
     if first.startswith(b"@HD"):
         for field in first.split(b"\t")[1:]:
             if field.startswith(b"SO:"):
                 order = field[3:].rstrip(b"\r\0").decode("latin-1")
-    return at, n_ref, order
+    return order
+
+
+MAX_GROUPS = _capi.VK_BAM_MAX_GROUPS
+MAX_ID_BYTES = 255
+GROUP_ID_BYTES = 100   # of a group's id in its sample name (fasta.RECORD_ID_BYTES)
+
+
+def groups_of_text(text):
+    """The read groups of a header's text: the `ID:` fields (bytes) of its `@RG` lines, in header order (SAM spec 1.3).
+    BamError for an `@RG` line without `ID:` (or with an empty one), an ID of more than 255 bytes, an ID twice, more than
+    VK_BAM_MAX_GROUPS groups."""
+    ids, seen = [], set()
+    for line in text.split(b"\n"):
+        line = line.rstrip(b"\r\0")
+        if line != b"@RG" and not line.startswith(b"@RG\t"):
+            continue
+        rid = next((f[3:] for f in line.split(b"\t")[1:] if f.startswith(b"ID:")), b"")
+        if not rid:
+            raise BamError("an @RG line without ID:")
+        if len(rid) > MAX_ID_BYTES:
+            raise BamError("a read group ID of more than %d bytes" % MAX_ID_BYTES)
+        if rid in seen:
+            raise BamError("read group ID %s twice" % rid.decode("latin-1"))
+        seen.add(rid)
+        ids.append(rid)
+        if len(ids) > MAX_GROUPS:
+            raise BamError("more than %d read groups" % MAX_GROUPS)
+    return ids
+
+
+def read_groups(path):
+    """The read groups of a BAM file (groups_of_text of its header), read once per file as it stands on disk (cached
+    beside file_info, by its key); BamError as bam_header raises it, or for a header whose @RG lines break the rule
+    (INTEGRATION.md, "--from-bam --bam-read-groups: the rule")."""
+    st = os.stat(path)
+    key = (str(path), st.st_size, st.st_mtime_ns)
+    if key not in _GROUPS:
+        try:
+            _GROUPS[key] = groups_of_text(_header(path)[2])
+        except (BamError, ValueError) as e:
+            _GROUPS[key] = BamError(str(e) or type(e).__name__)
+    if isinstance(_GROUPS[key], BamError):
+        raise _GROUPS[key]
+    return list(_GROUPS[key])
+
+
+def group_names(file_sample, ids):
+    """The sample names of a file's groups: `<file sample>__<id>`, the id cleaned and cut as fasta.record_names cleans a
+    record's (every byte outside [A-Za-z0-9._-] replaced by '_', at most GROUP_ID_BYTES).  BamError when two groups of
+    the file come to one name."""
+    out, seen = [], {}
+    for rid in ids:
+        clean = "".join(chr(b) if (48 <= b <= 57 or 65 <= b <= 90 or 97 <= b <= 122 or b in b"._-") else "_"
+                        for b in bytes(rid)[:GROUP_ID_BYTES])
+        name = f"{file_sample}__{clean}"
+        if name in seen:
+            raise BamError("read groups %s and %s both give the sample %s" % (seen[name].decode("latin-1"),
+                                                                               bytes(rid).decode("latin-1"), name))
+        seen[name] = bytes(rid)
+        out.append(name)
+    return out
 
 
 _INFO = {}   # (path, size, mtime) -> (inflated size, header) or the BamError
+_GROUPS = {}   # the same key -> the read groups or the BamError
 
 
 def file_info(path):
@@ -171,13 +243,39 @@ def batch_bytes(path):
     return n + n * 4 // 3 + FASTQ_SLACK
 
 
-def sample_plan(path, pairs=False):
+def sample_plan(path, pairs=False, group=None):
     """A sample's streams [(file, role, select)] in the order step B reads a sample's files (pipeline._sample_files):
-    single-end first, then R1, then R2."""
+    single-end first, then R1, then R2.  group (`--bam-read-groups`: an index into read_groups(path), or
+    VK_BAM_UNGROUPED): [(file, role, select, group)], the streams of that group's reads."""
+    more = () if group is None else (group,)
     if not pairs:
-        return [(path, _capi.VK_CL_ROLE_UNPAIRED, _capi.VK_BAM_ALL)]
-    return [(path, _capi.VK_CL_ROLE_UNPAIRED, _capi.VK_BAM_SINGLE), (path, _capi.VK_CL_ROLE_R1, _capi.VK_BAM_READ1),
-            (path, _capi.VK_CL_ROLE_R2, _capi.VK_BAM_READ2)]
+        return [(path, _capi.VK_CL_ROLE_UNPAIRED, _capi.VK_BAM_ALL) + more]
+    return [(path, _capi.VK_CL_ROLE_UNPAIRED, _capi.VK_BAM_SINGLE) + more, (path, _capi.VK_CL_ROLE_R1, _capi.VK_BAM_READ1) + more,
+            (path, _capi.VK_CL_ROLE_R2, _capi.VK_BAM_READ2) + more]
+
+
+def group_samples(files):
+    """`--bam-read-groups`: ([(sample, file, group index)] for every group of every file, in file and header order,
+    {file: why it has no samples}).  A file that is not BAM or whose @RG lines break the rule has none (the reason is
+    reported, the run goes on); a file without @RG lines has none either.  A group sample that is also another file's
+    sample or another file's group sample is the error that two BAM files of one sample are."""
+    out, why = [], {}
+    taken = {sample_of(f): f for f in files}
+    for f in files:
+        try:
+            ids = read_groups(f)
+            names = group_names(sample_of(f), ids)
+        except (BamError, OSError) as e:
+            why[f] = str(e) or type(e).__name__
+            continue
+        if not ids:
+            why[f] = "no @RG line in the header: no read groups, no samples"
+        for g, name in enumerate(names):
+            if name in taken:
+                raise Exception(f"Two BAM files for sample {name}: {Path(taken[name]).name} and {Path(f).name}")
+            taken[name] = f
+            out.append((name, f, g))
+    return out, why
 
 
 def check_pairs(files):

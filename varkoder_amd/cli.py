@@ -253,6 +253,10 @@ def add_bam_flags(p):
                    help="with --from-bam: a file's first mates (flag & 0xC1 == 0x41), second mates (0x81) and other reads "
                         "are the R1, R2 and unpaired files of its sample; mates must appear in the same order (unaligned "
                         "or collated BAMs): a file sorted by coordinate is refused")
+    p.add_argument("--bam-read-groups", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="with --from-bam: every read group of a file (the ID: of an @RG line of its header) is a sample "
+                        "`<file>__<id>` of the reads whose RG:Z tag names it, split on the GPU; reads of no listed group are "
+                        "passed over and counted on stderr (INTEGRATION.md, \"--from-bam --bam-read-groups: the rule\")")
     p.add_argument("--bam-exclude", type=lambda t: int(t, 0), default=argparse.SUPPRESS, metavar="INT",
                    help="with --from-bam: records with any of these flag bits are passed over (0x900 when absent: "
                         "secondary and supplementary, as `samtools fastq`; 0xF00 also drops QC-fail and duplicates)")
@@ -263,7 +267,8 @@ def bam_options(args):
     if not getattr(args, "from_bam", False):
         return None
     from .bam import EXCLUDE_DEFAULT
-    return dict(pairs=getattr(args, "bam_pairs", False), exclude=getattr(args, "bam_exclude", EXCLUDE_DEFAULT))
+    return dict(pairs=getattr(args, "bam_pairs", False), exclude=getattr(args, "bam_exclude", EXCLUDE_DEFAULT),
+                groups={} if getattr(args, "bam_read_groups", False) else None)   # ({sample: group}: filled by RawPlan)
 
 
 def add_record_flags(p):
@@ -315,7 +320,7 @@ def parse_args(argv=None):
         if hasattr(args, "bam_exclude") and not 0 <= args.bam_exclude <= 0xFFFF:
             parser.error("--bam-exclude: 0 to 0xFFFF")
     if args.command in ("image", "query") and not from_bam:
-        for name, flag in (("bam_pairs", "--bam-pairs"), ("bam_exclude", "--bam-exclude")):
+        for name, flag in (("bam_pairs", "--bam-pairs"), ("bam_exclude", "--bam-exclude"), ("bam_read_groups", "--bam-read-groups")):
             if hasattr(args, name):
                 parser.error(f"{flag}: only with --from-bam")
     if getattr(args, "from_fasta", False):   # one image per file, nothing written but images: no ladder, no intermediates
@@ -649,7 +654,17 @@ class RawPlan:
             from .bam import bam_files, sample_of
             files = bam_files(src)
             labels = {} if is_query else read_labels(getattr(args, "labels_csv", None))
-            table = [(sample_of(f), ["query"] if is_query else labels.get(sample_of(f), []), [f]) for f in files]
+            if self.bam["groups"] is not None:   # every read group of every file is one sample; a label by group sample first, then by its file's
+                from .bam import group_samples
+                from .fasta import RecordLabels
+                members, why = group_samples(files)
+                for f, reason in why.items():
+                    eprint(f"{f}: {reason}")
+                labels = RecordLabels(labels, [sample_of(f) for f in files])
+                table = [(s, ["query"] if is_query else labels.get(s, []), [f]) for s, f, _ in members]
+                self.bam["groups"] = {s: g for s, _, g in members}
+            else:
+                table = [(sample_of(f), ["query"] if is_query else labels.get(sample_of(f), []), [f]) for f in files]
         else:
             table = process_input(args.input, is_query=is_query)
         self.args = args
@@ -824,7 +839,10 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
         error = e
-    finish_image_job(args, outdir, rank, world, per_sample, error, samples=plan.samples, labels=plan.labels, base_sd=base_sd)
+    # (--bam-read-groups: a group without reads is no sample; the samples are those that came through)
+    grouped = plan.bam is not None and plan.bam["groups"] is not None
+    finish_image_job(args, outdir, rank, world, per_sample, error, samples=None if grouped else plan.samples, labels=plan.labels,
+                     base_sd=base_sd)
 
 
 def failpoint(rank):

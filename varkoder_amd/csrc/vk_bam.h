@@ -170,8 +170,13 @@ __device__ inline uint8_t bam_base(uint32_t code, uint32_t reverse) {
     return static_cast<uint8_t>(((code & 8u) ? hi : lo) >> (8 * (code & 7u)));
 }
 
+// The per-byte routine and what wraps it are inlined into every kernel that writes text (two do: vk_bam_emit_kernel here,
+// vk_bam_groups_emit_kernel in vk_bam_groups.h): left to the compiler, a second caller turns bam_emit_item into a call and
+// the emit pass loses a fifth of its speed.
+#define VK_BAM_INLINE __attribute__((always_inline))
+
 // Byte i of a read's text: '@' name '\n' SEQ '\n' '+' '\n' QUAL '\n'.
-__device__ inline uint8_t bam_text_byte(const BamEmit& e, uint64_t i) {
+__device__ inline VK_BAM_INLINE uint8_t bam_text_byte(const BamEmit& e, uint64_t i) {
     if (i == 0) return '@';
     if (i < e.l_name) return e.rec[32 + i - 1];
     if (i == e.l_name) return '\n';
@@ -198,14 +203,14 @@ struct alignas(16) BamQuad {
     uint32_t w[4];
 };
 
-__device__ inline uint32_t bam_text_word(const BamEmit& e, uint64_t i) {
+__device__ inline VK_BAM_INLINE uint32_t bam_text_word(const BamEmit& e, uint64_t i) {
     return bam_text_byte(e, i) | static_cast<uint32_t>(bam_text_byte(e, i + 1)) << 8 |
            static_cast<uint32_t>(bam_text_byte(e, i + 2)) << 16 | static_cast<uint32_t>(bam_text_byte(e, i + 3)) << 24;
 }
 
 // Bytes [lo, hi) of a read's text to out (the place of byte lo), each store as wide as the output's alignment allows:
 // bytes up to a dword boundary, dwords up to a 16-byte boundary, 16-byte stores, dwords, bytes.
-__device__ inline void bam_emit_range(const BamEmit& e, uint64_t lo, uint64_t hi, uint8_t* out) {
+__device__ inline VK_BAM_INLINE void bam_emit_range(const BamEmit& e, uint64_t lo, uint64_t hi, uint8_t* out) {
     uint64_t i = lo;
     for (; i < hi && (reinterpret_cast<uintptr_t>(out) & 3u); ++i) *out++ = bam_text_byte(e, i);
     while (hi - i >= 4) {
@@ -231,7 +236,7 @@ __device__ inline uint64_t bam_items(const uint8_t* out, uint64_t size) {
     const uint64_t a = reinterpret_cast<uintptr_t>(out) & (kBamItemBytes - 1);
     return size ? (a + size + kBamItemBytes - 1) / kBamItemBytes : 0;
 }
-__device__ inline void bam_emit_item(const BamEmit& e, uint8_t* out, uint64_t size, uint64_t item) {
+__device__ inline VK_BAM_INLINE void bam_emit_item(const BamEmit& e, uint8_t* out, uint64_t size, uint64_t item) {
     const uint64_t a = reinterpret_cast<uintptr_t>(out) & (kBamItemBytes - 1);
     const uint64_t lo = item ? kBamItemBytes * item - a : 0;
     const uint64_t hi = kBamItemBytes * (item + 1) - a < size ? kBamItemBytes * (item + 1) - a : size;

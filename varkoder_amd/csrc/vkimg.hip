@@ -30,6 +30,7 @@
 //   vk_far_*_kernel (vk_fasta_records.h): the same per FASTA record (`--per-record`): record ordinal by a second scan.
 //   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
 //   vk_bam_*_kernel (vk_bam.h): BAM records to FASTQ text (`--from-bam`): record starts guessed per segment, verified in order.
+//   vk_bam_groups_*_kernel (vk_bam_groups.h): the same split by read group (`--bam-read-groups`): one emit workgroup per panel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,6 +67,7 @@
 #include "vk_fasta_records.h"
 #include "vk_fasta_windows.h"
 #include "vk_bam.h"
+#include "vk_bam_groups.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -158,6 +160,10 @@ struct vk_ctx {
     size_t bamws_cap = 0;
     uint32_t bam_seg_bytes = 0;    // VKIMG_BAM_SEG_BYTES=n: bytes of a segment of the BAM framing, 64 .. 65536 (tests: many seams in little data; 0 = 65536)
     uint64_t bam_segments = 0, bam_rewalked = 0;   // of the last of those calls (vk_last_bam_frame)
+    uint8_t* d_bamgws = nullptr;   // vk_bam_groups_frame_device, vk_bam_groups_fastq_device: what vk_bam_groups_workspace_size states (beside d_bamws)
+    size_t bamgws_cap = 0;
+    uint32_t bam_panel_segs = 0;   // VKIMG_BAM_PANEL_SEGS=n: segments of a panel of the grouped BAM calls, 1 .. 4096 (tests: many panels in little data; 0 = 4)
+    uint64_t bam_groups_wgs = 0, bam_groups_walked = 0;   // of the last of those calls (vk_last_bam_groups)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -670,6 +676,8 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     env_uint("VKIMG_BAM_SEG_BYTES", &ctx->bam_seg_bytes);
     if (ctx->bam_seg_bytes && ctx->bam_seg_bytes < 64) ctx->bam_seg_bytes = 64;
     if (ctx->bam_seg_bytes > kBamSegBytes) ctx->bam_seg_bytes = kBamSegBytes;
+    env_uint("VKIMG_BAM_PANEL_SEGS", &ctx->bam_panel_segs);
+    if (ctx->bam_panel_segs > 4096) ctx->bam_panel_segs = 4096;
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return VK_EHIP; }
     {
@@ -692,7 +700,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin, ctx->d_bamws};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin, ctx->d_bamws, ctx->d_bamgws};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -3113,6 +3121,307 @@ int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked)
     if (!ctx || !segments || !rewalked) return VK_EINVAL;
     *segments = ctx->bam_segments;
     *rewalked = ctx->bam_rewalked;
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- BAM read groups (vk_bam_groups.h) ----------------
+
+namespace {
+
+// What a grouped call's sizes come to: of its tables, its notes and its rows.
+struct BgCounts {
+    uint64_t groups = 0, id_bytes = 0, slots = 0, map = 0, segs = 0, scap = 0, panels = 0, rows = 0;
+    uint32_t max_ls = 0;
+    std::vector<uint32_t> nls;   // [nfiles]: a file's streams
+};
+
+BgCounts bg_counts(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first,
+                   const uint32_t* stream_file, uint32_t nstreams, uint32_t seg, uint32_t panel) {
+    BgCounts c;
+    c.nls.assign(nfiles, 0);
+    for (uint32_t s = 0; s < nstreams; ++s) c.nls[stream_file[s]] += 1;
+    c.groups = nfiles ? group_first[nfiles] : 0;
+    c.id_bytes = c.groups ? id_first[c.groups] : 0;
+    c.scap = seg / kBamMinRecord + 2;   // (bam_starts_cap)
+    for (uint32_t f = 0; f < nfiles; ++f) {
+        const uint32_t ng = group_first[f + 1] - group_first[f];
+        c.slots += bam_table_slots(ng);
+        c.map += 3ull * (ng + 1);
+        uint64_t nseg = (lengths[f] + seg - 1) / seg;
+        if (nseg == 0) nseg = 1;
+        const uint64_t npan = (nseg + panel - 1) / panel;
+        c.segs += nseg;
+        c.panels += npan;
+        c.rows += npan * c.nls[f];
+        c.max_ls = std::max(c.max_ls, c.nls[f]);
+    }
+    return c;
+}
+
+// The descriptors (made on the host, uploaded as one block) and the device-only pieces of a grouped call.
+struct BgPieces {
+    uint8_t* ids;
+    uint32_t *group_first, *id_first, *slots, *slot_first, *map_first, *ls_first, *ls_stream, *stream_file, *stream_local;
+    uint16_t* map;
+    uint64_t *pan_first, *row_first, *out_offs, *out_caps;
+    size_t desc_bytes;
+    uint32_t* aux_bad;
+    unsigned long long* counters;
+    uint16_t* notes;
+    BamRow *rows, *totals;
+};
+
+void bg_take(WsTake& take, BgPieces& p, uint32_t nfiles, uint32_t nstreams, const BgCounts& c) {
+    take(p.ids, c.id_bytes);
+    take(p.group_first, nfiles + 1ull);
+    take(p.id_first, c.groups + 1);
+    take(p.slots, c.slots);
+    take(p.slot_first, nfiles);
+    take(p.map_first, nfiles);
+    take(p.ls_first, nfiles + 1ull);
+    take(p.ls_stream, nstreams);
+    take(p.stream_file, nstreams);
+    take(p.stream_local, nstreams);
+    take(p.map, c.map);
+    take(p.pan_first, nfiles + 1ull);
+    take(p.row_first, nfiles);
+    take(p.out_offs, nstreams);
+    take(p.out_caps, nstreams);
+    p.desc_bytes = take.at;
+    take(p.aux_bad, nfiles);
+    take(p.counters, 1);
+    take(p.notes, c.segs * c.scap);
+    take(p.rows, c.rows);
+    take(p.totals, nstreams);
+}
+
+bool bg_args_ok(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first, const uint8_t* id_bytes,
+                const uint32_t* stream_file, const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams) {
+    if (nfiles && (!group_first || !id_first || !lengths)) return false;
+    if (nstreams && !stream_group) return false;
+    if (nfiles && group_first[0] != 0) return false;
+    for (uint32_t f = 0; f < nfiles; ++f)
+        if (group_first[f + 1] < group_first[f] || group_first[f + 1] - group_first[f] > kBamMaxGroups) return false;
+    const uint32_t tg = nfiles ? group_first[nfiles] : 0;
+    if (tg && (!id_bytes || id_first[0] != 0)) return false;
+    for (uint32_t g = 0; g < tg; ++g)
+        if (id_first[g + 1] <= id_first[g] || id_first[g + 1] - id_first[g] > kBamMaxId) return false;
+    for (uint32_t f = 0; f < nfiles; ++f) {   // an ID names one group of its file
+        std::vector<std::string> ids;
+        for (uint32_t g = group_first[f]; g < group_first[f + 1]; ++g)
+            ids.emplace_back(reinterpret_cast<const char*>(id_bytes) + id_first[g], id_first[g + 1] - id_first[g]);
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return false;
+    }
+    std::vector<uint8_t> kinds(nfiles, 0);   // 1: a stream of VK_BAM_ALL, 2: one of a class
+    std::vector<std::pair<uint64_t, uint32_t>> keys;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        const uint32_t f = stream_file[s], g = stream_group[s];
+        if (g != kBamUngrouped && g >= group_first[f + 1] - group_first[f]) return false;
+        kinds[f] |= stream_select[s] == kBamAll ? 1 : 2;
+        if (kinds[f] == 3) return false;
+        keys.emplace_back(static_cast<uint64_t>(f) << 32 | g, stream_select[s]);
+    }
+    std::sort(keys.begin(), keys.end());
+    return std::adjacent_find(keys.begin(), keys.end()) == keys.end();
+}
+
+struct BgState {
+    BgPieces d{};
+    BgCounts c;
+    BamGroupsMeta G{};
+};
+
+// Behind bam_frame: the tables, the count pass and the scan (out_offsets, out_caps: null for the framing call).
+int bg_count(vk_ctx* ctx, const uint8_t* d_bam, const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first,
+             const uint32_t* id_first, const uint8_t* id_bytes, const uint32_t* stream_file, const uint32_t* stream_select,
+             const uint32_t* stream_group, uint32_t nstreams, const uint64_t* out_offsets, const uint64_t* out_caps, uint32_t exclude,
+             const BamState& st, BgState* bg) {
+    const uint32_t seg = st.m.seg_bytes, panel = ctx->bam_panel_segs ? ctx->bam_panel_segs : kBamPanelSegs;
+    bg->c = bg_counts(lengths, nfiles, group_first, id_first, stream_file, nstreams, seg, panel);
+    const BgCounts& c = bg->c;
+    WsTake size{nullptr, 0};
+    BgPieces h{};
+    bg_take(size, h, nfiles, nstreams, c);
+    std::vector<uint8_t> host(h.desc_bytes, 0);
+    WsTake on_host{host.data(), 0};
+    bg_take(on_host, h, nfiles, nstreams, c);
+    if (c.id_bytes) memcpy(h.ids, id_bytes, c.id_bytes);
+    memcpy(h.group_first, group_first, (nfiles + 1ull) * sizeof(uint32_t));
+    if (c.groups) memcpy(h.id_first, id_first, (c.groups + 1) * sizeof(uint32_t));
+    else h.id_first[0] = 0;
+    uint32_t slot_at = 0, map_at = 0;
+    uint64_t row_at = 0;
+    h.ls_first[0] = 0;
+    h.pan_first[0] = 0;
+    for (uint32_t f = 0; f < nfiles; ++f) {
+        const uint32_t g0 = group_first[f], ng = group_first[f + 1] - g0, nslots = bam_table_slots(ng);
+        h.slot_first[f] = slot_at;
+        for (uint32_t g = 0; g < ng; ++g) {
+            uint32_t hash = kBamHashSeed;
+            for (uint32_t i = id_first[g0 + g]; i < id_first[g0 + g + 1]; ++i) hash = bam_hash_step(hash, id_bytes[i]);
+            uint32_t i = hash & (nslots - 1);
+            while (h.slots[slot_at + i]) i = (i + 1) & (nslots - 1);
+            h.slots[slot_at + i] = g + 1;
+        }
+        slot_at += nslots;
+        h.map_first[f] = map_at;
+        for (uint32_t i = 0; i < 3 * (ng + 1); ++i) h.map[map_at + i] = kBamNoStream;
+        map_at += 3 * (ng + 1);
+        h.ls_first[f + 1] = h.ls_first[f] + c.nls[f];
+        uint64_t nseg = (lengths[f] + seg - 1) / seg;
+        if (nseg == 0) nseg = 1;
+        const uint64_t npan = (nseg + panel - 1) / panel;
+        h.pan_first[f + 1] = h.pan_first[f] + npan;
+        h.row_first[f] = row_at;
+        row_at += npan * c.nls[f];
+    }
+    std::vector<uint32_t> seen(nfiles, 0);
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        const uint32_t f = stream_file[s], ng = group_first[f + 1] - group_first[f], local = seen[f]++;
+        h.stream_file[s] = f;
+        h.stream_local[s] = local;
+        h.ls_stream[h.ls_first[f] + local] = s;
+        const uint32_t slot = stream_group[s] == kBamUngrouped ? ng : stream_group[s];
+        uint16_t* map = h.map + h.map_first[f];
+        for (uint32_t cls = 1; cls <= 3; ++cls)
+            if (stream_select[s] == kBamAll || stream_select[s] == cls) map[(cls - 1) * (ng + 1) + slot] = static_cast<uint16_t>(local);
+        h.out_offs[s] = out_offsets ? out_offsets[s] : 0;
+        h.out_caps[s] = out_caps ? out_caps[s] : 0;
+    }
+    int rc = ws_carve(ctx, &ctx->d_bamgws, &ctx->bamgws_cap, [&](WsTake& take) { bg_take(take, bg->d, nfiles, nstreams, c); });
+    if (rc) return rc;
+    const BgPieces& d = bg->d;
+    // (a pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(ctx->d_bamgws, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d.aux_bad, 0, nfiles * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d.counters, 0, sizeof(unsigned long long), ctx->stream));
+    bg->G = BamGroupsMeta{d.ids, d.group_first, d.id_first, d.slots, d.slot_first, d.map, d.map_first, d.ls_first, d.ls_stream,
+                          d.pan_first, d.row_first, panel};
+    hipLaunchKernelGGL(vk_bam_groups_count_kernel, dim3(static_cast<uint32_t>(c.panels)), dim3(kBamCountThreads),
+                       c.max_ls * 2 * sizeof(unsigned long long), ctx->stream, d_bam, st.m, bg->G, exclude, st.d_segs, st.d_starts,
+                       st.d_files, d.notes, d.rows, d.aux_bad, d.counters);
+    VK_HIP(ctx, hipGetLastError());
+    if (nstreams) {
+        hipLaunchKernelGGL(vk_bam_groups_scan_kernel, dim3((nstreams + 3) / 4), dim3(256), 0, ctx->stream, st.m, bg->G, d.stream_file,
+                           d.stream_local, nstreams, st.d_files, d.aux_bad, d.rows, d.totals);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    return VK_OK;
+}
+
+// The results of a grouped call on the host: totals[nstreams], status[nfiles]; synchronises.
+int bg_finish(vk_ctx* ctx, uint32_t nfiles, uint32_t nstreams, BamState* st, const BgState& bg, std::vector<BamRow>* totals,
+              uint32_t* status) {
+    totals->assign(nstreams, BamRow{0, 0});
+    std::vector<uint32_t> aux_bad(nfiles, 0);
+    unsigned long long walked = 0;
+    if (nstreams)
+        VK_HIP(ctx, hipMemcpyAsync(totals->data(), bg.d.totals, nstreams * sizeof(BamRow), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(aux_bad.data(), bg.d.aux_bad, nfiles * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(&walked, bg.d.counters, sizeof(walked), hipMemcpyDeviceToHost, ctx->stream));
+    int rc = bam_finish(ctx, nfiles, st);
+    if (rc) return rc;
+    ctx->bam_groups_walked = walked;
+    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st->files[i].status ? st->files[i].status : aux_bad[i] ? kBamBadAux : 0u;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_bam_groups_workspace_size(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first,
+                                 const uint32_t* stream_file, uint32_t nstreams, uint32_t seg_bytes, uint32_t panel_segs,
+                                 uint64_t* bytes) {
+    if (!bytes || (nfiles && (!lengths || !group_first || !id_first)) || (nstreams && !stream_file)) return VK_EINVAL;
+    if ((seg_bytes && (seg_bytes < 64 || seg_bytes > kBamSegBytes)) || panel_segs > 4096) return VK_EINVAL;
+    for (uint32_t s = 0; s < nstreams; ++s)
+        if (stream_file[s] >= nfiles) return VK_EINVAL;
+    const BgCounts c = bg_counts(lengths, nfiles, group_first, id_first, stream_file, nstreams, seg_bytes ? seg_bytes : kBamSegBytes,
+                                 panel_segs ? panel_segs : kBamPanelSegs);
+    WsTake size{nullptr, 0};
+    BgPieces p{};
+    bg_take(size, p, nfiles, nstreams, c);
+    *bytes = size.at;
+    return VK_OK;
+}
+
+int vk_bam_groups_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                               const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles, const uint32_t* group_first,
+                               const uint32_t* id_first, const uint8_t* id_bytes, const uint32_t* stream_file,
+                               const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams, uint32_t exclude,
+                               uint32_t flags, uint64_t* out_records, uint64_t* out_bytes, uint32_t* status) {
+    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
+        return VK_EINVAL;
+    if ((nstreams && (!out_records || !out_bytes)) || (nfiles && !status)) return VK_EINVAL;
+    if (!bg_args_ok(lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select, stream_group, nstreams)) return VK_EINVAL;
+    ctx->bam_segments = ctx->bam_rewalked = ctx->bam_groups_wgs = ctx->bam_groups_walked = 0;
+    if (nfiles == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    BamState st;
+    BgState bg;
+    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, 0, nullptr,
+                       nullptr, exclude, flags, &st);
+    if (rc) return rc;
+    rc = bg_count(ctx, static_cast<const uint8_t*>(d_bam), lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select,
+                  stream_group, nstreams, nullptr, nullptr, exclude, st, &bg);
+    if (rc) return rc;
+    std::vector<BamRow> totals;
+    rc = bg_finish(ctx, nfiles, nstreams, &st, bg, &totals, status);
+    if (rc) return rc;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        out_records[s] = totals[s].recs;
+        out_bytes[s] = totals[s].bytes;
+    }
+    return VK_OK;
+}
+
+int vk_bam_groups_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
+                               const uint64_t* first_record, const int32_t* n_ref, uint32_t nfiles, const uint32_t* group_first,
+                               const uint32_t* id_first, const uint8_t* id_bytes, const uint32_t* stream_file,
+                               const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams, uint32_t exclude,
+                               uint32_t flags, void* d_out, const uint64_t* out_offsets, const uint64_t* out_caps, uint64_t* out_lengths,
+                               uint32_t* status) {
+    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
+        return VK_EINVAL;
+    if ((nstreams && (!d_out || !out_offsets || !out_caps || !out_lengths)) || (nfiles && !status)) return VK_EINVAL;
+    if (!bg_args_ok(lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select, stream_group, nstreams)) return VK_EINVAL;
+    ctx->bam_segments = ctx->bam_rewalked = ctx->bam_groups_wgs = ctx->bam_groups_walked = 0;
+    if (nfiles == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    BamState st;
+    BgState bg;
+    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, 0, nullptr,
+                       nullptr, exclude, flags, &st);
+    if (rc) return rc;
+    rc = bg_count(ctx, static_cast<const uint8_t*>(d_bam), lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select,
+                  stream_group, nstreams, out_offsets, out_caps, exclude, st, &bg);
+    if (rc) return rc;
+    if (nstreams) {   // a workgroup per panel: the grid does not depend on the streams
+        hipLaunchKernelGGL(vk_bam_groups_emit_kernel, dim3(static_cast<uint32_t>(bg.c.panels)), dim3(kBamEmitThreads),
+                           bg.c.max_ls * sizeof(unsigned long long), ctx->stream, static_cast<const uint8_t*>(d_bam), st.m, bg.G,
+                           bg.d.out_offs, bg.d.out_caps, st.d_segs, st.d_starts, bg.d.notes, st.d_files, bg.d.aux_bad, bg.d.rows,
+                           bg.d.totals, static_cast<uint8_t*>(d_out));
+        VK_HIP(ctx, hipGetLastError());
+        ctx->bam_groups_wgs = bg.c.panels;
+    }
+    std::vector<BamRow> totals;
+    rc = bg_finish(ctx, nfiles, nstreams, &st, bg, &totals, status);
+    if (rc) return rc;
+    for (uint32_t s = 0; s < nstreams; ++s) {
+        out_lengths[s] = totals[s].bytes <= out_caps[s] ? totals[s].bytes : 0;
+        if (totals[s].bytes > out_caps[s]) rc = VK_ENOSPC;
+    }
+    return rc;
+}
+
+int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* walked) {
+    if (!ctx || !emit_workgroups || !walked) return VK_EINVAL;
+    *emit_workgroups = ctx->bam_groups_wgs;
+    *walked = ctx->bam_groups_walked;
     return VK_OK;
 }
 

@@ -89,6 +89,26 @@ MAPPED_BELOW_THREADS = 16
 PNG_CALL_BYTES = 512 << 20
 
 
+def bam_groups_workspace_size(lengths, groups, stream_file, seg_bytes=0, panel_segs=0, L=None):
+    """Bytes of workspace vk_bam_groups_frame_device / vk_bam_groups_fastq_device take beyond the ungrouped calls
+    (vk_bam_groups_workspace_size: host only, no context) for files of `lengths` inflated bytes whose groups are
+    groups[i] (a list of IDs), streams of the files `stream_file`, segments of seg_bytes and panels of panel_segs segments
+    (0: the defaults)."""
+    L = L or _capi.lib()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+    sf = np.ascontiguousarray(stream_file, dtype=np.uint32)
+    gfirst = np.zeros(len(lens) + 1, dtype=np.uint32)
+    gfirst[1:] = np.cumsum([len(g) for g in groups])
+    ifirst = np.zeros(int(gfirst[-1]) + 1, dtype=np.uint32)
+    ifirst[1:] = np.cumsum([len(i) for g in groups for i in g])
+    out = C.c_uint64()
+    st = L.vk_bam_groups_workspace_size(_u64(lens), len(lens), _u32(gfirst), _u32(ifirst), _u32(sf), len(sf), int(seg_bytes),
+                                        int(panel_segs), C.byref(out))
+    if st:
+        raise _capi.VkError(st, "vk_bam_groups_workspace_size")
+    return out.value
+
+
 def plain_route(threads, engine=None):
     """"mapped" or "staged": how stage_files brings plain-text files in for a rank with this many I/O threads.
     VARKODER_AMD_MMAP decides when set; else what the engine's pipeline has switched to (ImageEngine.route_override:
@@ -725,6 +745,93 @@ class ImageEngine:
         seg, re = C.c_uint64(), C.c_uint64()
         _capi.check(self.ctx, self.L.vk_last_bam_frame(self.ctx, C.byref(seg), C.byref(re)), "vk_last_bam_frame")
         return seg.value, re.value
+
+    # -- BAM, split by read group ---------------------------------------------------
+    def _bam_group_args(self, nfiles, groups, stream_group, nstreams):
+        """groups: per file the list of its group IDs (bytes) -> (group_first uint32 [nfiles + 1], id_first uint32
+        [groups + 1], the ID bytes uint8 (never empty: ctypes wants an address), stream_group uint32 [nstreams])."""
+        groups = [list(g) for g in groups]
+        if len(groups) != nfiles:
+            raise ValueError("groups: one list of IDs per file")
+        gfirst = np.zeros(nfiles + 1, dtype=np.uint32)
+        gfirst[1:] = np.cumsum([len(g) for g in groups])
+        ids = [bytes(i) for g in groups for i in g]
+        ifirst = np.zeros(len(ids) + 1, dtype=np.uint32)
+        ifirst[1:] = np.cumsum([len(i) for i in ids])
+        raw = np.frombuffer(b"".join(ids) + b"\0", dtype=np.uint8).copy()
+        sg = np.ascontiguousarray(stream_group, dtype=np.uint32)
+        if sg.shape != (nstreams,):
+            raise ValueError("stream_group: one per stream")
+        return gfirst, ifirst, raw, sg
+
+    def bam_groups_frame(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group,
+                         exclude=0x900, flags=0):
+        """bam_frame with the reads split by read group (vk_bam_groups_frame_device; the rule: INTEGRATION.md, "--from-bam
+        --bam-read-groups: the rule"): groups[i] = the IDs (bytes) of file i's @RG lines, stream s takes the reads
+        stream_select[s] of group stream_group[s] (an index into groups[stream_file[s]], or VK_BAM_UNGROUPED) of file
+        stream_file[s].  Returns (records uint64 [nstreams], text bytes uint64 [nstreams], status uint32 [nfiles]: VK_BAM_*,
+        VK_BAM_BAD_AUX among them) on the host; synchronises."""
+        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
+        gfirst, ifirst, raw, sg = self._bam_group_args(len(offs), groups, stream_group, len(sf))
+        recs = np.zeros(len(sf), dtype=np.uint64)
+        nbytes = np.zeros(len(sf), dtype=np.uint64)
+        status = np.zeros(len(offs), dtype=np.uint32)
+        st = self.L.vk_bam_groups_frame_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
+                                               nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(gfirst), _u32(ifirst),
+                                               raw.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(sf), _u32(sel), _u32(sg), len(sf),
+                                               int(exclude), int(flags), _u64(recs), _u64(nbytes), _u32(status))
+        _capi.check(self.ctx, st, "vk_bam_groups_frame_device")
+        return recs, nbytes, status
+
+    def bam_groups_fastq(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group, out,
+                         out_offsets, out_caps, exclude=0x900, flags=0):
+        """The FASTQ text of those streams (vk_bam_groups_fastq_device) into `out` (uint8 device tensor) at out_offsets, at
+        most out_caps bytes each.  Returns (text lengths uint64 [nstreams], status uint32 [nfiles]) on the host;
+        synchronises."""
+        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
+        gfirst, ifirst, raw, sg = self._bam_group_args(len(offs), groups, stream_group, len(sf))
+        oo, oc = self._desc(out_offsets, out_caps)
+        if oo.shape != sf.shape:
+            raise ValueError("out_offsets and out_caps: one per stream")
+        got = np.zeros(len(sf), dtype=np.uint64)
+        status = np.zeros(len(offs), dtype=np.uint32)
+        st = self.L.vk_bam_groups_fastq_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
+                                               nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(gfirst), _u32(ifirst),
+                                               raw.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(sf), _u32(sel), _u32(sg), len(sf),
+                                               int(exclude), int(flags), self._ptr(out), _u64(oo), _u64(oc), _u64(got), _u32(status))
+        _capi.check(self.ctx, st, "vk_bam_groups_fastq_device")
+        return got, status
+
+    def bam_groups_to_fastq(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group,
+                            exclude=0x900, flags=0):
+        """bam_groups_frame, a text buffer sized by it (every stream at a multiple of 16 bytes) and bam_groups_fastq: (text
+        uint8 device tensor, offsets uint64 [nstreams], lengths uint64 [nstreams], reads uint64 [nstreams], status uint32
+        [nfiles]).  `bam` stays the caller's."""
+        torch = _torch()
+        recs, nbytes, _ = self.bam_groups_frame(bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select,
+                                                stream_group, exclude, flags)
+        oo = np.zeros(len(nbytes), dtype=np.uint64)
+        pos = 0
+        for i, n in enumerate(nbytes):
+            oo[i] = pos
+            pos += (int(n) + 15) // 16 * 16
+        out = torch.zeros(pos + 16, dtype=torch.uint8, device=self.device)
+        got, status = self.bam_groups_fastq(bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select,
+                                            stream_group, out, oo, nbytes, exclude, flags)
+        return out, oo, got, recs, status
+
+    def bam_groups_workspace_size(self, lengths, groups, stream_file, seg_bytes=0, panel_segs=0):
+        """Bytes of workspace the grouped calls take beyond the ungrouped ones (vk_bam_groups_workspace_size; host only)."""
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+        sf = np.ascontiguousarray(stream_file, dtype=np.uint32)
+        return bam_groups_workspace_size(lens, groups, sf, seg_bytes, panel_segs, self.L)
+
+    def last_bam_groups(self):
+        """(workgroups of the emit launch, records whose aux was walked) of the last bam_groups_frame / bam_groups_fastq
+        call (vk_last_bam_groups)."""
+        wgs, walked = C.c_uint64(), C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_last_bam_groups(self.ctx, C.byref(wgs), C.byref(walked)), "vk_last_bam_groups")
+        return wgs.value, walked.value
 
     def count_sampled(self, fastq, offsets, lengths, seeds, thresholds, parts=0, hist=None, status=None,
                       sites=None):

@@ -543,8 +543,21 @@ def _budget(avgs, lines, sample_files, max_bp):
 def _raw_plans(samples, weights, rank, world, bam=None):
     """This rank's share of raw samples [(sample, [files])] as [(sample, [(file, role)])], dealt by weight (per sample:
     the sum of its files' weights; None: agreed on here, a collective when sharded).  bam (the options of `--from-bam`):
-    a sample is one BAM file and its plan [(file, role, select)] (bam.sample_plan)."""
-    if bam is not None:
+    a sample is one BAM file and its plan [(file, role, select)] (bam.sample_plan).  With bam["groups"] ({sample: its
+    group's index in its file}: `--bam-read-groups`) the samples of one file make ONE plan [(file, role, select, group,
+    sample)] under the file's name: a file is uploaded once for all of its groups, so they stay in one batch and on one
+    rank."""
+    if bam is not None and bam.get("groups") is not None:
+        from .bam import sample_plan
+        units, at = OrderedDict(), {}
+        for i, (s, files) in enumerate(samples):
+            units.setdefault(files[0], []).append(s)
+            at.setdefault(files[0], i)
+        plans = [(str(f), [e + (s,) for s in members for e in sample_plan(f, bam.get("pairs", False), bam["groups"][s])])
+                 for f, members in units.items()]
+        if weights is not None:   # (one per sample, each its file's: a unit weighs what its file weighs)
+            weights = [weights[at[f]] for f in units]
+    elif bam is not None:
         from .bam import sample_plan
         plans = [(s, sample_plan(files[0], bam.get("pairs", False))) for s, files in samples]
     else:
@@ -566,7 +579,7 @@ class Cleaning:
     clean_dir: object
     max_bp: int
     gpu_gzip: bool = False
-    bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int}; the plans then hold (file, role, select)
+    bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int, "groups": None or {sample: group}}; the plans then hold (file, role, select[, group, sample])
 
 
 def _bam_texts(eng, batch, pool, bam):
@@ -574,27 +587,42 @@ def _bam_texts(eng, batch, pool, bam):
     files' headers are read on the host (bam.bam_header), their bytes uploaded and inflated in HBM
     (ImageEngine.upload_files), converted to one FASTQ text per (file, role) there (ImageEngine.bam_to_fastq) and
     released.  Returns (text, offsets, lengths, {index in the batch: why it failed}): a file that is not BAM, whose
-    header does not parse or whose records give a status fails its sample; its texts are empty."""
-    from .bam import BamError, file_info
-    files = list(dict.fromkeys(Path(f) for _, plan in batch for f, _, _ in plan))
-    heads, why = {}, {}
+    header does not parse or whose records give a status fails its sample; its texts are empty.
+
+    With bam["groups"] (`--bam-read-groups`) the batch is [(file, [(file, role, select, group, sample)])] and a text is
+    made per (file, role, group) (ImageEngine.bam_groups_frame / bam_groups_fastq): the file is uploaded and inflated once
+    for all of its groups.  The reads of no listed group are counted by streams of their own, reported per file and not
+    written."""
+    from .bam import BamError, file_info, read_groups
+    grouped = bam.get("groups") is not None
+    files = list(dict.fromkeys(Path(e[0]) for _, plan in batch for e in plan))
+    heads, why, ids = {}, {}, {}
     for f in files:
         try:
             heads[f] = file_info(f)[1]   # (read when the batch was sized: not again)
+            if grouped:
+                ids[f] = read_groups(f)
         except (BamError, OSError) as e:
+            heads.pop(f, None)
             why[f] = str(e) or type(e).__name__
     good = [f for f in files if f in heads]
     at = {f: i for i, f in enumerate(good)}
-    streams = [(j, Path(f), sel) for j, (_, plan) in enumerate(batch) for f, _, sel in plan]
+    streams = [(j, Path(e[0]), e[2]) + ((e[3],) if grouped else ()) for j, (_, plan) in enumerate(batch) for e in plan]
     offs = np.zeros(len(streams), dtype=np.uint64)
     lens = np.zeros(len(streams), dtype=np.uint64)
     text, failed = None, {}
     if good:
         dev, doffs, dlens = eng.upload_files(good, pool)
-        live = [i for i, (_, f, _) in enumerate(streams) if f in at]
-        text, oo, ol, status = eng.bam_to_fastq(dev, doffs, dlens, [heads[f][0] for f in good], [heads[f][1] for f in good],
-                                                [at[streams[i][1]] for i in live], [streams[i][2] for i in live],
-                                                exclude=bam.get("exclude", 0x900))
+        live = [i for i, st in enumerate(streams) if st[1] in at]
+        first, n_ref = [heads[f][0] for f in good], [heads[f][1] for f in good]
+        exclude = bam.get("exclude", 0x900)
+        if grouped:
+            text, oo, ol, status = _bam_group_texts(eng, dev, doffs, dlens, first, n_ref, [ids[f] for f in good], good,
+                                                    [(at[streams[i][1]], streams[i][2], streams[i][3]) for i in live],
+                                                    bam.get("pairs", False), exclude)
+        else:
+            text, oo, ol, status = eng.bam_to_fastq(dev, doffs, dlens, first, n_ref, [at[streams[i][1]] for i in live],
+                                                    [streams[i][2] for i in live], exclude=exclude)
         del dev
         offs[live], lens[live] = oo, ol
         inflate = getattr(eng, "last_upload_status", None)   # (a member that does not inflate or fails its CRC: no bytes)
@@ -603,10 +631,45 @@ def _bam_texts(eng, batch, pool, bam):
                 why[f] = "inflate status %d" % int(inflate[at[f]])
             elif status[at[f]]:
                 why[f] = "BAM status %d" % int(status[at[f]])
-    for j, f, _ in streams:
+    for j, f, *_ in streams:
         if f in why:
             failed[j] = why[f]
     return text, offs, lens, failed
+
+
+def _bam_group_texts(eng, dev, doffs, dlens, first, n_ref, groups, files, streams, pairs, exclude):
+    """The texts of the streams [(file index, select, group)] of files in HBM, split by read group: one framing call that
+    also counts, per file, the reads of no listed group (streams of VK_BAM_UNGROUPED, reported on stderr and not
+    written), then one text call for the streams that have reads.  Returns (text, offsets, lengths, status) as
+    ImageEngine.bam_to_fastq does: a stream without reads has no bytes."""
+    from . import _capi
+    selects = (_capi.VK_BAM_SINGLE, _capi.VK_BAM_READ1, _capi.VK_BAM_READ2) if pairs else (_capi.VK_BAM_ALL,)
+    loose = [(i, sel, _capi.VK_BAM_UNGROUPED) for i in range(len(files)) for sel in selects]
+    every = list(streams) + loose
+    recs, nbytes, status = eng.bam_groups_frame(dev, doffs, dlens, first, n_ref, groups, [s[0] for s in every],
+                                                [s[1] for s in every], [s[2] for s in every], exclude=exclude)
+    passed = np.zeros(len(files), dtype=np.int64)
+    for (i, _, _), n in zip(loose, recs[len(streams):]):
+        passed[i] += int(n)
+    for i, f in enumerate(files):
+        if passed[i] and not status[i]:
+            eprint(f"{f}: {int(passed[i])} reads without a listed read group passed over")
+    oo = np.zeros(len(streams), dtype=np.uint64)
+    ol = np.zeros(len(streams), dtype=np.uint64)
+    full = [k for k in range(len(streams)) if nbytes[k]]
+    text = None
+    if full:
+        pos = 0
+        for k in full:
+            oo[k] = pos
+            pos += (int(nbytes[k]) + 15) // 16 * 16
+        import torch
+        text = torch.zeros(pos + 16, dtype=torch.uint8, device=eng.device)
+        got, status = eng.bam_groups_fastq(dev, doffs, dlens, first, n_ref, groups, [streams[k][0] for k in full],
+                                           [streams[k][1] for k in full], [streams[k][2] for k in full], text, oo[full],
+                                           nbytes[full], exclude=exclude)
+        ol[full] = got
+    return text, oo, ol, status
 
 
 def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, verbose):
@@ -647,7 +710,7 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
         from .bam import batch_bytes as bam_bytes
 
         def size(plan):
-            return sum(bam_bytes(f) for f in dict.fromkeys(f for f, _, _ in plan[1]))
+            return sum(bam_bytes(f) for f in dict.fromkeys(e[0] for e in plan[1]))
     else:
         def size(plan):
             return sum(text_bytes(f) for f, _ in plan[1])
@@ -655,9 +718,11 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
     for batch, nbytes, t0 in batches(mine, batch_bytes, size=size):
         if opt.bam is not None:   # BAM bytes in, one FASTQ text per (file, role) out; from here on the run is --from-raw's
             dev, offs, lens, bad = _bam_texts(eng, batch, pool, opt.bam)
+            grouped = opt.bam.get("groups") is not None
             for j, why in bad.items():
-                eprint("CLEAN FAIL:", sorted({str(f) for f, _, _ in batch[j][1]}), "-", why)
-                stats.setdefault(batch[j][0], OrderedDict())["failed_step"] = "clean"
+                eprint("CLEAN FAIL:", sorted({str(e[0]) for e in batch[j][1]}), "-", why)
+                for s in (dict.fromkeys(e[4] for e in batch[j][1]) if grouped else [batch[j][0]]):
+                    stats.setdefault(s, OrderedDict())["failed_step"] = "clean"
             nstreams = [len(plan) for _, plan in batch]
             first = np.concatenate(([0], np.cumsum(nstreams)))
             keep = [j for j in range(len(batch)) if j not in bad]
@@ -665,12 +730,22 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
             # sample, as a role without files is none of a raw sample's; a sample without any read keeps one empty
             # stream and fails where a raw sample of an empty file fails.  A stream per role of ONE file: named
             # apart, the read budget is kept by name.
+            # `--bam-read-groups`: a file's plan holds the streams of all of its groups; each group with reads is a
+            # sample of its own from here on, and a group without reads is none.
             rows, plans = [], []
             for j in keep:
-                mine = [i for i in range(first[j], first[j + 1]) if lens[i]] or [int(first[j])]
-                rows += mine
-                plans.append((batch[j][0], [(f"{f}:{('single', 'R1', 'R2')[role]}", role)
-                                            for f, role, _ in (batch[j][1][i - first[j]] for i in mine)]))
+                members = OrderedDict()
+                for i in range(first[j], first[j + 1]):
+                    members.setdefault(batch[j][1][i - first[j]][4] if grouped else batch[j][0], []).append(i)
+                for s, own in members.items():
+                    mine = [i for i in own if lens[i]] or ([] if grouped else [own[0]])
+                    if not mine:
+                        if verbose:
+                            eprint(f"{batch[j][0]}: read group sample {s} has no reads: no sample")
+                        continue
+                    rows += mine
+                    plans.append((s, [(f"{e[0]}:{('single', 'R1', 'R2')[e[1]]}" + (f":{e[3]}" if grouped else ""), e[1])
+                                      for e in (batch[j][1][i - first[j]] for i in mine)]))
             offs, lens, batch = offs[rows], lens[rows], plans
             if not batch:
                 continue
