@@ -625,6 +625,51 @@ int vk_bam_groups_workspace_size(const uint64_t* lengths, uint32_t nfiles, const
  * walked. */
 int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* walked);
 
+/* `image / query --exclude-fasta / --keep-fasta`: the k-mer set of a reference FASTA, built in HBM.  The rule is this
+ * project's ("--exclude-fasta / --keep-fasta: the rule", and tests/screen_ref.py): lines, headers and
+ * records as vk_count_fasta_device reads them; a base is ACGT of either case coded 0 1 2 3; every other sequence byte and
+ * every record boundary breaks the sequence; every window of k (16 .. 31) unbroken bases gives a key, the smaller of the
+ * window and its reverse complement read as 2k-bit integers, first base most significant; the set is the distinct keys.
+ *
+ * d_fasta[0 .. length) is the text (16-byte aligned, readable up to its 16-byte rounded end); a text of more than
+ * VK_SCREEN_MAX_REF bytes -- it cannot hold more sequence bytes than that -- returns VK_EINVAL before anything is
+ * touched.  d_table[nslots] is the caller's: open addressing over the keys, a free slot all ones (no key of 62 bits
+ * equals it); nslots is a power of two of at least VK_SCREEN_MIN_SLOTS.  The call with d_table NULL and nslots 0 only
+ * counts: *windows = the windows of k unbroken bases, from which a caller sizes the table (the engine takes the smallest
+ * power of two that is at least twice the windows).  With a table the call fills it and returns *windows and *distinct,
+ * the number of distinct keys; VK_ENOSPC when the keys do not leave one slot free (the table is then not to be used).
+ * *status: VK_ST_BAD_START for a non-empty text whose first byte is not '>' (no windows, an empty table).  Where a key
+ * lies in the table depends on a hash function that is the library's own; no result does.  d_ws: caller-allocated device
+ * workspace of vk_screen_build_workspace_size(length) bytes.  VK_EINVAL for a null pointer, k outside 16 .. 31, a
+ * misaligned text, a bad nslots or a workspace that is too small.  The call allocates no device memory and synchronises. */
+#define VK_SCREEN_MAX_REF (1ull << 30)
+#define VK_SCREEN_MIN_SLOTS 1024u
+int vk_screen_build_workspace_size(uint64_t length, uint64_t* bytes);
+int vk_screen_build_device(vk_ctx* ctx, const void* d_fasta, uint64_t length, int k, uint64_t* d_table, uint64_t nslots,
+                           void* d_ws, uint64_t ws_bytes, uint64_t* windows, uint64_t* distinct, uint32_t* status);
+
+/* The screen: cleaned FASTQ samples in HBM (what vk_clean_device wrote, or an upload) record by record against a table of
+ * vk_screen_build_device.  A read's windows are taken from its sequence line as the set's are from the reference (a
+ * trailing '\r' is no part of the line); its hits are the window POSITIONS whose key is in the table; it matches when
+ * hits >= min_hits (>= 1); a read of fewer than k bases never matches.  keep == 0 keeps the records that do not match
+ * (--exclude-fasta), keep != 0 those that do (--keep-fasta).  A kept record is copied byte for byte -- four lines as
+ * they stand, a '\r' included, a last line without '\n' as it is -- and kept records stay in input order.
+ *
+ * Samples as for vk_ladder_emit_device: offsets[i] a multiple of 16 (any other returns VK_EINVAL before anything is
+ * read), records[i] the lines of sample i over 4.  Sample i's text is written at d_out + out_offsets[i] (host array,
+ * multiples of 16), zeroed up to its 16-byte rounded end; its region is as large as its input, lengths[i] rounded up to
+ * 16, as vk_clean_device lays its output out, and must end within out_capacity (else VK_ENOSPC, nothing touched).  Device
+ * arrays out: d_out_lengths[nsamples]; d_stats[nsamples][4] = records in, records kept, sequence bases in, sequence
+ * bases kept; d_status[nsamples] = VK_ST_*, VK_EM_TOO_LARGE, VK_EM_BAD_RECORDS as vk_ladder_emit_device reports them: a
+ * sample with a status gets no text and zero stats.  d_ws: caller-allocated device workspace of
+ * vk_screen_workspace_size bytes (same records and lengths).  The call allocates no device memory and does not synchronise: it is
+ * enqueued on the context's stream (its host arrays have been read when it returns). */
+int vk_screen_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes);
+int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths,
+                     const uint64_t* records, uint32_t nsamples, const uint64_t* d_table, uint64_t nslots, int k,
+                     uint32_t min_hits, int keep, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_capacity,
+                     uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

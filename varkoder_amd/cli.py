@@ -117,6 +117,7 @@ def setup_parser():
                         "only the writing; pixels and text chunks are the same as without it, the files' bytes are not. "
                         "Not with -X")
     add_adapter_flags(p)
+    add_screen_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
     q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads); with --from-raw, "
@@ -178,6 +179,7 @@ def setup_parser():
                         "predictions are the same. Measured: 4,000 files of 128 x 128 in 80 ms against 403 ms, 400 of "
                         "512 x 512 in 36 ms against 313 ms (profiles/ab/unpng_time.txt)")
     add_adapter_flags(q)
+    add_screen_flags(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Convert images between different kmer mappings.")          # cli.py:447-482
@@ -269,6 +271,36 @@ def bam_options(args):
     from .bam import EXCLUDE_DEFAULT
     return dict(pairs=getattr(args, "bam_pairs", False), exclude=getattr(args, "bam_exclude", EXCLUDE_DEFAULT),
                 groups={} if getattr(args, "bam_read_groups", False) else None)   # ({sample: group}: filled by RawPlan)
+
+
+SCREEN_K_DEFAULT, SCREEN_K_MIN, SCREEN_K_MAX = 31, 16, 31
+
+
+def add_screen_flags(p):
+    which = p.add_mutually_exclusive_group()
+    which.add_argument("--exclude-fasta", default=argparse.SUPPRESS, metavar="FILE",   # (absent = no screen)
+                       help="where cleaned reads lie on the GPU in front of the subsampling (--from-raw, --from-bam, "
+                            "--from-clean; query's cleaned reads): drop every read that shares a k-mer with this reference "
+                            "FASTA (.gz or not, any number of records: PhiX, a host, an organelle) before the subsampling "
+                            "(rule: INTEGRATION.md, \"--exclude-fasta / --keep-fasta: the rule\")")
+    which.add_argument("--keep-fasta", default=argparse.SUPPRESS, metavar="FILE",
+                       help="the converse of --exclude-fasta: keep only the reads that share a k-mer with this reference")
+    p.add_argument("--screen-k", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help=f"with --exclude-fasta / --keep-fasta: the k-mer size of the screen, {SCREEN_K_MIN} to {SCREEN_K_MAX} "
+                        f"({SCREEN_K_DEFAULT} when absent)")
+    p.add_argument("--screen-min-hits", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --exclude-fasta / --keep-fasta: a read matches when at least N of its k-mer positions are in "
+                        "the reference (1 when absent)")
+
+
+def screen_options(args):
+    """pipeline.Screen of `--exclude-fasta` / `--keep-fasta`, None without either."""
+    keep = hasattr(args, "keep_fasta")
+    if not keep and not hasattr(args, "exclude_fasta"):
+        return None
+    from .pipeline import Screen
+    return Screen(Path(args.keep_fasta if keep else args.exclude_fasta), getattr(args, "screen_k", SCREEN_K_DEFAULT),
+                  getattr(args, "screen_min_hits", 1), keep)
 
 
 def add_record_flags(p):
@@ -369,6 +401,27 @@ def parse_args(argv=None):
             parser.error("--gpu-gzip: only with --from-raw and -i/--int-folder" +
                          (", or with --write-splits" if args.command == "image" else "") +
                          " (--from-bam counts as --from-raw)")
+    if args.command in ("image", "query"):
+        which = [flag for name, flag in (("exclude_fasta", "--exclude-fasta"), ("keep_fasta", "--keep-fasta")) if hasattr(args, name)]
+        for name, flag in (("screen_k", "--screen-k"), ("screen_min_hits", "--screen-min-hits")):
+            if hasattr(args, name) and not which:
+                parser.error(f"{flag}: only with --exclude-fasta or --keep-fasta")
+        if which:
+            # only where cleaned reads lie in HBM in front of the ladder
+            if getattr(args, "from_fasta", False):
+                parser.error(f"{which[0]}: not with --from-fasta (reads are screened, not assemblies)")
+            if args.command == "query" and args.images:
+                parser.error(f"{which[0]}: not with -I/--images (no reads)")
+            if args.command == "image" and not (args.from_raw or args.from_clean or from_bam):
+                parser.error(f"{which[0]}: only with --from-raw, --from-bam or --from-clean (the default entry takes "
+                             "subsamples that are drawn already)")
+            if hasattr(args, "screen_k") and not SCREEN_K_MIN <= args.screen_k <= SCREEN_K_MAX:
+                parser.error(f"--screen-k: {SCREEN_K_MIN} to {SCREEN_K_MAX}")
+            if hasattr(args, "screen_min_hits") and args.screen_min_hits < 1:
+                parser.error("--screen-min-hits: at least 1")
+            ref = getattr(args, "keep_fasta", None) or getattr(args, "exclude_fasta", None)
+            if not Path(ref).is_file():
+                parser.error(f"{which[0]}: no such file: {ref}")
     if getattr(args, "gpu_png", False):
         if args.command == "query" and not args.keep_images:
             parser.error("--gpu-png: only with -m/--keep-images")
@@ -586,7 +639,7 @@ def run_query(args):
                 wanted = [(i, stem(inputs[i])) for i in mine]
                 found = clean_to_query([(s, inputs[i]) for i, s in wanted], max_bp=max_bp, seeds=seeds, engine=eng,
                                        k=args.kmer_size, mapping_code=args.kmer_mapping,
-                                       io_threads=io_threads_per_rank(args.n_threads))
+                                       io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args))
                 images = found_images(found, wanted, {})
         if rank == 0:
             if args.single_label:
@@ -701,7 +754,7 @@ class RawPlan:
         from .shard import io_threads_per_rank, shard_by_size
         args = self.args
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp_of(args), seeds=self.seeds, engine=eng,
-                      io_threads=io_threads_per_rank(args.n_threads))
+                      io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args))
         found = {}
         if self.raw:
             found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
@@ -761,7 +814,7 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
                                      min_bp=parse_size(args.min_bp), max_bp=max_bp, seeds=seeds, labels=labels,
                                      base_sd=base_sd, **split_options(args), gpu_gzip=getattr(args, "gpu_gzip", False),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
-                                     verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False))
+                                     verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), screen=screen_options(args))
         for s, v in per_sample.items():
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
@@ -825,7 +878,8 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, min_bp=parse_size(args.min_bp), max_bp=max_bp,
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
-                      gpu_gzip=getattr(args, "gpu_gzip", False), gpu_png=getattr(args, "gpu_png", False))
+                      gpu_gzip=getattr(args, "gpu_gzip", False), gpu_png=getattr(args, "gpu_png", False),
+                      screen=screen_options(args))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, bam=plan.bam, **cleaning,
                                      **common)

@@ -31,6 +31,7 @@
 //   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
 //   vk_bam_*_kernel (vk_bam.h): BAM records to FASTQ text (`--from-bam`): record starts guessed per segment, verified in order.
 //   vk_bam_groups_*_kernel (vk_bam_groups.h): the same split by read group (`--bam-read-groups`): one emit workgroup per panel.
+//   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -68,6 +69,7 @@
 #include "vk_fasta_windows.h"
 #include "vk_bam.h"
 #include "vk_bam_groups.h"
+#include "vk_screen.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -164,6 +166,7 @@ struct vk_ctx {
     size_t bamgws_cap = 0;
     uint32_t bam_panel_segs = 0;   // VKIMG_BAM_PANEL_SEGS=n: segments of a panel of the grouped BAM calls, 1 .. 4096 (tests: many panels in little data; 0 = 4)
     uint64_t bam_groups_wgs = 0, bam_groups_walked = 0;   // of the last of those calls (vk_last_bam_groups)
+    uint32_t screen_tile = 0;      // VKIMG_SCREEN_TILE=n: bases of a wavefront's tile of the screen's match kernel, a multiple of 64 from 64 to 4096 (tests: tile seams in short reads; 0 = 4096)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -676,6 +679,12 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     env_uint("VKIMG_BAM_SEG_BYTES", &ctx->bam_seg_bytes);
     if (ctx->bam_seg_bytes && ctx->bam_seg_bytes < 64) ctx->bam_seg_bytes = 64;
     if (ctx->bam_seg_bytes > kBamSegBytes) ctx->bam_seg_bytes = kBamSegBytes;
+    env_uint("VKIMG_SCREEN_TILE", &ctx->screen_tile);
+    if (ctx->screen_tile) {
+        ctx->screen_tile = ctx->screen_tile / 64 * 64;
+        if (ctx->screen_tile < 64) ctx->screen_tile = 64;
+        if (ctx->screen_tile > kScMaxTile) ctx->screen_tile = kScMaxTile;
+    }
     env_uint("VKIMG_BAM_PANEL_SEGS", &ctx->bam_panel_segs);
     if (ctx->bam_panel_segs > 4096) ctx->bam_panel_segs = 4096;
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
@@ -3422,6 +3431,181 @@ int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* w
     if (!ctx || !emit_workgroups || !walked) return VK_EINVAL;
     *emit_workgroups = ctx->bam_groups_wgs;
     *walked = ctx->bam_groups_walked;
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- reads screened against a reference (vk_screen.h) ------
+
+namespace {
+
+// the pieces of a vk_screen_build_device workspace (the units counted at their smallest size, 64 bytes)
+struct ScBuildLayout {
+    uint64_t* meta;
+    uint32_t *ukey, *carry, *status;
+    ScBuildOut* out;
+    size_t total;
+};
+
+ScBuildLayout sc_build_layout(void* d_ws, uint64_t length) {
+    ScBuildLayout L{};
+    const uint64_t nunits = (length + kFaLaneBytes - 1) / kFaLaneBytes;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.meta, 6);
+    take(L.ukey, nunits + 1);
+    take(L.carry, nunits + 1);
+    take(L.out, 1);
+    take(L.status, 1);
+    L.total = take.at;
+    return L;
+}
+
+// the pieces of a vk_screen_device workspace: the record index in vk_clean_device's layout (the pieces of it that
+// cl_index_run fills), then the samples' tables and the records' kept bytes
+struct ScLayout {
+    ClLayout c;
+    EmSample* samples;
+    uint64_t *rec_base, *out_offs, *obytes, *oprefix;
+    size_t total;
+};
+
+ScLayout sc_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
+    ScLayout L{};
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        L.c.nrec += records[i];
+    }
+    const uint64_t nb = (std::max(L.c.nchunks, L.c.nrec) + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.c.files, nsamples);
+    take(L.c.fchunk, nsamples);
+    take(L.c.ccount, L.c.nchunks);
+    take(L.c.cprefix, L.c.nchunks + 1);
+    take(L.c.sums, nb + 1);
+    take(L.c.recs, L.c.nrec);
+    take(L.samples, nsamples);
+    take(L.rec_base, nsamples + 1ull);
+    take(L.out_offs, nsamples);
+    take(L.obytes, L.c.nrec);
+    take(L.oprefix, L.c.nrec + 1);
+    L.total = take.at;
+    return L;
+}
+
+bool sc_slots_ok(uint64_t nslots) { return nslots >= kScMinSlots && nslots <= (1ull << 40) && (nslots & (nslots - 1)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int vk_screen_build_workspace_size(uint64_t length, uint64_t* bytes) {
+    if (!bytes || length > VK_SCREEN_MAX_REF) return VK_EINVAL;
+    *bytes = sc_build_layout(nullptr, length).total;
+    return VK_OK;
+}
+
+int vk_screen_build_device(vk_ctx* ctx, const void* d_fasta, uint64_t length, int k, uint64_t* d_table, uint64_t nslots,
+                           void* d_ws, uint64_t ws_bytes, uint64_t* windows, uint64_t* distinct, uint32_t* status) {
+    if (!ctx || !d_ws || !windows || !distinct || !status) return VK_EINVAL;
+    if (length > VK_SCREEN_MAX_REF) return VK_EINVAL;   // (before anything is allocated or uploaded)
+    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK)) return VK_EINVAL;
+    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    if ((d_table == nullptr) != (nslots == 0) || (d_table && !sc_slots_ok(nslots))) return VK_EINVAL;
+    const ScBuildLayout L = sc_build_layout(d_ws, length);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    FaPlan pl;
+    const uint64_t zero = 0;
+    int rc = fa_plan(ctx, &zero, &length, 1, &pl);
+    if (rc) return rc;
+    // (pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(L.out, 0, sizeof(ScBuildOut), ctx->stream));
+    if (d_table) VK_HIP(ctx, hipMemsetAsync(d_table, 0xFF, nslots * sizeof(uint64_t), ctx->stream));
+    const FaMeta m = pl.on_device(L.meta);
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    rc = fa_header_state(ctx, text, pl, m, L.ukey, L.carry, L.status);
+    if (rc) return rc;
+    if (pl.nwg) {
+        const dim3 grid(static_cast<uint32_t>(pl.nwg)), block(kFaThreads);
+        if (d_table)
+            hipLaunchKernelGGL(vk_sc_build_kernel<true>, grid, block, 0, ctx->stream, text, m, L.carry, static_cast<uint32_t>(k), d_table,
+                               nslots, L.out);
+        else
+            hipLaunchKernelGGL(vk_sc_build_kernel<false>, grid, block, 0, ctx->stream, text, m, L.carry, static_cast<uint32_t>(k), d_table,
+                               nslots, L.out);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    ScBuildOut out{};
+    VK_HIP(ctx, hipMemcpyAsync(&out, L.out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(status, L.status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *windows = out.windows;
+    *distinct = out.distinct;
+    // (a table without a free slot would be no table: a probe for an absent key ends at one)
+    return d_table && (out.full || out.distinct >= nslots) ? VK_ENOSPC : VK_OK;
+}
+
+int vk_screen_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes) {
+    if (!bytes || (nsamples && (!records || !lengths))) return VK_EINVAL;
+    *bytes = sc_layout(nullptr, records, nsamples, lengths).total;
+    return VK_OK;
+}
+
+int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+                     uint32_t nsamples, const uint64_t* d_table, uint64_t nslots, int k, uint32_t min_hits, int keep,
+                     uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_capacity, uint64_t* d_out_lengths,
+                     uint64_t* d_stats, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nsamples == 0 || !d_fastq || !offsets || !lengths || !records || !d_table || !d_out || !out_offsets ||
+        !d_out_lengths || !d_stats || !d_status || !d_ws)
+        return VK_EINVAL;
+    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || min_hits < 1 || !sc_slots_ok(nslots)) return VK_EINVAL;
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        if (offsets[i] % 16 || out_offsets[i] % 16) return VK_EINVAL;
+        if (out_offsets[i] > out_capacity || (lengths[i] + 15) / 16 * 16 > out_capacity - out_offsets[i]) return VK_ENOSPC;
+    }
+    const ScLayout L = sc_layout(d_ws, records, nsamples, lengths);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    // a sample is one file of the record index
+    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
+    std::vector<EmSample> smp(nsamples);
+    std::vector<uint64_t> rec_base(nsamples + 1ull, 0);
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
+                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
+        rec_base[i + 1] = rec_base[i] + records[i];
+    }
+    const uint64_t nrec = rec_base[nsamples];
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_fastq);
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_stats, 0, nsamples * 4ull * sizeof(uint64_t), ctx->stream));
+    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                       L.samples, nsamples, L.c.recs, L.c.cprefix, d_status);
+    const uint32_t nblocks = static_cast<uint32_t>((nrec + kScRecsPerBlock - 1) / kScRecsPerBlock);
+    if (nrec) {
+        const ScParams P{d_table, nslots, static_cast<uint32_t>(k), min_hits, keep ? 1u : 0u,
+                         ctx->screen_tile ? ctx->screen_tile : kScMaxTile};
+        hipLaunchKernelGGL(vk_sc_match_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.rec_base, nsamples,
+                           nrec, L.c.recs, d_status, P, L.obytes, reinterpret_cast<unsigned long long*>(d_stats));
+    }
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.obytes, nrec, L.c.sums, L.oprefix);
+    if (rc) return rc;
+    if (nrec)
+        hipLaunchKernelGGL(vk_sc_write_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.rec_base, L.out_offs, nsamples,
+                           nrec, L.c.recs, L.oprefix, d_out);
+    hipLaunchKernelGGL(vk_sc_pad_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.rec_base,
+                       L.out_offs, nsamples, L.oprefix, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }
 

@@ -121,6 +121,20 @@ def plain_route(threads, engine=None):
     return "mapped" if threads < MAPPED_BELOW_THREADS else "staged"
 
 
+class ScreenSet:
+    """The k-mer set of a screen's reference as ImageEngine.screen_set leaves it in HBM: the table (an int64 device
+    tensor of `slots` words, a free slot all ones), its k, the distinct keys it holds and the windows they came from.
+    The table is freed with the object."""
+
+    def __init__(self, table, slots, k, distinct, windows):
+        self.table, self.slots, self.k, self.distinct, self.windows = table, slots, k, distinct, windows
+
+    def keys(self):
+        """The keys as a sorted uint64 array on the host (tests)."""
+        t = self.table.cpu().numpy().view(np.uint64)
+        return np.sort(t[t != np.uint64(0xFFFFFFFFFFFFFFFF)])
+
+
 class ImageEngine:
     """FASTQ (in HBM) -> forward k-mer histograms -> uint8 images, for one k and mapping.
 
@@ -165,6 +179,7 @@ class ImageEngine:
         ex = self.__dict__.pop("_releaser", None)
         if ex is not None:
             ex.shutdown(wait=True)   # mapped files still being unpinned
+        self.__dict__.pop("screen_sets", None)   # (the tables of pipeline.Screen: freed with the engine)
         if getattr(self, "ctx", None):
             self.L.vk_ctx_destroy(self.ctx)
             self.ctx = None
@@ -1030,6 +1045,76 @@ class ImageEngine:
             want = int(((out_lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)).sum())
         _capi.check(self.ctx, st, "vk_ladder_emit_device")
         return out, out_offs, out_lens, status
+
+    def screen_set(self, fasta, length, k=31, slots=None):
+        """The k-mer set of a reference FASTA whose text lies in HBM (vk_screen_build_device; the rule: INTEGRATION.md,
+        "--exclude-fasta / --keep-fasta: the rule"): fasta a uint8 device tensor readable up to the 16-byte rounded end of
+        its first `length` bytes, k in 16..31.  slots: the table's size, a power of two of at least 1,024 (None: the
+        smallest that is at least twice the number of windows).  Returns a ScreenSet (table, slots, k, distinct,
+        windows); a text that does not begin with '>' raises ValueError.  Synchronises."""
+        torch = _torch()
+        length = int(length)
+        if not _capi.VK_SCREEN_MIN_K <= int(k) <= _capi.VK_SCREEN_MAX_K:
+            raise ValueError(f"the screen's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
+        if length > _capi.VK_SCREEN_MAX_REF:   # (before anything is allocated)
+            raise ValueError(f"a screen reference holds at most 2^30 sequence bytes: {length} bytes of text")
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_screen_build_workspace_size(length, C.byref(ws_bytes)), "vk_screen_build_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        windows, distinct, status = C.c_uint64(), C.c_uint64(), C.c_uint32()
+
+        def call(table, n):
+            st = self.L.vk_screen_build_device(self.ctx, self._ptr(fasta), length, int(k), self._ptr(table) if n else None, n,
+                                               self._ptr(ws), ws.numel(), C.byref(windows), C.byref(distinct), C.byref(status))
+            _capi.check(self.ctx, st, "vk_screen_build_device")
+            if status.value:
+                raise ValueError("the screen's reference is no FASTA text: it does not begin with '>'")
+
+        if slots is None:
+            call(None, 0)
+            slots = _capi.VK_SCREEN_MIN_SLOTS
+            while slots < 2 * windows.value:
+                slots *= 2
+        table = torch.empty(int(slots), dtype=torch.int64, device=self.device)
+        call(table, int(slots))
+        return ScreenSet(table, int(slots), int(k), int(distinct.value), int(windows.value))
+
+    def screen(self, text, offs, lens, sset, keep=False, min_hits=1, records=None):
+        """Cleaned samples in HBM screened record by record against a ScreenSet (vk_screen_device): keep=False keeps the
+        records with fewer than min_hits window positions in the set (--exclude-fasta), keep=True the others
+        (--keep-fasta).  records: the samples' record counts (None: clean_lines here).  Returns (out uint8 device tensor,
+        out_offs uint64[n], out_lens uint64[n], stats uint64[n, 4] = records in, records kept, sequence bases in,
+        sequence bases kept, status uint32[n]); sample i's text is out[out_offs[i] .. + out_lens[i]), laid out as clean()
+        lays its output out; a sample with a status gets no text.  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        if int(min_hits) < 1:
+            raise ValueError("min_hits is at least 1")
+        if records is None:
+            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        if len(recs) != n:
+            raise ValueError("one record count per sample")
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_screen_workspace_size(_u64(recs), n, _u64(lens), C.byref(ws_bytes)), "vk_screen_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        rounded = (lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)
+        out_offs = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            out_offs[1:] = np.cumsum(rounded[:-1])
+        total = int(rounded.sum()) + 16
+        out = torch.empty(total, dtype=torch.uint8, device=self.device)
+        out_lens = torch.empty(n, dtype=torch.int64, device=self.device)
+        stats = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = self.L.vk_screen_device(self.ctx, self._ptr(text), _u64(offs), _u64(lens), _u64(recs), n, self._ptr(sset.table),
+                                     sset.slots, sset.k, int(min_hits), 1 if keep else 0, self._ptr(out), _u64(out_offs), total,
+                                     self._ptr(out_lens), self._ptr(stats), self._ptr(status), self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_screen_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
+                status.cpu().numpy().astype(np.uint32))
 
     def deflate_bound(self, lengths):
         """Bytes that the files of texts of these lengths take at most (vk_deflate_bound)."""

@@ -334,7 +334,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False,
-                    gpu_gzip=False, gpu_png=False):
+                    gpu_gzip=False, gpu_png=False, screen=None):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
@@ -343,7 +343,8 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     split_dir: also write every step's reads to `split_dir/<sample>@<bp>K.fq.gz` (SplitSink), as the reference's
     split_fastq leaves them; overwrite: also where a sample's files are all there.  no_image (with split_dir: the
     reference's -X, :1055): stop after step C -- no counting, no PNG.  gpu_gzip: the files are compressed on the GPU
-    (SplitSink).  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).
+    (SplitSink).  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).  screen (Screen): the uploaded reads are
+    screened in HBM before the ladder (`--exclude-fasta` / `--keep-fasta`); the stats gain its three columns.
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -359,6 +360,8 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
         splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
         for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
+            if screen is not None:
+                dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [stem(f) for f in batch], stats, pool)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
                                     splits=splits, no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=is_query)
             if verbose:
@@ -367,6 +370,57 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
             splits.finish()
         sink.finish(stats)
     return stats
+
+
+@dataclass
+class Screen:
+    """`--exclude-fasta` / `--keep-fasta`: cleaned reads in HBM are screened against the k-mers of one reference FASTA
+    before the ladder sees them ("--exclude-fasta / --keep-fasta: the rule").  The set is built once per
+    rank and run, on the first use, and lives with the engine (ImageEngine.screen_sets)."""
+    fasta: object
+    k: int = 31
+    min_hits: int = 1
+    keep: bool = False
+
+    def set_on(self, eng, pool=None):
+        """The reference's ScreenSet on this engine: the file uploaded (a .gz inflated in HBM) and its set built on
+        the first call."""
+        sets = eng.__dict__.setdefault("screen_sets", {})
+        key = (str(self.fasta), self.k)
+        if key not in sets:
+            dev, _, lens = eng.upload_files([Path(self.fasta)], pool)
+            status = getattr(eng, "last_upload_status", None)
+            if status is not None and status[0]:
+                raise Exception(f"{self.fasta}: inflate status {int(status[0])}")
+            try:
+                sets[key] = eng.screen_set(dev, int(lens[0]), self.k)
+            except ValueError as e:
+                raise Exception(f"{self.fasta}: {e}") from e
+        return sets[key]
+
+    def report(self, sset, row):
+        """The `"screen"` object of `<sample>_fastp_gpu.json` for a sample's stats row."""
+        return {"reference": Path(self.fasta).name, "k": self.k, "min_hits": self.min_hits,
+                "mode": "keep" if self.keep else "exclude", "distinct_kmers": sset.distinct, **self.columns(row)}
+
+    @staticmethod
+    def columns(row):
+        """The columns of stats.csv for a sample's stats row (records in, records kept, bases in, bases kept)."""
+        return {"screen_reads_in": int(row[0]), "screen_reads_removed": int(row[0]) - int(row[1]),
+                "screen_basepairs_removed": int(row[2]) - int(row[3])}
+
+    def apply(self, eng, text, offs, lens, names, stats, pool=None):
+        """The samples `names` in HBM (text[offs[i] .. +lens[i])) screened: (text, offsets, lengths, stats rows) of what
+        is kept, laid out as the input was; fills the samples' columns in `stats` ({sample: OrderedDict}, or None).  A
+        sample whose framing the screen refuses keeps no reads, and fails where an empty cleaned sample fails."""
+        sset = self.set_on(eng, pool)
+        out, ooffs, olens, rows, status = eng.screen(text, offs, lens, sset, keep=self.keep, min_hits=self.min_hits)
+        for j, s in enumerate(names):
+            if status[j]:
+                eprint("SCREEN FAIL:", s, "- status", int(status[j]))
+            if stats is not None:
+                stats.setdefault(s, OrderedDict()).update(self.columns(rows[j]))
+        return out, ooffs, olens, rows
 
 
 def _seed_groups(names, seeds):
@@ -579,6 +633,7 @@ class Cleaning:
     clean_dir: object
     max_bp: int
     gpu_gzip: bool = False
+    screen: object = None   # `--exclude-fasta` / `--keep-fasta`: a Screen, applied right after the cleaning
     bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int, "groups": None or {sample: group}}; the plans then hold (file, role, select[, group, sample])
 
 
@@ -696,13 +751,15 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
     if clean_dir is not None:
         clean_dir.mkdir(parents=True, exist_ok=True)
 
-    def write_clean(sample, text, curves, cutting=None, compressed=False):
+    def write_clean(sample, text, curves, cutting=None, compressed=False, screened=None):
         """text: the cleaned reads, or with `compressed` the .fq.gz file's own bytes (opt.gpu_gzip)"""
         with open(clean_dir / (sample + ".fq.gz"), "wb") as fh:
             fh.write(text if compressed else gzip.compress(text, compresslevel=1))
         report = {"read1_after_filtering": {"content_curves": curves}}
         if cutting is not None:
             report["adapter_cutting"] = cutting
+        if screened is not None:
+            report["screen"] = screened
         with open(clean_dir / (sample + "_fastp_gpu.json"), "w") as fh:
             json.dump(report, fh)
 
@@ -779,6 +836,9 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
                                                           adapters=table)
         ast = rest[0] if rest else None   # (adapter stats: with a table only)
         del dev
+        srows = None
+        if opt.screen is not None:   # the cleaned text screened where it lies: the files and the ladder see what is kept
+            out, ooffs, olens, srows = opt.screen.apply(eng, out, ooffs, olens, [s for s, _ in batch], None, pool)
         packed = {}
         if clean_dir is not None and opt.gpu_gzip:   # the cleaned text compressed where it lies: only the files' bytes come back
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
@@ -800,6 +860,8 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
             base_sd[s] = curves_sd(curves)
             st["clean_basepairs"] = int(row[0]) if (opt.adapter or opt.merge) else float("nan")
             st["cleaning_time"] = (tc - t0) / len(batch)
+            if srows is not None:
+                st.update(opt.screen.columns(srows[j]))
             if clean_dir is not None:
                 text = packed[j] if opt.gpu_gzip else out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
                 cutting = None
@@ -808,7 +870,8 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
                     cutting = {"read1_adapter_sequence": name[0], "read2_adapter_sequence": name[1],
                                "single_adapter_sequence": name[2], "adapter_trimmed_reads": int(ast[j][0]),
                                "adapter_trimmed_bases": int(ast[j][1])}
-                writes.append(pool.submit(write_clean, s, text, curves, cutting, opt.gpu_gzip))
+                screened = None if srows is None else opt.screen.report(opt.screen.set_on(eng), srows[j])
+                writes.append(pool.submit(write_clean, s, text, curves, cutting, opt.gpu_gzip, screened))
             ok.append(j)
         if verbose:
             eprint(f"batch of {len(batch)} samples, {nbytes} raw bytes: upload+clean {tc - t0:.3f}s")
@@ -820,7 +883,7 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
                   detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None,
-                  gpu_png=False):
+                  gpu_png=False, screen=None):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -837,11 +900,15 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     bam = {"pairs": bool, "exclude": int}: `--from-bam` -- every sample is ONE BAM file, converted to FASTQ text in HBM
     between the upload and the cleaning (_bam_texts; the rule: INTEGRATION.md, "--from-bam: the rule").
 
+    screen (Screen): `--exclude-fasta` / `--keep-fasta` -- the cleaned text is screened in HBM right after the cleaning,
+    so clean_dir's files, split_dir's files and the ladder see the reads that are kept; the stats gain `screen_reads_in`,
+    `screen_reads_removed`, `screen_basepairs_removed` (`clean_basepairs` and the base-frequency sd stay the cleaning's).
+
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
     mine = _raw_plans(samples, weights, rank, world, bam)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen, bam)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels, eng if gpu_png else None)
@@ -872,15 +939,15 @@ def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, 
 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
                  seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
-                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None):
+                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None, screen=None):
     """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
     cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
-    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU).  bam: as
-    raw_to_images takes it."""
+    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU).  bam, screen: as
+    raw_to_images takes them."""
     mine = _raw_plans(samples, weights, rank, world, bam)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen, bam)
     stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
@@ -892,14 +959,17 @@ def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), a
 
 
 def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, k=7, mapping_code="cgr", device=0,
-                   batch_bytes=None, io_threads=8):
+                   batch_bytes=None, io_threads=8, screen=None):
     """raw_to_query's result for samples = [(sample, its cleaned read file)] that an earlier run left in clean_dir
-    (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table)."""
+    (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table).  screen (Screen): the
+    uploaded reads are screened in HBM before they are subsampled."""
     samples = [(s, Path(f)) for s, f in samples]
     found = OrderedDict()
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for batch, _, _ in batches(samples, batch_bytes or DEFAULT_BATCH_BYTES, size=lambda sample: text_bytes(sample[1])):
             files = [f for _, f in batch]
             dev, offs, lens = eng.upload_files(files, pool)
+            if screen is not None:
+                dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [s for s, _ in batch], None, pool)
             _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], files, seeds or {}, max_bp, base_sd or {}, found)
     return found
