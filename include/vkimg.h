@@ -670,6 +670,46 @@ int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, 
                      uint32_t min_hits, int keep, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_capacity,
                      uint64_t* d_out_lengths, uint64_t* d_stats, uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
+/* `image / query --qc-report`: the quality profile of FASTQ streams in HBM -- what fastp's report states about the reads
+ * before and after filtering (the reference copies `*_fastp_*.json` and `*.html` next to the cleaned reads,
+ * commands/image.py:545-547, and users read them).  The rule is this project's ("--qc-report: the rule",
+ * and tests/qc_ref.py).
+ *
+ * Stream i is d_text[offsets[i] .. + lengths[i]) (offsets[i] a multiple of 16, any other returns VK_EINVAL before anything
+ * is read; readable up to its 16-byte rounded end; shorter than 4 GiB) and only its first records[i] records count: a read
+ * budget, as vk_clean_device takes it.  A record is four lines as vk_ladder_emit_device frames them (a trailing '\r' no
+ * part of a line, the last line with or without '\n').  With ls and lq the lengths of its sequence and quality lines:
+ * a record with ls != lq adds 1 to records and to ragged_records and nothing else.  Every other record counts its bases by
+ * class (A C G T of either case 0 1 2 3, every other byte 4) and its quality bytes b as q = min(max(b - 33, 0), 93), a byte
+ * outside 33..126 also once in invalid_quality_bytes.
+ *
+ * d_rows[nstreams][VK_QC_NSTAT], u64 in this order:
+ *     0 records   1 ragged_records   2 bases   3 gc_bases   4 other_bases   5 min_length   6 max_length
+ *     7 invalid_quality_bytes        (min_length is 0 in a row without counted records)
+ *     VK_QC_QUAL_HIST   94: bases of quality q (their sum is bases)
+ *     VK_QC_READQ_HIST  94: reads of mean quality floor(sum q / ls), ls > 0
+ *     VK_QC_LEN_HIST    1025: reads of length min(ls, 1024)
+ *     VK_QC_CYCLE_BASE  [VK_QC_CYCLES][5]: bases of each class at cycle c < VK_QC_CYCLES
+ *     VK_QC_CYCLE_QSUM  [VK_QC_CYCLES][5]: their qualities summed
+ * d_status[nstreams]: VK_QC_BAD_FRAMING when a budgeted record's header does not start with '@' or its third line not
+ * with '+'; VK_EM_BAD_RECORDS (alone) when the text holds fewer than 4 records[i] lines.  A stream with a status gets an
+ * all-zero row and disturbs no other; a defect behind the budget is not seen.  Results are integers and do not depend on
+ * the launch.  d_ws: caller-allocated device workspace of vk_qc_workspace_size bytes (same records and lengths).
+ * VK_EINVAL for a null pointer, nstreams 0, an unaligned offset, a stream of 4 GiB or more, a workspace that is too small.
+ * offsets, lengths and records are host arrays (read when the call returns).  The call allocates no device memory and
+ * does not synchronise: it is enqueued on the context's stream. */
+#define VK_QC_BAD_FRAMING 16u
+#define VK_QC_CYCLES 1024u
+#define VK_QC_QUAL_HIST 8u
+#define VK_QC_READQ_HIST 102u
+#define VK_QC_LEN_HIST 196u
+#define VK_QC_CYCLE_BASE 1221u
+#define VK_QC_CYCLE_QSUM 6341u
+#define VK_QC_NSTAT 11461u
+int vk_qc_workspace_size(const uint64_t* records, const uint64_t* lengths, uint32_t nstreams, uint64_t* bytes);
+int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+                 uint32_t nstreams, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

@@ -118,6 +118,7 @@ def setup_parser():
                         "Not with -X")
     add_adapter_flags(p)
     add_screen_flags(p)
+    add_qc_flag(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
     q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads); with --from-raw, "
@@ -180,6 +181,7 @@ def setup_parser():
                         "512 x 512 in 36 ms against 313 ms (profiles/ab/unpng_time.txt)")
     add_adapter_flags(q)
     add_screen_flags(q)
+    add_qc_flag(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Convert images between different kmer mappings.")          # cli.py:447-482
@@ -291,6 +293,19 @@ def add_screen_flags(p):
     p.add_argument("--screen-min-hits", type=int, default=argparse.SUPPRESS, metavar="N",
                    help="with --exclude-fasta / --keep-fasta: a read matches when at least N of its k-mer positions are in "
                         "the reference (1 when absent)")
+
+
+def add_qc_flag(p):
+    p.add_argument("--qc-report", default=argparse.SUPPRESS, metavar="DIR",   # (absent = no report)
+                   help="write DIR/<sample>.qc.json: reads, bases, Q20/Q30 rates, GC content, read lengths and per-cycle "
+                        "quality and base-content curves of the reads before and after cleaning, counted on the GPU where "
+                        "their text lies, and add their columns to stats.csv; where the run starts from cleaned reads "
+                        "the report has the `after` sections only (rule: INTEGRATION.md, \"--qc-report: the rule\")")
+
+
+def qc_options(args):
+    """The folder of `--qc-report`, None without it."""
+    return Path(args.qc_report) if hasattr(args, "qc_report") else None
 
 
 def screen_options(args):
@@ -422,6 +437,15 @@ def parse_args(argv=None):
             ref = getattr(args, "keep_fasta", None) or getattr(args, "exclude_fasta", None)
             if not Path(ref).is_file():
                 parser.error(f"{which[0]}: no such file: {ref}")
+    if args.command in ("image", "query") and hasattr(args, "qc_report"):
+        # only where reads lie in HBM as FASTQ text whole: raw files, BAM files' reads, cleaned reads
+        if getattr(args, "from_fasta", False):
+            parser.error("--qc-report: not with --from-fasta (assemblies have no qualities)")
+        if args.command == "query" and args.images:
+            parser.error("--qc-report: not with -I/--images (no reads)")
+        if args.command == "image" and not (args.from_raw or args.from_clean or from_bam):
+            parser.error("--qc-report: only with --from-raw, --from-bam or --from-clean (the default entry takes "
+                         "subsamples that are drawn already)")
     if getattr(args, "gpu_png", False):
         if args.command == "query" and not args.keep_images:
             parser.error("--gpu-png: only with -m/--keep-images")
@@ -639,7 +663,8 @@ def run_query(args):
                 wanted = [(i, stem(inputs[i])) for i in mine]
                 found = clean_to_query([(s, inputs[i]) for i, s in wanted], max_bp=max_bp, seeds=seeds, engine=eng,
                                        k=args.kmer_size, mapping_code=args.kmer_mapping,
-                                       io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args))
+                                       io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args),
+                                       qc_dir=qc_options(args))
                 images = found_images(found, wanted, {})
         if rank == 0:
             if args.single_label:
@@ -754,7 +779,7 @@ class RawPlan:
         from .shard import io_threads_per_rank, shard_by_size
         args = self.args
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp_of(args), seeds=self.seeds, engine=eng,
-                      io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args))
+                      io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args), qc_dir=qc_options(args))
         found = {}
         if self.raw:
             found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
@@ -814,7 +839,8 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
                                      min_bp=parse_size(args.min_bp), max_bp=max_bp, seeds=seeds, labels=labels,
                                      base_sd=base_sd, **split_options(args), gpu_gzip=getattr(args, "gpu_gzip", False),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
-                                     verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), screen=screen_options(args))
+                                     verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), screen=screen_options(args),
+                                     qc_dir=qc_options(args))
         for s, v in per_sample.items():
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
@@ -879,7 +905,7 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
                       gpu_gzip=getattr(args, "gpu_gzip", False), gpu_png=getattr(args, "gpu_png", False),
-                      screen=screen_options(args))
+                      screen=screen_options(args), qc_dir=qc_options(args))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, bam=plan.bam, **cleaning,
                                      **common)

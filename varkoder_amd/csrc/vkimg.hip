@@ -31,6 +31,7 @@
 //   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
 //   vk_bam_*_kernel (vk_bam.h): BAM records to FASTQ text (`--from-bam`): record starts guessed per segment, verified in order.
 //   vk_bam_groups_*_kernel (vk_bam_groups.h): the same split by read group (`--bam-read-groups`): one emit workgroup per panel.
+//   vk_qc_*_kernel (vk_qc.h): quality profiles of FASTQ streams (`--qc-report`): wave per record, lanes on cycles, counters in LDS merged per workgroup.
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
 
@@ -70,6 +71,7 @@
 #include "vk_bam.h"
 #include "vk_bam_groups.h"
 #include "vk_screen.h"
+#include "vk_qc.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -166,6 +168,7 @@ struct vk_ctx {
     size_t bamgws_cap = 0;
     uint32_t bam_panel_segs = 0;   // VKIMG_BAM_PANEL_SEGS=n: segments of a panel of the grouped BAM calls, 1 .. 4096 (tests: many panels in little data; 0 = 4)
     uint64_t bam_groups_wgs = 0, bam_groups_walked = 0;   // of the last of those calls (vk_last_bam_groups)
+    uint32_t qc_merge = 0;         // VKIMG_QC_MERGE=n: records per workgroup of the QC count kernel, 1 to VK_QC_MERGE (tests: many merges in small cases; 0 = VK_QC_MERGE)
     uint32_t screen_tile = 0;      // VKIMG_SCREEN_TILE=n: bases of a wavefront's tile of the screen's match kernel, a multiple of 64 from 64 to 4096 (tests: tile seams in short reads; 0 = 4096)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
@@ -685,6 +688,8 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
         if (ctx->screen_tile < 64) ctx->screen_tile = 64;
         if (ctx->screen_tile > kScMaxTile) ctx->screen_tile = kScMaxTile;
     }
+    env_uint("VKIMG_QC_MERGE", &ctx->qc_merge);
+    if (ctx->qc_merge > kQcMerge) ctx->qc_merge = kQcMerge;
     env_uint("VKIMG_BAM_PANEL_SEGS", &ctx->bam_panel_segs);
     if (ctx->bam_panel_segs > 4096) ctx->bam_panel_segs = 4096;
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
@@ -3605,6 +3610,96 @@ int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, 
                            nrec, L.c.recs, L.oprefix, d_out);
     hipLaunchKernelGGL(vk_sc_pad_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.rec_base,
                        L.out_offs, nsamples, L.oprefix, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- quality profiles of FASTQ streams (vk_qc.h) ------
+
+namespace {
+
+// the pieces of a vk_qc_device workspace: the record index in vk_clean_device's layout (the pieces of it that
+// cl_index_run fills), then the streams' tables
+struct QcLayout {
+    ClLayout c;
+    QcStream* streams;
+    uint64_t* block_base;
+    uint32_t* bad;
+    size_t total;
+};
+
+QcLayout qc_layout(void* d_ws, const uint64_t* records, const uint64_t* lengths, uint32_t nstreams) {
+    QcLayout L{};
+    for (uint32_t i = 0; i < nstreams; ++i) {
+        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        L.c.nrec += records[i];
+    }
+    const uint64_t nb = (L.c.nchunks + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.c.files, nstreams);
+    take(L.c.fchunk, nstreams);
+    take(L.c.ccount, L.c.nchunks);
+    take(L.c.cprefix, L.c.nchunks + 1);
+    take(L.c.sums, nb + 1);
+    take(L.c.recs, L.c.nrec);
+    take(L.streams, nstreams);
+    take(L.block_base, nstreams + 1ull);
+    take(L.bad, nstreams);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_qc_workspace_size(const uint64_t* records, const uint64_t* lengths, uint32_t nstreams, uint64_t* bytes) {
+    if (!bytes || (nstreams && (!records || !lengths))) return VK_EINVAL;
+    *bytes = qc_layout(nullptr, records, lengths, nstreams).total;
+    return VK_OK;
+}
+
+int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+                 uint32_t nstreams, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nstreams == 0 || !d_text || !offsets || !lengths || !records || !d_rows || !d_status || !d_ws) return VK_EINVAL;
+    const uint32_t per_block = ctx->qc_merge ? ctx->qc_merge : kQcMerge;
+    uint64_t nblocks = 0;
+    for (uint32_t i = 0; i < nstreams; ++i) {
+        // (a stream of 4 GiB or more: the lanes' sums and a record's lengths are 32-bit)
+        if (offsets[i] % 16 || lengths[i] >= (1ull << 32)) return VK_EINVAL;
+        nblocks += (records[i] + per_block - 1) / per_block;
+    }
+    if (nblocks >= (1ull << 31)) return VK_EINVAL;
+    const QcLayout L = qc_layout(d_ws, records, lengths, nstreams);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    // a stream is one file of the record index
+    std::vector<uint32_t> roles(nstreams, VK_CL_ROLE_UNPAIRED), owner(nstreams);
+    for (uint32_t i = 0; i < nstreams; ++i) owner[i] = i;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nstreams, nstreams, ~0ull);
+    std::vector<QcStream> str(nstreams);
+    std::vector<uint64_t> block_base(nstreams + 1ull, 0);
+    for (uint32_t i = 0; i < nstreams; ++i) {
+        str[i] = QcStream{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
+                          i + 1 < nstreams ? ix.files[i + 1].chunk0 : ix.nchunks};
+        block_base[i + 1] = block_base[i] + (records[i] + per_block - 1) / per_block;
+    }
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.streams, str.data(), nstreams * sizeof(QcStream), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(L.bad, 0, nstreams * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nstreams) * kQcNstat * sizeof(uint64_t), ctx->stream));
+    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_qc_status_kernel, dim3((nstreams + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                       L.streams, nstreams, L.c.cprefix, d_rows, d_status);
+    if (nblocks)
+        hipLaunchKernelGGL(vk_qc_count_kernel, dim3(static_cast<uint32_t>(nblocks)), dim3(kQcThreads), 0, ctx->stream, text, L.streams,
+                           L.block_base, nstreams, per_block, L.c.recs, d_rows, d_status, L.bad);
+    hipLaunchKernelGGL(vk_qc_finish_kernel, dim3(nstreams), dim3(kClThreads), 0, ctx->stream, d_rows, d_status, L.bad);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

@@ -1116,6 +1116,32 @@ class ImageEngine:
         return (out, out_offs, out_lens.cpu().numpy().astype(np.uint64), stats.cpu().numpy().astype(np.uint64),
                 status.cpu().numpy().astype(np.uint32))
 
+    def qc(self, text, offs, lens, records=None):
+        """The quality profiles of FASTQ streams in HBM, raw or cleaned (vk_qc_device; the rule: INTEGRATION.md,
+        "--qc-report: the rule"): stream i is text[offs[i] .. + lens[i]) and its first records[i] records count (None:
+        all of them, by clean_lines here).  Returns (rows uint64[n, VK_QC_NSTAT], status uint32[n]); a stream with a
+        status has an all-zero row.  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        if n == 0:
+            return np.zeros((0, _capi.VK_QC_NSTAT), dtype=np.uint64), np.zeros(0, dtype=np.uint32)
+        if records is None:
+            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        if len(recs) != n:
+            raise ValueError("one record budget per stream")
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_qc_workspace_size(_u64(recs), _u64(lens), n, C.byref(ws_bytes)), "vk_qc_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        rows = torch.empty((n, _capi.VK_QC_NSTAT), dtype=torch.int64, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        st = self.L.vk_qc_device(self.ctx, self._ptr(text), _u64(offs), _u64(lens), _u64(recs), n, self._ptr(rows),
+                                 self._ptr(status), self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_qc_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        return rows.cpu().numpy().view(np.uint64), status.cpu().numpy().astype(np.uint32)
+
     def deflate_bound(self, lengths):
         """Bytes that the files of texts of these lengths take at most (vk_deflate_bound)."""
         lens = np.ascontiguousarray(lengths, dtype=np.uint64)

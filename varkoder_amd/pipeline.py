@@ -334,7 +334,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False,
-                    gpu_gzip=False, gpu_png=False, screen=None):
+                    gpu_gzip=False, gpu_png=False, screen=None, qc_dir=None):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
@@ -344,7 +344,9 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     split_fastq leaves them; overwrite: also where a sample's files are all there.  no_image (with split_dir: the
     reference's -X, :1055): stop after step C -- no counting, no PNG.  gpu_gzip: the files are compressed on the GPU
     (SplitSink).  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).  screen (Screen): the uploaded reads are
-    screened in HBM before the ladder (`--exclude-fasta` / `--keep-fasta`); the stats gain its three columns.
+    screened in HBM before the ladder (`--exclude-fasta` / `--keep-fasta`); the stats gain its three columns.  qc_dir
+    (`--qc-report`): `<qc_dir>/<sample>.qc.json` of the uploaded reads (behind the screen), its `after` sections only, and
+    qc.columns' columns in the stats.
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -358,14 +360,20 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd or {}, subfolder_levels, eng if gpu_png else None)
         splits = SplitSink(split_dir, pool, overwrite, gpu_gzip) if split_dir is not None else None
+        reports = []
         for batch, nbytes, t0 in batches(mine, batch_bytes):
             dev, offs, lens = eng.upload_files(batch, pool)
             if screen is not None:
                 dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [stem(f) for f in batch], stats, pool)
+            if qc_dir is not None:
+                for f, row in zip(batch, QcReport.after(eng, dev, offs, lens)):
+                    QcReport(qc_dir).emit(stem(f), None, row, stats.setdefault(stem(f), OrderedDict()), pool, reports)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
                                     splits=splits, no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=is_query)
             if verbose:
                 eprint(f"batch of {len(batch)} samples, {nbytes} bytes: upload+ladder {t1 - t0:.3f}s images {t2 - t1:.3f}s")
+        for w in reports:
+            w.result()
         if splits is not None:
             splits.finish()
         sink.finish(stats)
@@ -421,6 +429,38 @@ class Screen:
             if stats is not None:
                 stats.setdefault(s, OrderedDict()).update(self.columns(rows[j]))
         return out, ooffs, olens, rows
+
+
+@dataclass
+class QcReport:
+    """`--qc-report DIR`: the reads' quality profiles, counted where their text lies in HBM (ImageEngine.qc; the rule:
+    INTEGRATION.md, "--qc-report: the rule") -- the raw texts under the cleaning's read budget and the cleaned text as the
+    ladder sees it -- written as `DIR/<sample>.qc.json` (qc.report) with their stats.csv columns (qc.columns)."""
+    dir: object
+
+    @staticmethod
+    def before(eng, text, offs, lens, records, roles, owner, nsamples):
+        """Per sample {"read1" | "read2" | "single": row} of the raw streams in HBM: stream i gives its first records[i]
+        records to sample owner[i] as roles[i]; a role's streams are taken together, a role without one has no entry.
+        A stream with a status counts as empty (the cleaning fails its sample)."""
+        from . import qc
+        rows, _ = eng.qc(text, offs, lens, records)
+        parts = [dict() for _ in range(nsamples)]
+        for i, (role, j) in enumerate(zip(roles, owner)):
+            parts[j].setdefault(qc.ROLE_KEYS[int(role)], []).append(rows[i])
+        return [{role: qc.add_rows(rs) for role, rs in p.items()} for p in parts]
+
+    @staticmethod
+    def after(eng, text, offs, lens):
+        """The rows of cleaned samples in HBM, every record counted."""
+        return eng.qc(text, offs, lens)[0]
+
+    def emit(self, sample, before, after, stats_row, pool, writes):
+        """A sample's file queued on the pool (its future goes to `writes`) and its columns into stats_row (None: none)."""
+        from . import qc
+        if stats_row is not None:
+            stats_row.update(qc.columns(qc.add_rows(before.values()) if before else None, after))
+        writes.append(pool.submit(qc.write_report, self.dir, sample, qc.report(before, after)))
 
 
 def _seed_groups(names, seeds):
@@ -634,6 +674,7 @@ class Cleaning:
     max_bp: int
     gpu_gzip: bool = False
     screen: object = None   # `--exclude-fasta` / `--keep-fasta`: a Screen, applied right after the cleaning
+    qc: object = None   # `--qc-report`: a QcReport
     bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int, "groups": None or {sample: group}}; the plans then hold (file, role, select[, group, sample])
 
 
@@ -835,10 +876,15 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
                                                           adapter=opt.adapter, merge=opt.merge, dedup=opt.dedup,
                                                           adapters=table)
         ast = rest[0] if rest else None   # (adapter stats: with a table only)
+        qc_before = opt.qc.before(eng, dev, offs, lens, records, roles, owner, len(batch)) if opt.qc is not None else None
         del dev
         srows = None
         if opt.screen is not None:   # the cleaned text screened where it lies: the files and the ladder see what is kept
             out, ooffs, olens, srows = opt.screen.apply(eng, out, ooffs, olens, [s for s, _ in batch], None, pool)
+        qc_after = {}
+        if opt.qc is not None:   # (behind the screen: what the ladder sees)
+            good = [j for j in range(len(batch)) if not status[j] and j not in failed]
+            qc_after = dict(zip(good, opt.qc.after(eng, out, ooffs[good], olens[good])))
         packed = {}
         if clean_dir is not None and opt.gpu_gzip:   # the cleaned text compressed where it lies: only the files' bytes come back
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
@@ -862,6 +908,8 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
             st["cleaning_time"] = (tc - t0) / len(batch)
             if srows is not None:
                 st.update(opt.screen.columns(srows[j]))
+            if opt.qc is not None:
+                opt.qc.emit(s, qc_before[j], qc_after[j], st, pool, writes)
             if clean_dir is not None:
                 text = packed[j] if opt.gpu_gzip else out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
                 cutting = None
@@ -883,7 +931,7 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
                   detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None,
-                  gpu_png=False, screen=None):
+                  gpu_png=False, screen=None, qc_dir=None):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -904,11 +952,15 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     so clean_dir's files, split_dir's files and the ladder see the reads that are kept; the stats gain `screen_reads_in`,
     `screen_reads_removed`, `screen_basepairs_removed` (`clean_basepairs` and the base-frequency sd stay the cleaning's).
 
+    qc_dir: `--qc-report` -- `<qc_dir>/<sample>.qc.json` (QcReport) of the raw texts under their read budget and of the
+    cleaned text behind the screen; the stats gain qc.columns' columns.
+
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
     mine = _raw_plans(samples, weights, rank, world, bam)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen,
+                   None if qc_dir is None else QcReport(qc_dir), bam)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels, eng if gpu_png else None)
@@ -939,15 +991,17 @@ def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, 
 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
                  seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
-                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None, screen=None):
+                 weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None, screen=None,
+                 qc_dir=None):
     """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
     cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
-    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU).  bam, screen: as
-    raw_to_images takes them."""
+    the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU), and with qc_dir
+    the samples' `.qc.json`.  bam, screen, qc_dir: as raw_to_images takes them."""
     mine = _raw_plans(samples, weights, rank, world, bam)
-    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen, bam)
+    opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen,
+                   None if qc_dir is None else QcReport(qc_dir), bam)
     stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
@@ -959,17 +1013,23 @@ def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), a
 
 
 def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, k=7, mapping_code="cgr", device=0,
-                   batch_bytes=None, io_threads=8, screen=None):
+                   batch_bytes=None, io_threads=8, screen=None, qc_dir=None):
     """raw_to_query's result for samples = [(sample, its cleaned read file)] that an earlier run left in clean_dir
     (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table).  screen (Screen): the
-    uploaded reads are screened in HBM before they are subsampled."""
+    uploaded reads are screened in HBM before they are subsampled.  qc_dir (`--qc-report`): `<qc_dir>/<sample>.qc.json`
+    of the uploaded reads (behind the screen), its `after` sections only."""
     samples = [(s, Path(f)) for s, f in samples]
-    found = OrderedDict()
+    found, reports = OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for batch, _, _ in batches(samples, batch_bytes or DEFAULT_BATCH_BYTES, size=lambda sample: text_bytes(sample[1])):
             files = [f for _, f in batch]
             dev, offs, lens = eng.upload_files(files, pool)
             if screen is not None:
                 dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [s for s, _ in batch], None, pool)
+            if qc_dir is not None:
+                for (s, _), row in zip(batch, QcReport.after(eng, dev, offs, lens)):
+                    QcReport(qc_dir).emit(s, None, row, None, pool, reports)
             _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], files, seeds or {}, max_bp, base_sd or {}, found)
+        for w in reports:
+            w.result()
     return found
