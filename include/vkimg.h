@@ -710,6 +710,36 @@ int vk_qc_workspace_size(const uint64_t* records, const uint64_t* lengths, uint3
 int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
                  uint32_t nstreams, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
+/* `compare`: exact squared Euclidean distances between images and the nearest neighbours of every query among the
+ * references (the rule: INTEGRATION.md, "`compare`: the rule", and tests/dist_ref.py).  Neither the reference nor any
+ * other call here compares images.
+ *
+ * d_q: u8 [nq][npix], d_r: u8 [nr][npix], pixels of any count (no side is assumed); d_q == d_r with nq == nr is allowed
+ * (self mode: the rows are prepared once).  d2(i, j) = sum over p of (q[i][p] - r[j][p])^2, an exact integer.
+ * d_qgroup u32[nq], d_rgroup u32[nr]: group ids, both or neither (null: no groups); reference j is eligible for query i
+ * if d_qgroup[i] == VK_DIST_NO_GROUP or d_rgroup[j] != d_qgroup[i].  The neighbours of i are its n_neighbours eligible
+ * references with the smallest (d2, j) -- d2 first, then the lower j -- written in that order to d_idx u32[nq][n] and
+ * d_d2 u64[nq][n]; slots without an eligible reference hold VK_DIST_NO_IDX and VK_DIST_NO_D2.  d_matrix, if not null:
+ * u64 [nq][nr], every d2 (eligibility does not apply).
+ *
+ * Limits: 1 <= n_neighbours <= VK_DIST_MAX_NEIGHBOURS, 1 <= npix <= VK_DIST_MAX_PIXELS, 1 <= nr <= VK_DIST_MAX_REFS,
+ * 1 <= nq < 2^31, and 65025 npix + 1 < 2^(64 - b) with b the bits of nr - 1 (1 at least): a distance and an index share a
+ * 64-bit key.  Up to 264,208 pixels (512 x 512 included) that holds for every nr; an input it refuses would not fit
+ * the device's memory.  VK_EINVAL for anything else, a null pointer, one group array without the other, a workspace
+ * smaller than vk_dist_workspace_size states (same nq, nr, npix; n_neighbours and want_matrix do not change it).
+ * Results are integers and do not depend on the launch or on VKIMG_DIST_STRIP.  The call allocates no device memory and
+ * does not synchronise: it is enqueued on the context's stream. */
+#define VK_DIST_NO_GROUP 0xFFFFFFFFu
+#define VK_DIST_NO_IDX 0xFFFFFFFFu
+#define VK_DIST_NO_D2 0xFFFFFFFFFFFFFFFFull
+#define VK_DIST_MAX_NEIGHBOURS 64u
+#define VK_DIST_MAX_PIXELS (1u << 20)
+#define VK_DIST_MAX_REFS (1u << 30)
+int vk_dist_workspace_size(uint64_t nq, uint64_t nr, uint64_t npix, uint32_t n_neighbours, int want_matrix, uint64_t* bytes);
+int vk_dist_device(vk_ctx* ctx, const void* d_q, uint64_t nq, const void* d_r, uint64_t nr, uint64_t npix, const uint32_t* d_qgroup,
+                   const uint32_t* d_rgroup, uint32_t n_neighbours, uint32_t* d_idx, uint64_t* d_d2, uint64_t* d_matrix, void* d_ws,
+                   uint64_t ws_bytes);
+
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */
 int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uint32_t* lds_bytes);

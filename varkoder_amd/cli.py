@@ -245,6 +245,27 @@ def setup_parser():
                         "file, and any the decoder refuses, is decoded by PIL as without the flag); the training set is "
                         "the same. Measured: 4,000 files of 128 x 128 in 80 ms against 403 ms, 400 of 512 x 512 in 36 ms "
                         "against 313 ms (profiles/ab/unpng_time.txt)")
+    m = sub.add_parser("compare", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                       help="Nearest neighbours among images by exact squared Euclidean distance, computed on the GPU "
+                            "(no model; not in the reference).")
+    m.add_argument("input", help="path to the folder with the images to compare (IMAGES).")
+    m.add_argument("outdir", help="path to the folder where neighbours.csv and samples.csv will be written (OUT).")
+    m.add_argument("--against", metavar="REF_IMAGES",
+                   help="folder of reference images: the neighbours of every image of IMAGES are looked for among these, "
+                        "without exclusions. By default IMAGES is compared with itself.")
+    m.add_argument("-N", "--neighbours", type=int, default=10, help="neighbours per image, 1 to 64.")
+    m.add_argument("--same-sample", action="store_true", default=False,
+                   help="let the other images of an image's own sample (its other bp steps) be its neighbours: only the "
+                        "image itself is excluded. Not with --against.")
+    m.add_argument("--matrix", action="store_true", default=False,
+                   help="also write every distance: distances.npy (uint64) with distances_rows.txt and distances_cols.txt; "
+                        "refused above 4 GiB.")
+    m.add_argument("-t", "--label-table", help="csv table `sample,labels`; by default labels come from the image metadata.")
+    m.add_argument("--gpu-png-read", action="store_true", default=argparse.SUPPRESS,   # (absent = off)
+                   help="decode the image files on the GPU, as `train --gpu-png-read` does; the images are the same.")
+    m.add_argument("-n", "--n-threads", type=int, default=1, help="accepted for parity and inert: the files are read in turn")
+    m.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
+    m.add_argument("-v", "--verbose", action="store_true", default=False)
     return main
 
 
@@ -358,6 +379,12 @@ def parse_args(argv=None):
     with -a, and their sequences are checked."""
     parser = setup_parser()
     args = parser.parse_args(argv)
+    if args.command == "compare":
+        if not 1 <= args.neighbours <= 64:
+            parser.error("-N/--neighbours: 1 to 64")
+        if args.same_sample and args.against:
+            parser.error("--same-sample: not with --against (nothing is excluded there)")
+        return args
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
     from_bam = args.command in ("image", "query") and getattr(args, "from_bam", False)
@@ -1079,6 +1106,9 @@ def main(argv=None):
     elif args.command == "train":
         from .train import run_train
         run_train(args)
+    elif args.command == "compare":
+        from .compare import run_compare
+        run_compare(args)
     eprint("DONE")
 
 

@@ -31,6 +31,7 @@
 //   vk_faw_*_kernel (vk_fasta_windows.h): the same per window of a record (`--windows`): tiles by start, summed to windows.
 //   vk_bam_*_kernel (vk_bam.h): BAM records to FASTQ text (`--from-bam`): record starts guessed per segment, verified in order.
 //   vk_bam_groups_*_kernel (vk_bam_groups.h): the same split by read group (`--bam-read-groups`): one emit workgroup per panel.
+//   vk_dist_*_kernel (vk_dist.h): exact distances between images and nearest neighbours (`compare`): centred i8 rows, tiles on the i8 matrix cores, a workgroup's selection per row.
 //   vk_qc_*_kernel (vk_qc.h): quality profiles of FASTQ streams (`--qc-report`): wave per record, lanes on cycles, counters in LDS merged per workgroup.
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
@@ -72,6 +73,7 @@
 #include "vk_bam_groups.h"
 #include "vk_screen.h"
 #include "vk_qc.h"
+#include "vk_dist.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -169,6 +171,7 @@ struct vk_ctx {
     uint32_t bam_panel_segs = 0;   // VKIMG_BAM_PANEL_SEGS=n: segments of a panel of the grouped BAM calls, 1 .. 4096 (tests: many panels in little data; 0 = 4)
     uint64_t bam_groups_wgs = 0, bam_groups_walked = 0;   // of the last of those calls (vk_last_bam_groups)
     uint32_t qc_merge = 0;         // VKIMG_QC_MERGE=n: records per workgroup of the QC count kernel, 1 to VK_QC_MERGE (tests: many merges in small cases; 0 = VK_QC_MERGE)
+    uint32_t dist_strip = 0;       // VKIMG_DIST_STRIP=n: query rows of a strip of vk_dist_device, from 1 up to what the workspace holds (tests: strip seams in small inputs; 0 = what the workspace holds)
     uint32_t screen_tile = 0;      // VKIMG_SCREEN_TILE=n: bases of a wavefront's tile of the screen's match kernel, a multiple of 64 from 64 to 4096 (tests: tile seams in short reads; 0 = 4096)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
@@ -690,6 +693,7 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     }
     env_uint("VKIMG_QC_MERGE", &ctx->qc_merge);
     if (ctx->qc_merge > kQcMerge) ctx->qc_merge = kQcMerge;
+    env_uint("VKIMG_DIST_STRIP", &ctx->dist_strip);
     env_uint("VKIMG_BAM_PANEL_SEGS", &ctx->bam_panel_segs);
     if (ctx->bam_panel_segs > 4096) ctx->bam_panel_segs = 4096;
     ctx->no_read_index = getenv("VKIMG_NO_READ_INDEX") != nullptr;   // (set at all, as ever)
@@ -3700,6 +3704,84 @@ int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const
         hipLaunchKernelGGL(vk_qc_count_kernel, dim3(static_cast<uint32_t>(nblocks)), dim3(kQcThreads), 0, ctx->stream, text, L.streams,
                            L.block_base, nstreams, per_block, L.c.recs, d_rows, d_status, L.bad);
     hipLaunchKernelGGL(vk_qc_finish_kernel, dim3(nstreams), dim3(kClThreads), 0, ctx->stream, d_rows, d_status, L.bad);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- distances and nearest neighbours of images (vk_dist.h) ------
+
+namespace {
+
+// the pieces of a vk_dist_device workspace
+struct DistLayout {
+    int8_t *q, *r;            // the prepared rows
+    uint64_t *qnorm, *rnorm;
+    uint64_t* strip;
+    uint64_t strip_rows;
+    size_t total;
+};
+
+DistLayout dist_layout(void* d_ws, uint64_t nq, uint64_t nr, uint64_t npix) {
+    DistLayout L{};
+    const uint64_t padded = dist_padded(npix);
+    L.strip_rows = dist_strip_rows(nq, nr, VK_DIST_STRIP);
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.q, nq * padded);
+    take(L.r, nr * padded);
+    take(L.qnorm, nq);
+    take(L.rnorm, nr);
+    take(L.strip, L.strip_rows * nr);
+    L.total = take.at;
+    return L;
+}
+
+bool dist_args_ok(uint64_t nq, uint64_t nr, uint64_t npix, uint32_t nn) {
+    return nq >= 1 && nq < (1ull << 31) && nr >= 1 && nr <= kDistMaxRefs && npix >= 1 && npix <= kDistMaxPix && nn >= 1 &&
+           nn <= kDistMaxN && dist_key_fits(npix, dist_idx_bits(nr));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_dist_workspace_size(uint64_t nq, uint64_t nr, uint64_t npix, uint32_t n_neighbours, int want_matrix, uint64_t* bytes) {
+    (void)want_matrix;   // (the matrix goes to the caller's buffer)
+    if (!bytes || !dist_args_ok(nq, nr, npix, n_neighbours)) return VK_EINVAL;
+    *bytes = dist_layout(nullptr, nq, nr, npix).total;
+    return VK_OK;
+}
+
+int vk_dist_device(vk_ctx* ctx, const void* d_q, uint64_t nq, const void* d_r, uint64_t nr, uint64_t npix, const uint32_t* d_qgroup,
+                   const uint32_t* d_rgroup, uint32_t n_neighbours, uint32_t* d_idx, uint64_t* d_d2, uint64_t* d_matrix, void* d_ws,
+                   uint64_t ws_bytes) {
+    if (!ctx || !d_q || !d_r || !d_idx || !d_d2 || !d_ws || !dist_args_ok(nq, nr, npix, n_neighbours)) return VK_EINVAL;
+    if ((d_qgroup == nullptr) != (d_rgroup == nullptr)) return VK_EINVAL;
+    const DistLayout L = dist_layout(d_ws, nq, nr, npix);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    const uint64_t padded = dist_padded(npix);
+    const uint32_t bits = dist_idx_bits(nr);
+    const bool self = d_q == d_r && nq == nr;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(vk_dist_prep_kernel, dim3(static_cast<uint32_t>(nq)), dim3(kDistThreads), 0, ctx->stream,
+                       static_cast<const uint8_t*>(d_q), L.q, L.qnorm, npix, padded);
+    if (!self)
+        hipLaunchKernelGGL(vk_dist_prep_kernel, dim3(static_cast<uint32_t>(nr)), dim3(kDistThreads), 0, ctx->stream,
+                           static_cast<const uint8_t*>(d_r), L.r, L.rnorm, npix, padded);
+    const int8_t* refs = self ? L.q : L.r;
+    const uint64_t* rnorm = self ? L.qnorm : L.rnorm;
+    const uint64_t strip = dist_strip_rows(nq, nr, ctx->dist_strip && ctx->dist_strip < L.strip_rows ? ctx->dist_strip : L.strip_rows);
+    const uint32_t jtiles = static_cast<uint32_t>((nr + kDistTile - 1) / kDistTile);
+    for (uint64_t q0 = 0; q0 < nq; q0 += strip) {
+        const uint32_t rows = static_cast<uint32_t>(std::min(strip, nq - q0));
+        const uint64_t tiles = static_cast<uint64_t>((rows + kDistTile - 1) / kDistTile) * jtiles;
+        if (tiles >= (1ull << 31)) return VK_EINVAL;
+        hipLaunchKernelGGL(vk_dist_tile_kernel, dim3(static_cast<uint32_t>(tiles)), dim3(kDistThreads), 0, ctx->stream, L.q, refs, L.qnorm,
+                           rnorm, q0, rows, static_cast<uint32_t>(nr), jtiles, padded, L.strip, d_matrix);
+        hipLaunchKernelGGL(vk_dist_select_kernel, dim3(rows), dim3(kDistSelThreads), 0, ctx->stream, L.strip, q0,
+                           static_cast<uint32_t>(nr), d_qgroup, d_rgroup, n_neighbours, bits, d_idx, d_d2);
+    }
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

@@ -1142,6 +1142,51 @@ class ImageEngine:
         # (the copies below wait for the kernels: the workspace is free after them)
         return rows.cpu().numpy().view(np.uint64), status.cpu().numpy().astype(np.uint32)
 
+    def neighbours(self, q, r, n=10, qgroup=None, rgroup=None, matrix=False):
+        """The n nearest references of every query image by exact squared Euclidean distance (vk_dist_device; the rule:
+        INTEGRATION.md, "`compare`: the rule").  q, r: uint8 device tensors [nq, side, side] or [nq, P] of equal P; `q is
+        r` compares a set with itself.  qgroup, rgroup: group ids (uint32 values, 0xFFFFFFFF = no group), both or
+        neither: a reference of a query's own group is no neighbour of it.  Returns (idx uint32[nq, n], d2 uint64[nq, n])
+        as NumPy arrays, slots without a reference 0xFFFFFFFF and 2^64 - 1; with matrix=True also every distance as an
+        int64 device tensor [nq, nr] (the values are below 2^63).  Synchronises."""
+        torch = _torch()
+
+        def rows(t):
+            if t.dtype != torch.uint8 or t.device != self.device or t.dim() not in (2, 3):
+                raise ValueError("images are uint8 tensors [n, side, side] or [n, P] on the engine's device")
+            return t.reshape(t.shape[0], -1).contiguous()
+        q2 = rows(q)
+        r2 = q2 if r is q else rows(r)
+        nq, npix = (int(v) for v in q2.shape)
+        nr = int(r2.shape[0])
+        if int(r2.shape[1]) != npix:
+            raise ValueError("queries and references differ in size")
+        if (qgroup is None) != (rgroup is None):
+            raise ValueError("group ids for both sides or for neither")
+        n = int(n)
+        groups = [None, None]
+        if qgroup is not None:
+            for i, (g, count) in enumerate(((qgroup, nq), (rgroup, nr))):
+                g = np.array(g, dtype=np.uint32)   # (a copy: the caller's may be read-only)
+                if g.shape != (count,):
+                    raise ValueError("one group id per image")
+                groups[i] = torch.from_numpy(g.view(np.int32)).to(self.device)
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_dist_workspace_size(nq, nr, npix, n if 0 <= n < 2 ** 32 else 0, int(matrix), C.byref(ws_bytes)),
+                    "vk_dist_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        idx = torch.empty((nq, n), dtype=torch.int32, device=self.device)
+        d2 = torch.empty((nq, n), dtype=torch.int64, device=self.device)
+        mat = torch.empty((nq, nr), dtype=torch.int64, device=self.device) if matrix else None
+        st = self.L.vk_dist_device(self.ctx, self._ptr(q2), nq, self._ptr(r2), nr, npix,
+                                   self._ptr(groups[0]) if qgroup is not None else None,
+                                   self._ptr(groups[1]) if qgroup is not None else None, n, self._ptr(idx), self._ptr(d2),
+                                   self._ptr(mat) if matrix else None, self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_dist_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        out = (idx.cpu().numpy().view(np.uint32), d2.cpu().numpy().view(np.uint64))
+        return out + (mat,) if matrix else out
+
     def deflate_bound(self, lengths):
         """Bytes that the files of texts of these lengths take at most (vk_deflate_bound)."""
         lens = np.ascontiguousarray(lengths, dtype=np.uint64)
