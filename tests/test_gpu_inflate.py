@@ -14,12 +14,18 @@ from varkoder_amd import _capi, synth
 pytestmark = pytest.mark.gpu
 
 
-def gz(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, wbits=31):
-    co = zlib.compressobj(level, zlib.DEFLATED, wbits, 9, strategy)
+def gz(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, wbits=31, mem=9):
+    co = zlib.compressobj(level, zlib.DEFLATED, wbits, mem, strategy)
     return co.compress(data) + co.flush()
 
 
 def run(eng, files, caps=None):
+    lens, status, res, ooffs = run_raw(eng, files, caps)
+    return [bytes(res[o:o + int(n)]) for o, n in zip(ooffs, lens)], status, res, ooffs
+
+
+def run_raw(eng, files, caps=None):
+    """(text lengths as reported, status words, the whole output buffer, the slots' offsets in it)"""
     import torch
     offs, pos = [], 0
     for f in files:
@@ -38,8 +44,7 @@ def run(eng, files, caps=None):
     out = torch.full((pos + 16,), 0xEE, dtype=torch.uint8, device="cuda")
     lens, status = eng.inflate(dev, np.array(offs, dtype=np.uint64), np.array([len(f) for f in files], dtype=np.uint64),
                                out, np.array(ooffs, dtype=np.uint64), np.array(caps, dtype=np.uint64))
-    res = out.cpu().numpy()
-    return [bytes(res[o:o + int(n)]) for o, n in zip(ooffs, lens)], status, res, ooffs
+    return lens, status, out.cpu().numpy(), ooffs
 
 
 def test_inflate_matches_zlib_on_every_block_type(engines):
@@ -311,6 +316,73 @@ def test_inflate_chunk_sizes_and_false_block_starts(monkeypatch):
             eng.close()
         assert status.tolist() == [0, 0], cb
         assert got[0] == texts[0] and got[1] == texts[1], cb
+
+
+def test_inflate_switches_on_small_files(monkeypatch):
+    """The switches of the inflate's host path on files just large enough to be cut into chunks: 64 KiB chunks (eight and
+    more per file) with the block starts found by the chunk decoder's own wavefronts, the same with the finder as a launch
+    of its own (VKIMG_GZ_SPLIT_FIND), and every file through the one-wavefront kernel (VKIMG_GZ_NO_CHUNKS).  The set: a
+    sound file, two members of which the first carries a wrong check word, a slot a third of the text, stored blocks only
+    (no block start to find: the chunked path hands the file over), and a small file.
+
+
+    The large files are written the way gzip, zlib.compress and Python's gzip module write them: zlib's default memory
+    level, 8, whose DEFLATE blocks hold 16 383 symbols (this module's other files: level 9, 32 767).  That matters to the
+    slot a third of the text.  It learns the size it needs only where the chunked path decodes the whole file, and a
+    chunk's room follows the slot: twice the ratio slot / file, the ratio at least 4, plus 65 536 elements, so 589 824
+    elements per 64 KiB chunk here.  A wavefront decodes from its chunk's first block start to a later chunk's first: a
+    chunk's length and at most one block more, at this text's ratio of 6.07 about (64 + 28) KiB x 6.07 = 570 000 bytes
+    of text with 28 KiB blocks, 730 000 with the 57 KiB blocks of memory level 9.  (zlib's inflate with Z_BLOCK gives
+    the blocks' ends: the longest stretch between chunk starts is 518 651 bytes at level 8 and 691 816 at level 9.)  So
+    at level 9 a chunk outgrows its room, the file goes to the one-wavefront kernel and the slot learns only the bytes
+    that fitted (1 066 662 of 3 200 000 measured, the same before the host path was reworked): that input is outside
+    what 64 KiB chunks with this room serve, by the rule of the room, which is not this test's subject."""
+    from varkoder_amd.engine import ImageEngine
+    needed = []
+    reads = 9000
+    while True:                                                   # (about 10 000 reads)
+        a = synth.sample_fastq(71, reads, 150).tobytes()
+        fa = gz(a, 6, mem=8)
+        if len(fa) >= 1 << 19:
+            break
+        reads += 500
+    assert 1 << 19 <= len(fa) < 5 << 17
+    word = struct.unpack("<I", fa[-8:-4])[0]
+    fb = fa[:-8] + struct.pack("<I", (word + 1) & 0xFFFFFFFF) + fa[-4:] + fa
+    stored = synth.sample_fastq(72, 2000, 150).tobytes()[:600_000]
+    fd = gz(stored, 0)
+    assert len(fd) >= 1 << 19
+    small = synth.sample_fastq(73, 3000, 150).tobytes()
+    fe = gz(small, 6)
+    assert len(fe) < 1 << 19
+    files = [fa, fb, fa, fd, fe]
+    texts = [a, a + a, None, stored, small]
+    caps = [len(a), 2 * len(a), len(a) // 3, len(stored), len(small)]
+    # zlib's texts ((b) with its check word put right: zlib does not deliver a text whose check fails)
+    assert [zlib.decompress(f, 47) for f in (fa, fd, fe)] == [a, stored, small] and gzip.decompress(fa + fa) == a + a
+    settings = [({"VKIMG_GZ_CHUNK_BYTES": "65536"}, True), ({"VKIMG_GZ_CHUNK_BYTES": "65536", "VKIMG_GZ_SPLIT_FIND": "1"}, True),
+                ({"VKIMG_GZ_NO_CHUNKS": "1"}, False)]
+    for env, chunked in settings:
+        for name in ("VKIMG_GZ_CHUNK_BYTES", "VKIMG_GZ_SPLIT_FIND", "VKIMG_GZ_NO_CHUNKS"):
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        eng = ImageEngine(k=7, mapping="cgr", device=0)
+        try:
+            lens, status, res, ooffs = run_raw(eng, files, caps=caps)
+        finally:
+            eng.close()
+        for i in (0, 1, 3, 4):
+            assert int(lens[i]) == len(texts[i]) and bytes(res[ooffs[i]:ooffs[i] + len(texts[i])]) == texts[i], (env, i)
+        assert status[0] == 0 and status[1] == _capi.VK_GZ_BAD_CRC and status[3] == 0 and status[4] == 0, (env, status)
+        assert status[2] & _capi.VK_GZ_OVERFLOW, (env, status)
+        for o, c, nxt in zip(ooffs, caps, ooffs[1:] + [res.size - 16]):
+            assert (res[o + c:nxt] == 0xEE).all(), env
+        assert (res[-16:] == 0xEE).all(), env
+        if chunked:
+            needed.append((env, int(lens[2])))
+    print("length reported for the slot a third of the text:", needed, "text:", len(a))
+    assert [n for _, n in needed] == [len(a)] * 2                 # the size a second call needs
 
 
 def bgzf(data, block=30000, level=6):

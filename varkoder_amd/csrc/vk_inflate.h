@@ -24,6 +24,8 @@
 
 #include <cstdint>
 
+#include "vk_gzplan.h"   // the structs host and device share, the status bits, the host's plans
+
 namespace {
 
 constexpr int kLitRoot = 10, kDistRoot = 9;
@@ -410,30 +412,8 @@ __device__ bool gz_dynamic_header(GzLds& L, const uint8_t* __restrict__ in, uint
     return L.lens[256] != 0;  // a block without an end-of-block code is not valid
 }
 
-// status bits of one gzip file
-constexpr uint32_t kGzBadHeader = 1u, kGzBadData = 2u, kGzTruncated = 4u, kGzOverflow = 8u, kGzBadSize = 16u, kGzBadCrc = 32u;
-
-struct GzJob {
-    uint64_t in_off, in_len;     // compressed bytes in the input buffer
-    uint64_t out_off, out_cap;   // where the text goes, and how much room there is
-};
-
-// A CHUNK of a large gzip file (the chunked path, below): one wavefront decodes the DEFLATE blocks
-// from the block start `start_bit` (found by vk_gzfind_kernel; chunk 0: the gzip header at bit 0)
-// up to the block start of a later chunk.
-struct GzChunk {
-    uint64_t in_off, in_len;     // the whole FILE's compressed bytes
-    uint64_t out_off, out_cap;   // this chunk's u16 elements in the symbolic buffer (offset and room, in elements)
-    uint32_t file_chunk0;        // index of the file's chunk 0 in the chunk arrays
-    uint32_t nchunks;            // chunks of the file
-    uint32_t chunk_bytes;        // compressed bytes per chunk (chosen per call, vk_inflate_device)
-    uint32_t pad_;
-};
-constexpr uint64_t kGzNone = ~0ull;       // start_bit of a chunk in which no block start was found
-constexpr uint64_t kGzPending = 0xFEFEFEFEFEFEFEFEull;   // ... of a chunk whose wavefront has not looked yet (the host's memset; vk_gzchunk_kernel)
-constexpr uint32_t kGzSpinMax = 1u << 15;  // looks at a pending start before it is given up as "none" (~2 us apart: 60 ms -- the wavefront next door needs 13 at most)
-constexpr uint32_t kGzEnd = 0xFFFFFFFFu;  // next[] of the chunk that decoded the file's last member
-constexpr uint32_t kGzMemRec = 62;         // member trailers a wavefront records (end of the member's text in ITS output, CRC-32 word); a file with more in one chunk goes unchecked
+// (the status bits of a gzip file, GzJob, GzChunk and the marks kGzNone, kGzPending, kGzEnd, kGzMemRec: vk_gzplan.h)
+constexpr uint32_t kGzSpinMax = 1u << 15;  // looks at a pending start (kGzPending) before it is given up as "none" (~2 us apart: 60 ms -- the wavefront next door needs 13 at most)
 
 #ifdef VK_GZ_STAMPS
 // Diagnostic build only (tools/gz_stamps.py): per-chunk clocks of the chunk decoder, in a debug buffer that
@@ -1157,8 +1137,7 @@ __global__ __launch_bounds__(64) void vk_inflate_kernel(const uint8_t* __restric
 // and turns each chunk's last 32 KiB into the next chunk's window, (4) vk_gzfinal_kernel replaces the
 // markers and writes the text.  Anything unexpected (no start found, a chunk that overflows its
 // room, sizes that do not add up) sends the file through vk_inflate_kernel instead.
-constexpr uint32_t kGzChunkMin = 1u << 17;                            // compressed bytes per chunk: this, or twice this
-constexpr uint32_t kGzBigFile = 1u << 19;                             // files at least this large are cut into chunks
+// (kGzChunkMin, kGzBigFile and the fit of the chunk size: vk_gzplan.h)
 #ifndef VK_GZ_CHUNK_OCC
 #define VK_GZ_CHUNK_OCC 6     // wavefronts of vk_gzchunk_kernel per SIMD the register budget is set for
 #endif
@@ -1363,11 +1342,7 @@ __global__ __launch_bounds__(64, VK_GZ_CHUNK_OCC) void vk_gzchunk_kernel(const u
 }
 
 // One workgroup per file: chunk after chunk of its chain, the 32 KiB window a chunk sees (win_in[k]) and the
-// one it leaves behind.  items: {chunk's element offset, its length}; first/count: the file's slice of them.
-struct GzItem {
-    uint64_t sym_off, len, text_off;
-};
-
+// one it leaves behind.  items: {chunk's element offset, its length}; first/count: the file's slice of them (GzItem: vk_gzplan.h).
 __global__ __launch_bounds__(1024) void vk_gzwin_kernel(const uint16_t* __restrict__ sym, const GzItem* __restrict__ items,
                                                          const uint32_t* __restrict__ first, const uint32_t* __restrict__ count,
                                                          uint8_t* __restrict__ win_in) {
@@ -1457,12 +1432,7 @@ __global__ __launch_bounds__(256) void vk_gzfinal_kernel(const uint16_t* __restr
 // (operator gz_ops[33]).  The 64 lanes are merged by a tree of "shift by 64 x 2^l bytes" operators (32 x 32
 // bit matrices, gz_ops[n] = the operator for 2^n zero bytes, built on the host as zlib's crc32_combine
 // does), one wave per file folds the segment values, and the host adds the preset's contribution (shift by
-// the text length) and the inversion.
-struct GzCrcJob {
-    uint64_t text_off, text_len;
-    uint32_t seg0, nseg;  // this file's slice of the segment array
-};
-
+// the text length) and the inversion (GzCrcJob, GzCrcOps: vk_gzplan.h).
 __device__ __forceinline__ uint32_t gz_apply(const uint32_t* op, uint32_t v) {  // op x v over GF(2)
     uint32_t r = 0;
 #pragma unroll

@@ -114,7 +114,7 @@ struct vk_ctx {
     size_t spill_budget = 96ull << 30;  // bytes of HBM the spill path may use at a time (VKIMG_SPILL_BUDGET=n: tests force several sub-batches)
     // host-call staging
     uint64_t* d_sub = nullptr;    // subsampling launches: seeds | thresholds
-    uint8_t* d_gzjobs = nullptr;  // vk_inflate_device: jobs | text lengths | status words
+    uint8_t* d_gzjobs = nullptr;  // vk_inflate_device: jobs | check words | what the kernel reports (gz_direct_stage)
     size_t gzjobs_cap = 0;
     uint8_t* d_gzmeta = nullptr;  // ... chunked path: chunk table and results, then the chain items
     size_t gzmeta_cap = 0;
@@ -1143,41 +1143,19 @@ int vk_image_host(vk_ctx* ctx, const uint32_t* hist, int k, uint8_t* img) {
 
 }  // extern "C"
 
+// ---- vk_inflate_device: the plans and decisions are vk_gzplan.h's, the workspaces and launches are here ----
 namespace {
 
-// Operators of the CRC-32 (reflected polynomial 0xEDB88320) over GF(2), as zlib's crc32_combine builds them:
-// op[k] advances a remainder over 2^k zero BYTES; 32 columns each.
-struct GzCrcOps {
-    uint32_t op[34][32];  // [33]: 4032 bytes, the step between a lane's pieces in vk_crc32_seg_kernel
-    GzCrcOps() {
-        uint32_t bit1[32], bit2[32], bit4[32];
-        bit1[0] = 0xEDB88320u;  // one zero bit
-        for (int n = 1; n < 32; ++n) bit1[n] = 1u << (n - 1);
-        square(bit2, bit1);
-        square(bit4, bit2);
-        square(op[0], bit4);  // eight zero bits
-        for (int k = 1; k <= 32; ++k) square(op[k], op[k - 1]);
-        for (int n = 0; n < 32; ++n) op[33][n] = shift(1u << n, 4032);
-    }
-    static uint32_t times(const uint32_t* m, uint32_t v) {
-        uint32_t r = 0;
-        for (int i = 0; v; v >>= 1, ++i)
-            if (v & 1u) r ^= m[i];
-        return r;
-    }
-    static void square(uint32_t* sq, const uint32_t* m) {
-        for (int n = 0; n < 32; ++n) sq[n] = times(m, m[n]);
-    }
-    uint32_t shift(uint32_t v, uint64_t nbytes) const {
-        for (int k = 0; nbytes; nbytes >>= 1, ++k)
-            if (nbytes & 1u) v = times(op[k], v);
-        return v;
-    }
+static_assert(kGzOverflow == VK_GZ_OVERFLOW && kGzBadCrc == VK_GZ_BAD_CRC, "vk_gzplan.h sets the status bits of vkimg.h");
+
+// d_gzcrc
+struct GzCrcLayout {
+    GzCrcJob* jobs;
+    uint32_t* seg_job;   // per segment: its job
+    uint32_t* ops;       // GzCrcOps::op
+    uint32_t* seg;       // per segment: its remainder
+    uint32_t* raw;       // per job: the zero-preset remainder of its text
 };
-const GzCrcOps& gz_crc_ops() {
-    static const GzCrcOps ops;
-    return ops;
-}
 
 // CRC-32 of texts resident on the device (vk_inflate.h, "CRC-32 of the inflated text"): crc[i] for every job.
 int gz_text_crc(vk_ctx* ctx, const uint8_t* text, const std::vector<GzCrcJob>& jobs_in, std::vector<uint32_t>& crc) {
@@ -1192,27 +1170,193 @@ int gz_text_crc(vk_ctx* ctx, const uint8_t* text, const std::vector<GzCrcJob>& j
     crc.assign(nj, 0u);
     const GzCrcOps& ops = gz_crc_ops();
     if (ns != 0) {
-        const size_t o_jobs = 0, o_segjob = o_jobs + nj * sizeof(GzCrcJob), o_ops = o_segjob + ns * 4ull,
-                     o_seg = o_ops + sizeof(ops.op), o_raw = o_seg + ns * 4ull, total = o_raw + nj * 4ull;
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzcrc), &ctx->gzcrc_cap, total + 256);
+        GzCrcLayout L{};
+        int rc = ws_carve(ctx, &ctx->d_gzcrc, &ctx->gzcrc_cap, [&](WsTake& take) {
+            take(L.jobs, nj);
+            take(L.seg_job, ns);
+            take(L.ops, sizeof(ops.op) / sizeof(uint32_t));
+            take(L.seg, ns);
+            take(L.raw, nj);
+        });
         if (rc) return rc;
-        uint8_t* m = ctx->d_gzcrc;
-        VK_HIP(ctx, hipMemcpyAsync(m + o_jobs, jobs.data(), nj * sizeof(GzCrcJob), hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(m + o_segjob, seg_job.data(), ns * 4ull, hipMemcpyHostToDevice, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(m + o_ops, ops.op, sizeof(ops.op), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(vk_crc32_seg_kernel, dim3((ns + 3) / 4), dim3(256), 0, ctx->stream, text,
-                           reinterpret_cast<const GzCrcJob*>(m + o_jobs), nj, reinterpret_cast<const uint32_t*>(m + o_segjob), ns,
-                           reinterpret_cast<const uint32_t*>(m + o_ops), reinterpret_cast<uint32_t*>(m + o_seg));
+        VK_HIP(ctx, hipMemcpyAsync(L.jobs, jobs.data(), nj * sizeof(GzCrcJob), hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.seg_job, seg_job.data(), ns * 4ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.ops, ops.op, sizeof(ops.op), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(vk_crc32_seg_kernel, dim3((ns + 3) / 4), dim3(256), 0, ctx->stream, text, L.jobs, nj, L.seg_job, ns, L.ops, L.seg);
         VK_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(vk_crc32_fold_kernel, dim3(nj), dim3(64), 0, ctx->stream, reinterpret_cast<const GzCrcJob*>(m + o_jobs),
-                           nj, reinterpret_cast<const uint32_t*>(m + o_ops), reinterpret_cast<const uint32_t*>(m + o_seg),
-                           reinterpret_cast<uint32_t*>(m + o_raw));
+        hipLaunchKernelGGL(vk_crc32_fold_kernel, dim3(nj), dim3(64), 0, ctx->stream, L.jobs, nj, L.ops, L.seg, L.raw);
         VK_HIP(ctx, hipGetLastError());
-        VK_HIP(ctx, hipMemcpyAsync(crc.data(), m + o_raw, nj * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(crc.data(), L.raw, nj * 4ull, hipMemcpyDeviceToHost, ctx->stream));
+        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (also keeps jobs and seg_job alive until the copies have read them)
     }
     // zero-preset remainder -> CRC-32: the preset 0xFFFFFFFF shifted over the text, and the final inversion
     for (uint32_t j = 0; j < nj; ++j) crc[j] ^= ops.shift(0xFFFFFFFFu, jobs[j].text_len) ^ 0xFFFFFFFFu;
+    return VK_OK;
+}
+
+// The arguments of a vk_inflate_device call.
+struct GzCall {
+    const uint8_t* gz;
+    uint8_t* out;
+    const uint64_t *gz_offsets, *gz_lengths, *out_offsets, *out_caps;
+    uint64_t* out_lengths;
+    uint32_t* status;
+};
+
+// What a stage's kernel reports is ONE run of pieces, so that one copy brings it back: the same statement of pieces lays out
+// the run in the device's workspace and, over a host buffer, its mirror.
+void gz_chunk_results(WsTake& take, GzChunkResults& r, size_t nc) {
+    take(r.len, nc);
+    take(r.status, nc);
+    take(r.next, nc);
+    take(r.isize, nc);
+    take(r.nmem, nc);
+    take(r.rec, nc * kGzMemRec);
+}
+
+// The chunked path, steps (1) and (2): the chunks of `plan` decoded into d_gzsym, what they report on the host (h: pointers
+// into `mirror`).  d_gzmeta holds the chunk table and the results here; no pointer into it leaves this function, because
+// gz_chunks_write carves the buffer anew.
+int gz_chunks_decode(vk_ctx* ctx, const uint8_t* gz, const GzChunkPlan& plan, std::vector<uint8_t>& mirror, GzChunkResults& h) {
+    const uint32_t nc = static_cast<uint32_t>(plan.chunks.size());
+    GzChunk* d_chunks = nullptr;
+    uint64_t* d_starts = nullptr;
+    uint32_t* d_crc = nullptr;   // the last member's check word per chunk: written by the kernel, not read by the host
+    GzChunkResults d{};
+    size_t res_at = 0, res_bytes = 0;
+    int rc = ws_carve(ctx, &ctx->d_gzmeta, &ctx->gzmeta_cap, [&](WsTake& take) {
+        take(d_chunks, nc);
+        take(d_starts, nc);
+        take(d_crc, nc);
+        res_at = take.at;
+        gz_chunk_results(take, d, nc);
+        res_bytes = take.at - res_at;
+    });
+    if (rc) return rc;
+    uint16_t* d_sym = nullptr;
+    rc = ws_carve(ctx, &ctx->d_gzsym, &ctx->gzsym_cap, [&](WsTake& take) { take(d_sym, plan.sym_total + 128); });   // (256 bytes to spare)
+    if (rc) return rc;
+    mirror.resize(res_bytes);
+    WsTake host{mirror.data(), 0};
+    gz_chunk_results(host, h, nc);
+    VK_HIP(ctx, hipMemcpyAsync(d_chunks, plan.chunks.data(), nc * sizeof(GzChunk), hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->gz_split_find) {
+        hipLaunchKernelGGL(vk_gzfind_kernel, dim3(nc), dim3(64), 0, ctx->stream, gz, d_chunks, nc, d_starts);
+        VK_HIP(ctx, hipGetLastError());
+    } else {
+        VK_HIP(ctx, hipMemsetAsync(d_starts, 0xFE, nc * 8ull, ctx->stream));   // kGzPending: the chunks' wavefronts find their own starts
+    }
+    hipLaunchKernelGGL(vk_gzchunk_kernel, dim3(nc), dim3(64), ctx->gz_lds_pad, ctx->stream, gz, d_sym, d_chunks, nc, d_starts, d.len,
+                       d.status, d.next, d.isize, d.nmem, d_crc, reinterpret_cast<uint2*>(d.rec), ctx->gz_split_find ? 0u : 1u);
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(mirror.data(), ctx->d_gzmeta + res_at, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the chunk table is read by the copy: the plan is the caller's)
+    return VK_OK;
+}
+
+// The chunked path, steps (3) and (4): the accepted files' windows handed on and their text written.  The chunk metadata
+// has been read back and the stream synchronised (gz_chunks_decode): d_gzmeta now carries the items.
+int gz_chunks_write(vk_ctx* ctx, uint8_t* out, const GzChains& ch) {
+    const uint32_t ni = static_cast<uint32_t>(ch.items.size()), nf = static_cast<uint32_t>(ch.okfile.size());
+    GzItem* d_items = nullptr;
+    uint32_t *d_first = nullptr, *d_count = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_gzmeta, &ctx->gzmeta_cap, [&](WsTake& take) {
+        take(d_items, ni);
+        take(d_first, nf);
+        take(d_count, nf);
+    });
+    if (rc) return rc;
+    uint8_t* d_win = nullptr;
+    rc = ws_carve(ctx, &ctx->d_gzwin, &ctx->gzwin_cap, [&](WsTake& take) { take(d_win, static_cast<size_t>(ni) * 32768 + 256); });
+    if (rc) return rc;
+    const uint16_t* d_sym = reinterpret_cast<const uint16_t*>(ctx->d_gzsym);
+    VK_HIP(ctx, hipMemcpyAsync(d_items, ch.items.data(), ni * sizeof(GzItem), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_first, ch.first.data(), nf * 4ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_count, ch.count.data(), nf * 4ull, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(vk_gzwin_kernel, dim3(nf), dim3(1024), 0, ctx->stream, d_sym, d_items, d_first, d_count, d_win);
+    VK_HIP(ctx, hipGetLastError());
+    for (uint32_t i0 = 0; i0 < ni; i0 += 65535u) {  // (gridDim.y holds 65535 at most: 8 GiB of 128 KiB chunks)
+        const uint32_t n = ni - i0 < 65535u ? ni - i0 : 65535u;
+        hipLaunchKernelGGL(vk_gzfinal_kernel, dim3(32, n), dim3(256), 0, ctx->stream, d_sym, d_items + i0, n,
+                           d_win + static_cast<size_t>(i0) * 32768, out);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (items / first / count are read by the kernels)
+    return VK_OK;
+}
+
+// Large files: many wavefronts per file (vk_inflate.h, "the chunked path").  A file whose chain of chunks is sound gets its
+// text, or learns the room it needs; the others join `direct`.
+int gz_chunked_stage(vk_ctx* ctx, const GzCall& f, const std::vector<uint32_t>& big, std::vector<uint32_t>& direct, GzChecks& checks) {
+    const uint32_t chunk_bytes = gz_fit_chunk_bytes(f.gz_lengths, big, static_cast<uint64_t>(ctx->num_cus) * kGzChunkWaves,
+                                                    ctx->gz_chunk_bytes, ctx->gz_fill_pct);
+    const GzChunkPlan plan = gz_chunk_table(chunk_bytes, f.gz_offsets, f.gz_lengths, f.out_caps, big);
+    std::vector<uint8_t> mirror;
+    GzChunkResults res{};
+    int rc = gz_chunks_decode(ctx, f.gz, plan, mirror, res);
+    if (rc) return rc;
+    const GzChains ch = gz_walk_chains(plan, res, big, f.out_offsets, f.out_caps, checks);
+    for (size_t b = 0; b < big.size(); ++b) {
+        const GzVerdict& v = ch.verdict[b];
+        if (v.kind == kGzGoDirect) {
+            direct.push_back(big[b]);
+        } else {
+            f.status[big[b]] = v.status;
+            f.out_lengths[big[b]] = v.total;
+        }
+    }
+    return ch.okfile.empty() ? VK_OK : gz_chunks_write(ctx, f.out, ch);
+}
+
+// what vk_inflate_kernel reports per file: one run, as above
+struct GzDirectResults {
+    unsigned long long* len;
+    uint32_t *status, *nmem;
+    GzTrailer* rec;
+};
+void gz_direct_results(WsTake& take, GzDirectResults& r, size_t nd) {
+    take(r.len, nd);
+    take(r.status, nd);
+    take(r.nmem, nd);
+    take(r.rec, nd * kGzMemRec);
+}
+
+// Small files, and large ones the chunked path gave up on: one wavefront per file.
+int gz_direct_stage(vk_ctx* ctx, const GzCall& f, const std::vector<uint32_t>& direct, GzChecks& checks) {
+    const uint32_t nd = static_cast<uint32_t>(direct.size());
+    GzJob* d_jobs = nullptr;
+    uint32_t* d_crc = nullptr;   // (written by the kernel, not read by the host)
+    GzDirectResults d{}, h{};
+    size_t res_at = 0, res_bytes = 0;
+    int rc = ws_carve(ctx, &ctx->d_gzjobs, &ctx->gzjobs_cap, [&](WsTake& take) {
+        take(d_jobs, nd);
+        take(d_crc, nd);
+        res_at = take.at;
+        gz_direct_results(take, d, nd);
+        res_bytes = take.at - res_at;
+    });
+    if (rc) return rc;
+    std::vector<uint8_t> mirror(res_bytes);
+    WsTake host{mirror.data(), 0};
+    gz_direct_results(host, h, nd);
+    std::vector<GzJob> jobs(nd);
+    for (uint32_t j = 0; j < nd; ++j) {
+        const uint32_t i = direct[j];
+        jobs[j] = GzJob{f.gz_offsets[i], f.gz_lengths[i], f.out_offsets[i], f.out_caps[i]};
+    }
+    VK_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), nd * sizeof(GzJob), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(vk_inflate_kernel, dim3(nd), dim3(64), 0, ctx->stream, f.gz, f.out, d_jobs, nd, d.len, d.status, d.nmem, d_crc,
+                       reinterpret_cast<uint2*>(d.rec));
+    VK_HIP(ctx, hipGetLastError());
+    VK_HIP(ctx, hipMemcpyAsync(mirror.data(), ctx->d_gzjobs + res_at, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also keeps `jobs` alive until the copy has read it)
+    std::vector<GzMember> members;
+    for (uint32_t j = 0; j < nd; ++j) {
+        const uint32_t i = direct[j];
+        f.out_lengths[i] = h.len[j];
+        f.status[i] = h.status[j] | gz_direct_checks(checks, i, h.status[j], h.nmem[j], h.rec + static_cast<size_t>(j) * kGzMemRec,
+                                                     f.out_offsets[i], h.len[j], members);
+    }
     return VK_OK;
 }
 
@@ -1227,264 +1371,27 @@ int vk_inflate_device(vk_ctx* ctx, const void* d_gz, const uint64_t* gz_offsets,
     if (nfiles == 0) return VK_OK;
     if (!d_gz || !d_out) return VK_EINVAL;
     VK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint8_t* gz = static_cast<const uint8_t*>(d_gz);
-    uint8_t* out = static_cast<uint8_t*>(d_out);
-    std::vector<uint32_t> direct;  // files that go through the one-wavefront-per-file kernel
-    std::vector<GzCrcJob> crc_jobs;        // one per gzip member with text: its CRC-32 is checked against the member's trailer
-    std::vector<uint32_t> crc_file, crc_want;
-    std::vector<std::pair<uint64_t, uint32_t>> members;  // of the file in hand: (end of the member's text in the file's text, CRC-32 word)
-    // every member of file i (text at text_off, text_len bytes; `members` in order) gets a check of its own;
-    // an empty member's check word must be that of no bytes
-    auto add_member_checks = [&](uint32_t i, uint64_t text_off, uint64_t text_len) {
-        uint64_t from = 0;
-        for (const auto& mb : members) {
-            if (mb.first < from || mb.first > text_len) return;  // (cannot happen for a file whose sizes added up)
-            if (mb.first == from) {
-                if (mb.second != 0u) status[i] |= VK_GZ_BAD_CRC;
-            } else {
-                crc_jobs.push_back(GzCrcJob{text_off + from, mb.first - from, 0, 0});
-                crc_file.push_back(i);
-                crc_want.push_back(mb.second);
-            }
-            from = mb.first;
-        }
-    };
-
-    // ---- large files: many wavefronts per file (vk_inflate.h, "the chunked path") ------------------
-    std::vector<uint32_t> big;
+    const GzCall f{static_cast<const uint8_t*>(d_gz), static_cast<uint8_t*>(d_out), gz_offsets, gz_lengths, out_offsets, out_caps,
+                   out_lengths, status};
+    std::vector<uint32_t> big, direct;  // files that are cut into chunks, files that go through the one-wavefront-per-file kernel
     for (uint32_t i = 0; i < nfiles; ++i) {
         out_lengths[i] = 0;
         status[i] = 0;
         if (!ctx->gz_no_chunks && gz_lengths[i] >= kGzBigFile) big.push_back(i);
         else direct.push_back(i);
     }
-    if (!big.empty()) {
-        std::vector<GzChunk> chunks;
-        std::vector<uint32_t> chunk0(big.size());
-        uint64_t sym_total = 0;
-        // Chunk size: 128 KiB gives a small call the most wavefronts (8 files of 24 MB: 48 ms against 72 ms with
-        // 256 KiB); once there are more chunks than the device holds wavefronts, throughput no longer
-        // depends on it (measured flat from 128 to 320 KiB) and 256 KiB halves the per-chunk work of the finder.
-        // Round 6: the chunk decoder's wavefronts are all resident from the start when there are no more of them than the device
-        // holds (slots), and a launch of 1.26 rounds is the worst there is (64 files of 24 MB, level 1: 96.9 ms at 192 KiB = 1.26
-        // rounds, 88.0 at 128 KiB = 1.9, 80.9 at 256 KiB = 0.95, 86.4 at 320 KiB = 0.76): the size is fitted so that the chunks
-        // fill 0.99 of the slots a whole number of times, the fewest times that keep a chunk under 352 KiB -- by the exact count
-        // (every file's length is known), so that a SIMD holds six wavefronts or, here and there, five: at 0.96 a quarter of the
-        // SIMDs held five and were done a sixth early (64 files of 33 MB: 113.5 ms at 0.96, 102.1 at 0.99 and at 1.00; 0.90: 115.9).
-        uint32_t chunk_bytes = ctx->gz_chunk_bytes;
-        if (chunk_bytes == 0) {
-            uint64_t big_total = 0;
-            for (uint32_t i : big) big_total += gz_lengths[i];
-            const uint64_t slots = static_cast<uint64_t>(ctx->num_cus) * kGzChunkWaves;
-            chunk_bytes = kGzChunkMin;
-            if (big_total / kGzChunkMin > slots) {
-                for (uint64_t rounds = 1; rounds <= 64; ++rounds) {
-                    // (every file ends in a part of a chunk: half a chunk per file goes off the count)
-                    const double fill = ctx->gz_fill_pct ? 0.01 * ctx->gz_fill_pct : 0.99;
-                    const double want = fill * static_cast<double>(slots * rounds) - 0.5 * static_cast<double>(big.size());
-                    if (want < 1.0) continue;
-                    uint64_t cb = (static_cast<uint64_t>(static_cast<double>(big_total) / want) + 4095u) & ~4095ull;
-                    if (cb < kGzChunkMin) cb = kGzChunkMin;
-                    // (the count is known exactly: never one chunk more than the rounds hold)
-                    for (;;) {
-                        uint64_t count = 0;
-                        for (uint32_t i : big) count += (gz_lengths[i] + cb - 1) / cb;
-                        if (count <= static_cast<uint64_t>(fill * static_cast<double>(slots * rounds)) || cb > 352u * 1024u) break;
-                        cb += 4096;
-                    }
-                    if (cb <= 352u * 1024u) {
-                        chunk_bytes = cb < kGzChunkMin ? kGzChunkMin : static_cast<uint32_t>(cb);
-                        break;
-                    }
-                    chunk_bytes = 2 * kGzChunkMin;   // (never reached by a sane input: a thousand rounds)
-                }
-            }
-        }
-        if (chunk_bytes < 65536u) chunk_bytes = 65536u;
-        for (size_t b = 0; b < big.size(); ++b) {
-            const uint32_t i = big[b];
-            const uint32_t nch = static_cast<uint32_t>((gz_lengths[i] + chunk_bytes - 1) / chunk_bytes);
-            // room per chunk (u16 elements): twice what the file's overall ratio predicts for a chunk, at least 8x
-            double ratio = static_cast<double>(out_caps[i]) / static_cast<double>(gz_lengths[i]);
-            if (ratio < 4.0) ratio = 4.0;
-            uint64_t cap = static_cast<uint64_t>(2.0 * ratio * chunk_bytes) + 65536;
-            if (cap > (1ull << 25)) cap = 1ull << 25;
-            chunk0[b] = static_cast<uint32_t>(chunks.size());
-            for (uint32_t j = 0; j < nch; ++j) {
-                chunks.push_back(GzChunk{gz_offsets[i], gz_lengths[i], sym_total, cap, chunk0[b], nch, chunk_bytes, 0});
-                sym_total += cap;
-            }
-        }
-        const uint32_t nc = static_cast<uint32_t>(chunks.size());
-        // metadata: chunks | starts u64 | len u64 | status u32 | next u32 | isize u32
-        const size_t o_chunks = 0, o_starts = o_chunks + nc * sizeof(GzChunk), o_len = o_starts + nc * 8ull,
-                     o_st = o_len + nc * 8ull, o_next = o_st + nc * 4ull, o_is = o_next + nc * 4ull, o_nm = o_is + nc * 4ull,
-                     o_cr = o_nm + nc * 4ull, o_rec = (o_cr + nc * 4ull + 15) / 16 * 16,
-                     meta_b = o_rec + static_cast<size_t>(nc) * kGzMemRec * sizeof(uint2);
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzmeta), &ctx->gzmeta_cap, meta_b + 256);
-        if (rc) return rc;
-        rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzsym), &ctx->gzsym_cap, sym_total * 2 + 256);
-        if (rc) return rc;
-        uint8_t* m = ctx->d_gzmeta;
-        GzChunk* d_chunks = reinterpret_cast<GzChunk*>(m + o_chunks);
-        uint64_t* d_starts = reinterpret_cast<uint64_t*>(m + o_starts);
-        unsigned long long* d_len = reinterpret_cast<unsigned long long*>(m + o_len);
-        uint32_t* d_st = reinterpret_cast<uint32_t*>(m + o_st);
-        uint32_t* d_next = reinterpret_cast<uint32_t*>(m + o_next);
-        uint32_t* d_is = reinterpret_cast<uint32_t*>(m + o_is);
-        uint32_t* d_nm = reinterpret_cast<uint32_t*>(m + o_nm);
-        uint32_t* d_cr = reinterpret_cast<uint32_t*>(m + o_cr);
-        uint2* d_rec = reinterpret_cast<uint2*>(m + o_rec);
-        uint16_t* d_sym = reinterpret_cast<uint16_t*>(ctx->d_gzsym);
-        VK_HIP(ctx, hipMemcpyAsync(d_chunks, chunks.data(), nc * sizeof(GzChunk), hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->gz_split_find) {
-            hipLaunchKernelGGL(vk_gzfind_kernel, dim3(nc), dim3(64), 0, ctx->stream, gz, d_chunks, nc, d_starts);
-            VK_HIP(ctx, hipGetLastError());
-        } else {
-            VK_HIP(ctx, hipMemsetAsync(d_starts, 0xFE, nc * 8ull, ctx->stream));   // kGzPending: the chunks' wavefronts find their own starts
-        }
-        hipLaunchKernelGGL(vk_gzchunk_kernel, dim3(nc), dim3(64), ctx->gz_lds_pad, ctx->stream, gz, d_sym, d_chunks, nc, d_starts, d_len,
-                           d_st, d_next, d_is, d_nm, d_cr, d_rec, ctx->gz_split_find ? 0u : 1u);
-        VK_HIP(ctx, hipGetLastError());
-        std::vector<unsigned long long> h_len(nc);
-        std::vector<uint32_t> h_st(nc), h_next(nc), h_is(nc), h_nm(nc), h_cr(nc);
-        std::vector<uint2> h_rec(static_cast<size_t>(nc) * kGzMemRec);
-        VK_HIP(ctx, hipMemcpyAsync(h_rec.data(), d_rec, h_rec.size() * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_len.data(), d_len, nc * 8ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_st.data(), d_st, nc * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_next.data(), d_next, nc * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_is.data(), d_is, nc * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_nm.data(), d_nm, nc * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_cr.data(), d_cr, nc * 4ull, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        // follow every file's chain of chunks; a file with anything odd in it goes the direct way instead
-        std::vector<GzItem> items;
-        std::vector<uint32_t> first, count, okfile;
-        for (size_t b = 0; b < big.size(); ++b) {
-            const uint32_t i = big[b];
-            const size_t mark = items.size();
-            uint64_t total = 0;
-            uint32_t isum = 0, nmem = 0, lastcrc = 0;
-            bool ok = true;
-            uint32_t c = chunk0[b];
-            members.clear();
-            bool members_known = true;   // every trailer's (end of text, check word) on record?
-            for (;;) {
-                if (h_st[c] != 0) { ok = false; break; }
-                items.push_back(GzItem{chunks[c].out_off, h_len[c], out_offsets[i] + total});
-                if (h_nm[c] > kGzMemRec) members_known = false;
-                for (uint32_t r = 0; r < h_nm[c] && r < kGzMemRec; ++r) {
-                    const uint2 rec = h_rec[static_cast<size_t>(c) * kGzMemRec + r];
-                    members.push_back({total + rec.x, rec.y});
-                }
-                total += h_len[c];
-                isum += h_is[c];
-                if (h_nm[c]) {
-                    nmem += h_nm[c];
-                    lastcrc = h_cr[c];
-                }
-                const uint32_t nx = h_next[c];
-                if (nx == kGzEnd) break;
-                if (nx <= c || nx >= chunk0[b] + chunks[c].nchunks) { ok = false; break; }
-                c = nx;
-            }
-            if (ok && isum != static_cast<uint32_t>(total)) ok = false;  // the members' size words do not add up to the text
-            if (ok && total > out_caps[i]) {  // e.g. several members and a caller who knew only the last one's size
-                status[i] = VK_GZ_OVERFLOW;
-                out_lengths[i] = total;       // ... who now learns the size a second call needs
-                items.resize(mark);
-                continue;
-            }
-            if (!ok) {
-                items.resize(mark);
-                direct.push_back(i);
-                continue;
-            }
-            first.push_back(static_cast<uint32_t>(mark));
-            count.push_back(static_cast<uint32_t>(items.size() - mark));
-            okfile.push_back(i);
-            out_lengths[i] = total;
-            (void)lastcrc;
-            if (members_known && members.size() == nmem) add_member_checks(i, out_offsets[i], total);
-        }
-        if (!okfile.empty()) {
-            const uint32_t ni = static_cast<uint32_t>(items.size()), nf = static_cast<uint32_t>(okfile.size());
-            const size_t o_items = 0, o_first = o_items + ni * sizeof(GzItem), o_count = o_first + nf * 4ull,
-                         tail_b = o_count + nf * 4ull;
-            // the chunk metadata has been read back: its buffer now carries the items
-            rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzmeta), &ctx->gzmeta_cap, tail_b + 256);
-            if (rc) return rc;
-            rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzwin), &ctx->gzwin_cap, static_cast<size_t>(ni) * 32768 + 256);
-            if (rc) return rc;
-            m = ctx->d_gzmeta;
-            GzItem* d_items = reinterpret_cast<GzItem*>(m + o_items);
-            uint32_t* d_first = reinterpret_cast<uint32_t*>(m + o_first);
-            uint32_t* d_count = reinterpret_cast<uint32_t*>(m + o_count);
-            VK_HIP(ctx, hipMemcpyAsync(d_items, items.data(), ni * sizeof(GzItem), hipMemcpyHostToDevice, ctx->stream));
-            VK_HIP(ctx, hipMemcpyAsync(d_first, first.data(), nf * 4ull, hipMemcpyHostToDevice, ctx->stream));
-            VK_HIP(ctx, hipMemcpyAsync(d_count, count.data(), nf * 4ull, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(vk_gzwin_kernel, dim3(nf), dim3(1024), 0, ctx->stream, reinterpret_cast<uint16_t*>(ctx->d_gzsym),
-                               d_items, d_first, d_count, ctx->d_gzwin);
-            VK_HIP(ctx, hipGetLastError());
-            for (uint32_t i0 = 0; i0 < ni; i0 += 65535u) {  // (gridDim.y holds 65535 at most: 8 GiB of 128 KiB chunks)
-                const uint32_t n = ni - i0 < 65535u ? ni - i0 : 65535u;
-                hipLaunchKernelGGL(vk_gzfinal_kernel, dim3(32, n), dim3(256), 0, ctx->stream,
-                                   reinterpret_cast<uint16_t*>(ctx->d_gzsym), d_items + i0, n,
-                                   ctx->d_gzwin + static_cast<size_t>(i0) * 32768, out);
-                VK_HIP(ctx, hipGetLastError());
-            }
-            VK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (items / first / count are read by the kernels)
-        }
-    }
-
-    // ---- small files, and large ones the chunked path gave up on: one wavefront per file -----------
-    if (!direct.empty()) {
-        const uint32_t nd = static_cast<uint32_t>(direct.size());
-        const size_t jobs_b = static_cast<size_t>(nd) * sizeof(GzJob), len_b = static_cast<size_t>(nd) * 8,
-                     st_b = static_cast<size_t>(nd) * 4;
-        const size_t rec_o = (jobs_b + len_b + 3 * st_b + 15) / 16 * 16, rec_b = static_cast<size_t>(nd) * kGzMemRec * sizeof(uint2);
-        int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_gzjobs), &ctx->gzjobs_cap, rec_o + rec_b);
-        if (rc) return rc;
-        std::vector<GzJob> jobs(nd);
-        for (uint32_t j = 0; j < nd; ++j) {
-            const uint32_t i = direct[j];
-            jobs[j] = GzJob{gz_offsets[i], gz_lengths[i], out_offsets[i], out_caps[i]};
-        }
-        GzJob* d_jobs = reinterpret_cast<GzJob*>(ctx->d_gzjobs);
-        unsigned long long* d_len = reinterpret_cast<unsigned long long*>(ctx->d_gzjobs + jobs_b);
-        uint32_t* d_st = reinterpret_cast<uint32_t*>(ctx->d_gzjobs + jobs_b + len_b);
-        uint32_t* d_nm = d_st + nd;
-        uint32_t* d_cr = d_nm + nd;
-        VK_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), jobs_b, hipMemcpyHostToDevice, ctx->stream));
-        uint2* d_rec = reinterpret_cast<uint2*>(ctx->d_gzjobs + rec_o);
-        hipLaunchKernelGGL(vk_inflate_kernel, dim3(nd), dim3(64), 0, ctx->stream, gz, out, d_jobs, nd, d_len, d_st, d_nm, d_cr, d_rec);
-        VK_HIP(ctx, hipGetLastError());
-        std::vector<unsigned long long> h_len(nd);
-        std::vector<uint32_t> h_st(3 * static_cast<size_t>(nd));
-        std::vector<uint2> h_rec(static_cast<size_t>(nd) * kGzMemRec);
-        VK_HIP(ctx, hipMemcpyAsync(h_rec.data(), d_rec, rec_b, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_len.data(), d_len, len_b, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipMemcpyAsync(h_st.data(), d_st, 3 * st_b, hipMemcpyDeviceToHost, ctx->stream));
-        VK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also keeps `jobs` alive until the copy has read it)
-        for (uint32_t j = 0; j < nd; ++j) {
-            const uint32_t i = direct[j];
-            out_lengths[i] = h_len[j];
-            status[i] = h_st[j];
-            const uint32_t nm = h_st[nd + j];
-            if (h_st[j] == 0 && nm >= 1 && nm <= kGzMemRec && h_len[j] < (1ull << 32)) {
-                members.clear();
-                for (uint32_t r = 0; r < nm; ++r) members.push_back({h_rec[static_cast<size_t>(j) * kGzMemRec + r].x, h_rec[static_cast<size_t>(j) * kGzMemRec + r].y});
-                add_member_checks(i, out_offsets[i], h_len[j]);
-            }
-        }
-    }
+    GzChecks checks;
+    int rc = big.empty() ? VK_OK : gz_chunked_stage(ctx, f, big, direct, checks);
+    if (rc) return rc;
+    rc = direct.empty() ? VK_OK : gz_direct_stage(ctx, f, direct, checks);
+    if (rc) return rc;
     // the check word of every member against the CRC-32 of the text it inflated to
-    if (!crc_jobs.empty()) {
+    if (!checks.jobs.empty()) {
         std::vector<uint32_t> got;
-        int rc = gz_text_crc(ctx, out, crc_jobs, got);
+        rc = gz_text_crc(ctx, f.out, checks.jobs, got);
         if (rc) return rc;
-        for (size_t j = 0; j < crc_jobs.size(); ++j)
-            if (got[j] != crc_want[j]) status[crc_file[j]] |= VK_GZ_BAD_CRC;
+        for (size_t j = 0; j < checks.jobs.size(); ++j)
+            if (got[j] != checks.want[j]) status[checks.file[j]] |= VK_GZ_BAD_CRC;
     }
     return VK_OK;
 }
@@ -2061,19 +1968,23 @@ int vk_clean_lines_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
         if (offsets[i] % 16) return VK_EINVAL;
     const ClIndex ix = cl_index(offsets, lengths, nullptr, nullptr, nullptr, nfiles, 0, 0);
     VK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_chunk = ws_align(nfiles * sizeof(ClFile)), o_lines = o_chunk + ws_align(nfiles * 8ull);
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, o_lines + nfiles * 8ull);
+    ClFile* d_files = nullptr;
+    uint64_t* d_fchunk = nullptr;
+    unsigned long long* d_lines = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_clines, &ctx->clines_cap, [&](WsTake& take) {
+        take(d_files, nfiles);
+        take(d_fchunk, nfiles);
+        take(d_lines, nfiles);
+    });
     if (rc) return rc;
-    uint8_t* m = ctx->d_clines;
-    VK_HIP(ctx, hipMemcpyAsync(m, ix.files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(m + o_chunk, ix.fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(m + o_lines, 0, nfiles * 8ull, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_files, ix.files.data(), nfiles * sizeof(ClFile), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_fchunk, ix.fchunk.data(), nfiles * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_lines, 0, nfiles * 8ull, ctx->stream));
     if (ix.nchunks)
         hipLaunchKernelGGL(vk_cl_lines_kernel, dim3(ix.nchunks), dim3(kClThreads), 0, ctx->stream,
-                           static_cast<const uint8_t*>(d_text), reinterpret_cast<const ClFile*>(m),
-                           reinterpret_cast<const uint64_t*>(m + o_chunk), nfiles, reinterpret_cast<unsigned long long*>(m + o_lines));
+                           static_cast<const uint8_t*>(d_text), d_files, d_fchunk, nfiles, d_lines);
     VK_HIP(ctx, hipGetLastError());
-    VK_HIP(ctx, hipMemcpyAsync(lines, m + o_lines, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(lines, d_lines, nfiles * 8ull, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }
@@ -2088,16 +1999,21 @@ int vk_clean_heads_device(vk_ctx* ctx, const void* d_text, const uint64_t* offse
     VK_HIP(ctx, hipSetDevice(ctx->device));
     // offsets | lengths | totals | counted, nfiles u64 words each, in the buffer of vk_clean_lines_device
     const size_t row = nfiles * 8ull;
-    int rc = ensure(ctx, reinterpret_cast<void**>(&ctx->d_clines), &ctx->clines_cap, 4 * row);
+    uint64_t *d_offs = nullptr, *d_lens = nullptr, *d_totals = nullptr, *d_counted = nullptr;
+    int rc = ws_carve(ctx, &ctx->d_clines, &ctx->clines_cap, [&](WsTake& take) {
+        take(d_offs, nfiles);
+        take(d_lens, nfiles);
+        take(d_totals, nfiles);
+        take(d_counted, nfiles);
+    });
     if (rc) return rc;
-    auto* m = reinterpret_cast<uint64_t*>(ctx->d_clines);
-    VK_HIP(ctx, hipMemcpyAsync(m, offsets, row, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(m + nfiles, lengths, row, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_offs, offsets, row, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(d_lens, lengths, row, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(vk_cl_heads_kernel, dim3(nfiles), dim3(kClThreads), 0, ctx->stream, static_cast<const uint8_t*>(d_text),
-                       m, m + nfiles, sample_size, m + 2ull * nfiles, m + 3ull * nfiles);
+                       d_offs, d_lens, sample_size, d_totals, d_counted);
     VK_HIP(ctx, hipGetLastError());
-    VK_HIP(ctx, hipMemcpyAsync(totals, m + 2ull * nfiles, row, hipMemcpyDeviceToHost, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(counted, m + 3ull * nfiles, row, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(totals, d_totals, row, hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(counted, d_counted, row, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }
