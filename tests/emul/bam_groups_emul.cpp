@@ -7,7 +7,8 @@
 // count pass takes panel after panel, notes every record's stream beside its start and fills the panel's row; the scan
 // turns the rows into the places where a panel's reads begin; the emit pass takes a panel's records 64 at a time, places
 // each read at its stream's cursor plus the sizes of the earlier lanes of the same stream, lets the last lane of every
-// stream move the cursor on, and writes item by item.  The file, the ID bytes, the hash table, the map, every segment's
+// stream move the cursor on, and writes item by item.  The hash table and the map are the product's: csrc/vk_bamplan.h's
+// bg_describe builds them, and the pieces the lanes read are copied out of its block.  The file, the ID bytes, the hash table, the map, every segment's
 // starts and notes and every text lie in heap blocks of exactly their size: under the address sanitizer a byte read past
 // the file (an aux length followed without a check), a probe past the table or a byte written past a text is an error.
 //
@@ -31,6 +32,7 @@
 #define VK_BAM_LANE_ONLY
 #include "vk_bam.h"
 #include "vk_bam_groups.h"
+#include "vk_bamplan.h"
 
 namespace {
 
@@ -46,9 +48,9 @@ struct Result {
 };
 
 template <class T>
-std::unique_ptr<T[]> exact(const std::vector<T>& v) {   // a heap block of exactly v's size
-    std::unique_ptr<T[]> p(new T[v.size()]);
-    for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
+std::unique_ptr<T[]> exact(const T* v, size_t n) {   // a heap block of exactly n elements
+    std::unique_ptr<T[]> p(new T[n]);
+    for (size_t i = 0; i < n; ++i) p[i] = v[i];
     return p;
 }
 
@@ -76,27 +78,36 @@ Result convert(const uint8_t* p, uint64_t len, uint64_t first, const std::vector
     if (!status && truth != len) status = kBamTruncated;
     res.status = status;
     if (status) return res;
-    // the tables, as the host layer builds them
+    // the tables: the host layer's own (bg_describe), as a call with this one file makes them
     const uint32_t ng = static_cast<uint32_t>(ids.size()), nslots = bam_table_slots(ng);
     std::vector<uint8_t> id_bytes;
-    std::vector<uint32_t> id_first(1, 0), slots(nslots, 0);
-    for (uint32_t g = 0; g < ng; ++g) {
-        uint32_t h = kBamHashSeed;
-        for (uint8_t b : ids[g]) h = bam_hash_step(h, b);
-        id_bytes.insert(id_bytes.end(), ids[g].begin(), ids[g].end());
+    std::vector<uint32_t> id_first(1, 0), stream_file(streams.size(), 0), select, group;
+    for (const auto& id : ids) {
+        id_bytes.insert(id_bytes.end(), id.begin(), id.end());
         id_first.push_back(static_cast<uint32_t>(id_bytes.size()));
-        uint32_t i = h & (nslots - 1);
-        while (slots[i]) i = (i + 1) & (nslots - 1);
-        slots[i] = g + 1;
     }
-    std::vector<uint16_t> map(3 * (ng + 1), kBamNoStream);
-    for (size_t s = 0; s < streams.size(); ++s)
-        for (uint32_t cls = 1; cls <= 3; ++cls)
-            if (streams[s].select == kBamAll || streams[s].select == cls) map[bam_map_at(cls, streams[s].group, ng)] = static_cast<uint16_t>(s);
-    const auto x_ids = exact(id_bytes);
-    const auto x_first = exact(id_first);
-    const auto x_slots = exact(slots);
-    const auto x_map = exact(map);
+    for (const Stream& s : streams) {
+        select.push_back(s.select);
+        group.push_back(s.group);
+    }
+    const uint32_t group_first[2] = {0, ng};
+    BamCall c{};
+    c.lengths = &len;
+    c.nfiles = 1;
+    c.group_first = group_first;
+    c.id_first = id_first.data();
+    c.id_bytes = id_bytes.data();
+    c.stream_file = stream_file.data();
+    c.stream_select = select.data();
+    c.stream_group = group.data();
+    c.nstreams = static_cast<uint32_t>(streams.size());
+    c.grouped = true;
+    std::vector<uint8_t> desc;
+    const BgPieces h = bg_describe(c, bg_counts(c, static_cast<uint32_t>(seg_bytes), static_cast<uint32_t>(panel)), desc);
+    const auto x_ids = exact(h.ids, id_bytes.size());
+    const auto x_first = exact(h.id_first, ng + 1);
+    const auto x_slots = exact(h.slots, nslots);
+    const auto x_map = exact(h.map, 3 * (ng + 1));
     const BamGroupTable T{x_ids.get(), x_first.get(), x_slots.get(), nslots - 1, ng};
     // count pass: a row per panel
     const uint64_t npan = (nseg + panel - 1) / panel;

@@ -198,6 +198,40 @@ def test_the_emit_grid_does_not_depend_on_the_groups(group_engines, seg):
     assert few[(BR.ALL, 0)] != b"" and len(few[(BR.ALL, GR.UNGROUPED)]) > len(many[(BR.SINGLE, GR.UNGROUPED)]) > 0
 
 
+def test_two_files_with_their_streams_interleaved(group_engines):
+    """File 0 without groups and with one stream, its ungrouped reads; file 1 with three groups and a stream per class and
+    group; file 0's stream stands in the middle of file 1's.  The smallest call in which a file's local streams are not
+    the call's (ls_stream, stream_local) and a file's rows do not begin at 0 (row_first): the framing call and the text
+    call against the rule."""
+    import torch
+    eng = group_engines("small")
+    cases, want = expected()
+    loose = next(c for c in cases if c[0] == "placement")
+    three = next(i for i, c in enumerate(cases) if c[0] == "groups_3")
+    two = [loose[:4] + ([],), cases[three]]
+    rule = [GR.convert(loose[1], loose[2], [], BR.EXCLUDE_DEFAULT), want[three]]
+    assert rule[0][0] == 0 and rule[1][0] == 0 and len(rule[0][1][(BR.ALL, GR.UNGROUPED)]) > 0
+    keys = [(1,) + k for k in streams_of(two[1][4], True)]
+    keys.insert(len(keys) // 2, (0, BR.ALL, GR.UNGROUPED))
+    assert sum(len(rule[1][1].get(k[1:], b"")) > 0 for k in keys[:5]) and sum(len(rule[1][1].get(k[1:], b"")) > 0 for k in keys[7:])
+    dev, host, offs, lens = lay_out(eng, two)
+    a = (dev, offs, lens, [c[2] for c in two], [c[3] for c in two], [c[4] for c in two], [k[0] for k in keys], [k[1] for k in keys],
+         [k[2] for k in keys])
+    recs, nbytes, status = eng.bam_groups_frame(*a)
+    oo = [3 + sum(int(n) + GAP for n in nbytes[:k]) for k in range(len(keys))]
+    out = torch.full((oo[-1] + int(nbytes[-1]) + 64,), OUT_SENTINEL, dtype=torch.uint8, device=eng.device)
+    got, status2 = eng.bam_groups_fastq(*a, out, oo, nbytes)
+    assert not status.any() and not status2.any() and np.array_equal(got, nbytes)
+    text = out.cpu().numpy()
+    mask = np.ones(len(text), dtype=bool)
+    for k, (f, sel, g) in enumerate(keys):
+        wt = rule[f][1].get((sel, g), b"")
+        assert text[oo[k]:oo[k] + int(got[k])].tobytes() == wt, keys[k]
+        assert int(recs[k]) == wt.count(b"\n") // 4, keys[k]
+        mask[oo[k]:oo[k] + int(got[k])] = False
+    assert (text[mask] == OUT_SENTINEL).all(), "a byte outside a stream's slot was written"
+
+
 def test_what_the_calls_refuse(group_engines):
     """VK_EINVAL before any launch: a group at or past the file's count, 1025 groups, a (file, select, group) named twice,
     VK_BAM_ALL mixed with a class select, an ID twice, an empty ID."""

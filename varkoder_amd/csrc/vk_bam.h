@@ -114,7 +114,13 @@ struct BamTally {
 };
 
 // The starts a segment of seg_bytes can hold: one per kBamMinRecord bytes.
-__device__ inline uint32_t bam_starts_cap(uint32_t seg_bytes) { return seg_bytes / kBamMinRecord + 2; }
+// (the host sizes its workspaces with it: vk_bamplan.h.  A lane-only build has no `__host__`: its `__device__` is empty)
+#ifdef VK_BAM_LANE_ONLY
+#define VK_BAM_HOST
+#else
+#define VK_BAM_HOST __host__
+#endif
+VK_BAM_HOST __device__ inline uint32_t bam_starts_cap(uint32_t seg_bytes) { return seg_bytes / kBamMinRecord + 2; }
 
 // From the record at `at` to the first that starts at or past `end`: the reads of each class and their text bytes.
 // Returns 0 or the status of the record it stopped at; *exit = that record, or the first one past the end.

@@ -124,7 +124,7 @@ __device__ inline uint64_t bam_aux_at(const BamRec& r) {
 
 // A file's map from (class, group) to the stream that takes such a read: map[(cls - 1) * (ngroups + 1) + slot], slot = the
 // group, or ngroups for an ungrouped read; kBamNoStream: none.
-__device__ inline uint32_t bam_map_at(uint32_t cls, uint32_t group, uint32_t ngroups) {
+__host__ __device__ inline uint32_t bam_map_at(uint32_t cls, uint32_t group, uint32_t ngroups) {
     return (cls - 1) * (ngroups + 1) + (group == kBamUngrouped ? ngroups : group);
 }
 
@@ -140,13 +140,13 @@ __device__ inline uint16_t bam_note_of(const uint8_t* p, const BamRec& r, uint32
     return map[bam_map_at(cls, g, T.ngroups)];
 }
 
-#ifndef VK_BAM_LANE_ONLY
-
-constexpr uint32_t kBamCountThreads = 256;
-
 struct BamRow {
     uint64_t recs, bytes;   // of a panel's reads in one stream; behind the scan `bytes` is where they begin in its text
 };
+
+#ifndef VK_BAM_LANE_ONLY
+
+constexpr uint32_t kBamCountThreads = 256;
 
 // The groups and streams of a call's files (device arrays), on top of BamMeta.
 struct BamGroupsMeta {

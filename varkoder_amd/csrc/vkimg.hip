@@ -51,6 +51,7 @@
 
 #include "vkimg.h"
 #include "vk_lane.h"
+#include "vk_ws.h"
 
 #include "vk_count.h"
 #include "vk_pack.h"
@@ -71,6 +72,7 @@
 #include "vk_fasta_windows.h"
 #include "vk_bam.h"
 #include "vk_bam_groups.h"
+#include "vk_bamplan.h"
 #include "vk_screen.h"
 #include "vk_qc.h"
 #include "vk_dist.h"
@@ -197,18 +199,6 @@ int ensure(vk_ctx* ctx, void** p, size_t* cap, size_t need) {
     *cap = n;
     return VK_OK;
 }
-
-size_t ws_align(size_t x) { return (x + 255) / 256 * 256; }
-// Hands out the pieces of a workspace one after another, each at a multiple of 256 bytes.  A piece is stated once: the
-// typed pointer it fills and its element count.  Without a base only the sizes add up (the *_workspace_size calls).
-struct WsTake {
-    uint8_t* base;
-    size_t at;
-    template <class T> void operator()(T*& piece, size_t count) {
-        piece = base ? reinterpret_cast<T*>(base + at) : nullptr;
-        at += ws_align(count * sizeof(T));
-    }
-};
 
 // A workspace of the context (*p, *cap: grown on demand) in the pieces `pieces(take)` states: once for the size, once for the pointers.
 template <class P, class F>
@@ -2885,112 +2875,231 @@ int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- BAM to FASTQ (vk_bam.h) --------------------------
+// ---------------------------------------------------------------- BAM to FASTQ (vk_bam.h, vk_bam_groups.h) ---------
+// The four calls are one sequence (bam_run): what a call carries, the rules of its arguments, the plans and the host's
+// tables and what is made of the results are vk_bamplan.h's; the workspaces, copies and launches are here.
 
 namespace {
 
-// What the two BAM calls share: the descriptors on the device, the segments, the link pass's results on the host.
-struct BamState {
-    BamMeta m;
-    BamStreams ss;
-    BamSeg* d_segs = nullptr;
-    uint16_t* d_starts = nullptr;   // bam_starts_cap per segment
-    BamFile* d_files = nullptr;
-    unsigned long long* d_link = nullptr;
-    uint64_t segs = 0, stream_segs = 0;
-    std::vector<BamFile> files;   // (host) once bam_finish has run
+// What the link pass reports is ONE run of pieces, so that one copy brings it back: the same statement lays out the run in
+// the device's workspace and, over a host buffer, its mirror.
+struct BamBack {
+    BamFile* files;
+    unsigned long long* link;   // segments, segments walked again
+};
+void bam_back(WsTake& take, BamBack& b, uint32_t nfiles) {
+    take(b.files, nfiles);
+    take(b.link, 2);
+}
+
+// d_bamws: the descriptors (made on the host, uploaded as one block) and the device-only pieces of the framing.
+struct BamPieces {
+    uint64_t *offs, *lens, *first, *seg_first, *sseg_first, *out_offs, *out_caps;
+    int32_t* n_ref;
+    uint32_t *stream_file, *stream_select;
+    size_t desc_bytes;
+    BamSeg* segs;
+    uint16_t* starts;   // bam_starts_cap per segment
+    BamBack back;
+    size_t back_bytes;
 };
 
-bool bam_args_ok(const vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
-                 const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select, uint32_t nstreams,
-                 uint32_t flags) {
-    if (!ctx || (flags & ~kBamNoGuess)) return false;
-    if (nfiles && (!d_bam || !offsets || !lengths || !first_record || !n_ref)) return false;
-    if (nstreams && (!stream_file || !stream_select)) return false;
-    for (uint32_t s = 0; s < nstreams; ++s)
-        if (stream_file[s] >= nfiles || stream_select[s] > kBamSingle) return false;
-    return true;
+void bam_take(WsTake& take, BamPieces& p, uint32_t nfiles, const BamPlan& pl) {
+    take(p.offs, nfiles);
+    take(p.lens, nfiles);
+    take(p.first, nfiles);
+    take(p.seg_first, nfiles + 1ull);
+    take(p.sseg_first, pl.nstreams + 1ull);
+    take(p.out_offs, pl.nstreams);
+    take(p.out_caps, pl.nstreams);
+    take(p.n_ref, nfiles);
+    take(p.stream_file, pl.nstreams);
+    take(p.stream_select, pl.nstreams);
+    p.desc_bytes = take.at;
+    take(p.segs, pl.segs);
+    take(p.starts, pl.segs * bam_starts_cap(pl.seg));
+    const size_t at = take.at;
+    bam_back(take, p.back, nfiles);
+    p.back_bytes = take.at - at;
 }
 
-// Segment pass and link pass (out_offsets, out_caps: null for the framing call).
-int bam_frame(vk_ctx* ctx, const uint8_t* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
-              const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select, uint32_t nstreams,
-              const uint64_t* out_offsets, const uint64_t* out_caps, uint32_t exclude, uint32_t flags, BamState* st) {
-    const uint32_t seg = ctx->bam_seg_bytes ? ctx->bam_seg_bytes : kBamSegBytes;
-    // u64 descriptors: offsets | lengths | first records | files' segment sums | streams' segment sums | slots | caps
-    std::vector<uint64_t> h64(3ull * nfiles + (nfiles + 1ull) + (nstreams + 1ull) + 2ull * nstreams);
-    uint64_t* h_offs = h64.data();
-    uint64_t* h_lens = h_offs + nfiles;
-    uint64_t* h_first = h_lens + nfiles;
-    uint64_t* h_seg_first = h_first + nfiles;
-    uint64_t* h_sseg_first = h_seg_first + nfiles + 1;
-    uint64_t* h_out_offs = h_sseg_first + nstreams + 1;
-    uint64_t* h_out_caps = h_out_offs + nstreams;
-    h_seg_first[0] = 0;
-    for (uint32_t i = 0; i < nfiles; ++i) {
-        h_offs[i] = offsets[i];
-        h_lens[i] = lengths[i];
-        h_first[i] = first_record[i];
-        const uint64_t n = (lengths[i] + seg - 1) / seg;
-        h_seg_first[i + 1] = h_seg_first[i] + (n ? n : 1);
-    }
-    h_sseg_first[0] = 0;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        const uint32_t f = stream_file[s];
-        h_sseg_first[s + 1] = h_sseg_first[s] + (h_seg_first[f + 1] - h_seg_first[f]);
-        h_out_offs[s] = out_offsets ? out_offsets[s] : 0;
-        h_out_caps[s] = out_caps ? out_caps[s] : 0;
-    }
-    st->segs = h_seg_first[nfiles];
-    st->stream_segs = h_sseg_first[nstreams];
-    if (st->segs >= (1ull << 31) || st->stream_segs >= (1ull << 31)) return VK_EINVAL;
-    // u32 descriptors: reference counts | streams' files | streams' selections
-    std::vector<uint32_t> h32(nfiles + 2ull * nstreams + 1);
-    for (uint32_t i = 0; i < nfiles; ++i) h32[i] = static_cast<uint32_t>(n_ref[i]);
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        h32[nfiles + s] = stream_file[s];
-        h32[nfiles + nstreams + s] = stream_select[s];
-    }
-    uint64_t* d64 = nullptr;
-    uint32_t* d32 = nullptr;
-    int rc = ws_carve(ctx, &ctx->d_bamws, &ctx->bamws_cap, [&](WsTake& take) {
-        take(d64, h64.size());
-        take(d32, h32.size());
-        take(st->d_segs, st->segs);
-        take(st->d_starts, st->segs * (seg / kBamMinRecord + 2));   // (bam_starts_cap)
-        take(st->d_files, nfiles);
-        take(st->d_link, 2);
-    });
+template <class T>
+void bam_put(T* dst, const T* src, size_t n) {
+    if (n) memcpy(dst, src, n * sizeof(T));
+}
+
+// What the calls share: the descriptors on the device, the plan, the link pass's results on the host.
+struct BamState {
+    BamPieces d{};
+    BamPlan plan;
+    BamMeta m;
+    BamStreams ss;
+    std::vector<uint8_t> mirror;   // (host) of d.back, once bam_finish has run: `h` points into it
+    BamBack h{};
+};
+
+// Segment pass and link pass.
+int bam_frame(vk_ctx* ctx, const BamCall& c, BamState* st) {
+    st->plan = bam_plan(c, ctx->bam_seg_bytes);
+    const BamPlan& pl = st->plan;
+    if (!pl.ok) return VK_EINVAL;
+    const uint32_t nfiles = c.nfiles;
+    BamPieces h{};
+    WsTake size{nullptr, 0};
+    bam_take(size, h, nfiles, pl);
+    std::vector<uint8_t> host(h.desc_bytes, 0);
+    WsTake on_host{host.data(), 0};
+    bam_take(on_host, h, nfiles, pl);
+    bam_put(h.offs, c.offsets, nfiles);
+    bam_put(h.lens, c.lengths, nfiles);
+    bam_put(h.first, c.first_record, nfiles);
+    bam_put(h.seg_first, pl.seg_first.data(), pl.seg_first.size());
+    bam_put(h.sseg_first, pl.sseg_first.data(), pl.sseg_first.size());
+    bam_put(h.out_offs, pl.out_offs.data(), pl.nstreams);
+    bam_put(h.out_caps, pl.out_caps.data(), pl.nstreams);
+    bam_put(h.n_ref, c.n_ref, nfiles);
+    bam_put(h.stream_file, c.stream_file, pl.nstreams);
+    bam_put(h.stream_select, c.stream_select, pl.nstreams);
+    int rc = ws_carve(ctx, &ctx->d_bamws, &ctx->bamws_cap, [&](WsTake& take) { bam_take(take, st->d, nfiles, pl); });
     if (rc) return rc;
-    // (pageable sources: the copies have read them on return)
-    VK_HIP(ctx, hipMemcpyAsync(d64, h64.data(), h64.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(d32, h32.data(), h32.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(st->d_link, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    st->m = BamMeta{d64, d64 + nfiles, d64 + 2ull * nfiles, d64 + 3ull * nfiles, reinterpret_cast<const int32_t*>(d32), nfiles, seg};
-    const uint64_t* d_sseg = d64 + 3ull * nfiles + nfiles + 1;
-    st->ss = BamStreams{d32 + nfiles, d32 + nfiles + nstreams, d_sseg, d_sseg + nstreams + 1, d_sseg + nstreams + 1 + nstreams, nstreams};
-    hipLaunchKernelGGL(vk_bam_segment_kernel, dim3(static_cast<uint32_t>(st->segs)), dim3(64), 0, ctx->stream, d_bam, st->m, exclude, flags,
-                       st->d_segs, st->d_starts);
+    const BamPieces& d = st->d;
+    // (a pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(ctx->d_bamws, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d.back.link, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    st->m = BamMeta{d.offs, d.lens, d.first, d.seg_first, d.n_ref, nfiles, pl.seg};
+    st->ss = BamStreams{d.stream_file, d.stream_select, d.sseg_first, d.out_offs, d.out_caps, pl.nstreams};
+    hipLaunchKernelGGL(vk_bam_segment_kernel, dim3(static_cast<uint32_t>(pl.segs)), dim3(64), 0, ctx->stream, c.d_bam, st->m, c.exclude,
+                       c.flags, d.segs, d.starts);
     VK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(vk_bam_link_kernel, dim3(nfiles), dim3(64), 0, ctx->stream, d_bam, st->m, exclude, st->d_segs, st->d_starts,
-                       st->d_files, st->d_link);
+    hipLaunchKernelGGL(vk_bam_link_kernel, dim3(nfiles), dim3(64), 0, ctx->stream, c.d_bam, st->m, c.exclude, d.segs, d.starts,
+                       d.back.files, d.back.link);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }
 
-// The link pass's results on the host; synchronises.
+int bam_emit(vk_ctx* ctx, const BamCall& c, const BamState& st) {
+    if (st.plan.stream_segs == 0) return VK_OK;
+    hipLaunchKernelGGL(vk_bam_emit_kernel, dim3(static_cast<uint32_t>(st.plan.stream_segs)), dim3(kBamEmitThreads), 0, ctx->stream,
+                       c.d_bam, st.m, st.ss, c.exclude, st.d.segs, st.d.starts, st.d.back.files, c.d_out);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// The link pass's results on the host (st->h); synchronises.
 int bam_finish(vk_ctx* ctx, uint32_t nfiles, BamState* st) {
-    st->files.resize(nfiles);
-    unsigned long long link[2] = {0, 0};
-    VK_HIP(ctx, hipMemcpyAsync(st->files.data(), st->d_files, nfiles * sizeof(BamFile), hipMemcpyDeviceToHost, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(link, st->d_link, sizeof(link), hipMemcpyDeviceToHost, ctx->stream));
+    st->mirror.resize(st->d.back_bytes);
+    WsTake on_host{st->mirror.data(), 0};
+    bam_back(on_host, st->h, nfiles);
+    VK_HIP(ctx, hipMemcpyAsync(st->mirror.data(), st->d.back.files, st->d.back_bytes, hipMemcpyDeviceToHost, ctx->stream));
     VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->bam_segments = link[0];
-    ctx->bam_rewalked = link[1];
+    ctx->bam_segments = st->h.link[0];
+    ctx->bam_rewalked = st->h.link[1];
     return VK_OK;
 }
 
-uint64_t bam_host_pick(const uint64_t* v, uint32_t select) { return select == kBamAll ? v[0] + v[1] + v[2] : v[select - 1]; }
+struct BgState {
+    BgPieces d{};
+    BgCounts n;
+    BamGroupsMeta G{};
+};
+
+// Behind bam_frame, for a grouped call: the tables, the count pass and the scan.
+int bg_count(vk_ctx* ctx, const BamCall& c, const BamState& st, BgState* bg) {
+    const uint32_t panel = ctx->bam_panel_segs ? ctx->bam_panel_segs : kBamPanelSegs;
+    bg->n = bg_counts(c, st.plan.seg, panel);
+    const BgCounts& n = bg->n;
+    std::vector<uint8_t> host;
+    bg_describe(c, n, host);
+    int rc = ws_carve(ctx, &ctx->d_bamgws, &ctx->bamgws_cap, [&](WsTake& take) { bg_take(take, bg->d, c.nfiles, c.nstreams, n); });
+    if (rc) return rc;
+    const BgPieces& d = bg->d;
+    // (a pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(ctx->d_bamgws, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d.aux_bad, 0, c.nfiles * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d.counters, 0, sizeof(unsigned long long), ctx->stream));
+    bg->G = BamGroupsMeta{d.ids, d.group_first, d.id_first, d.slots, d.slot_first, d.map, d.map_first, d.ls_first, d.ls_stream,
+                          d.pan_first, d.row_first, panel};
+    hipLaunchKernelGGL(vk_bam_groups_count_kernel, dim3(static_cast<uint32_t>(n.panels)), dim3(kBamCountThreads),
+                       n.max_ls * 2 * sizeof(unsigned long long), ctx->stream, c.d_bam, st.m, bg->G, c.exclude, st.d.segs, st.d.starts,
+                       st.d.back.files, d.notes, d.rows, d.aux_bad, d.counters);
+    VK_HIP(ctx, hipGetLastError());
+    if (c.nstreams) {
+        hipLaunchKernelGGL(vk_bam_groups_scan_kernel, dim3((c.nstreams + 3) / 4), dim3(256), 0, ctx->stream, st.m, bg->G, d.stream_file,
+                           d.stream_local, c.nstreams, st.d.back.files, d.aux_bad, d.rows, d.totals);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    return VK_OK;
+}
+
+int bg_emit(vk_ctx* ctx, const BamCall& c, const BamState& st, const BgState& bg) {
+    if (c.nstreams == 0) return VK_OK;
+    // a workgroup per panel: the grid does not depend on the streams
+    hipLaunchKernelGGL(vk_bam_groups_emit_kernel, dim3(static_cast<uint32_t>(bg.n.panels)), dim3(kBamEmitThreads),
+                       bg.n.max_ls * sizeof(unsigned long long), ctx->stream, c.d_bam, st.m, bg.G, bg.d.out_offs, bg.d.out_caps,
+                       st.d.segs, st.d.starts, bg.d.notes, st.d.back.files, bg.d.aux_bad, bg.d.rows, bg.d.totals, c.d_out);
+    VK_HIP(ctx, hipGetLastError());
+    ctx->bam_groups_wgs = bg.n.panels;
+    return VK_OK;
+}
+
+// The results of a grouped call on the host: totals[nstreams], aux_bad[nfiles], and bam_finish's; synchronises.
+int bg_finish(vk_ctx* ctx, const BamCall& c, BamState* st, const BgState& bg, std::vector<BamRow>* totals, std::vector<uint32_t>* aux_bad) {
+    totals->assign(c.nstreams, BamRow{0, 0});
+    std::vector<uint8_t> mirror(bg.d.back_bytes);
+    uint32_t* h_bad = nullptr;
+    unsigned long long* h_walked = nullptr;
+    WsTake on_host{mirror.data(), 0};
+    bg_back(on_host, h_bad, h_walked, c.nfiles);
+    if (c.nstreams)
+        VK_HIP(ctx, hipMemcpyAsync(totals->data(), bg.d.totals, c.nstreams * sizeof(BamRow), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(mirror.data(), bg.d.aux_bad, mirror.size(), hipMemcpyDeviceToHost, ctx->stream));
+    int rc = bam_finish(ctx, c.nfiles, st);
+    if (rc) return rc;
+    ctx->bam_groups_walked = *h_walked;
+    aux_bad->assign(h_bad, h_bad + c.nfiles);
+    return VK_OK;
+}
+
+// What a call wants back: per stream the reads and text bytes (a framing call) or the text's length (a text call), per
+// file the status.
+struct BamWant {
+    uint64_t *records, *bytes, *lengths;
+    uint32_t* status;
+};
+
+// The one sequence of the four calls: check, reset the counters of the last call, frame, (grouped: count and scan),
+// (text: emit), finish, write the results.
+int bam_run(vk_ctx* ctx, const BamCall& c, const BamWant& w) {
+    if (!ctx || !bam_args_ok(c) || (c.nfiles && (!c.d_bam || !w.status))) return VK_EINVAL;
+    if (c.nstreams && (c.text ? !c.d_out || !c.out_offsets || !c.out_caps || !w.lengths : !w.records || !w.bytes)) return VK_EINVAL;
+    if (c.grouped && !bg_args_ok(c)) return VK_EINVAL;
+    ctx->bam_segments = ctx->bam_rewalked = 0;
+    if (c.grouped) ctx->bam_groups_wgs = ctx->bam_groups_walked = 0;
+    if (c.nfiles == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    BamState st;
+    BgState bg;
+    std::vector<BamRow> totals;      // a grouped call's streams
+    std::vector<uint32_t> aux_bad;   // ... and files
+    int rc = bam_frame(ctx, c, &st);
+    if (rc == VK_OK && c.grouped) rc = bg_count(ctx, c, st, &bg);
+    if (rc == VK_OK && c.text) rc = c.grouped ? bg_emit(ctx, c, st, bg) : bam_emit(ctx, c, st);
+    if (rc == VK_OK) rc = c.grouped ? bg_finish(ctx, c, &st, bg, &totals, &aux_bad) : bam_finish(ctx, c.nfiles, &st);
+    if (rc) return rc;
+    const BamFile* files = st.h.files;
+    for (uint32_t i = 0; i < c.nfiles; ++i) w.status[i] = bam_status_of(files[i].status, c.grouped ? aux_bad[i] : 0u);
+    for (uint32_t s = 0; s < c.nstreams; ++s) {
+        const BamFile& f = files[c.stream_file[s]];
+        const BamRow got = c.grouped ? totals[s] : BamRow{bam_host_pick(f.recs, c.stream_select[s]), bam_host_pick(f.bytes, c.stream_select[s])};
+        if (!c.text) {
+            w.records[s] = got.recs;
+            w.bytes[s] = got.bytes;
+        } else if (!bam_slot_fits(got.bytes, c.out_caps[s], &w.lengths[s])) {
+            rc = VK_ENOSPC;
+        }
+    }
+    return rc;
+}
 
 }  // namespace
 
@@ -3000,55 +3109,19 @@ int vk_bam_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets,
                         const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select,
                         uint32_t nstreams, uint32_t exclude, uint32_t flags, uint64_t* out_records, uint64_t* out_bytes,
                         uint32_t* status) {
-    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
-        return VK_EINVAL;
-    if ((nstreams && (!out_records || !out_bytes)) || (nfiles && !status)) return VK_EINVAL;
-    ctx->bam_segments = ctx->bam_rewalked = 0;
-    if (nfiles == 0) return VK_OK;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    BamState st;
-    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select,
-                       nstreams, nullptr, nullptr, exclude, flags, &st);
-    if (rc) return rc;
-    rc = bam_finish(ctx, nfiles, &st);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st.files[i].status;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        out_records[s] = bam_host_pick(st.files[stream_file[s]].recs, stream_select[s]);
-        out_bytes[s] = bam_host_pick(st.files[stream_file[s]].bytes, stream_select[s]);
-    }
-    return VK_OK;
+    const BamCall c{static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, nullptr,
+                    stream_file, stream_select, nullptr, nstreams, nullptr, nullptr, nullptr, exclude, flags, false, false};
+    return bam_run(ctx, c, BamWant{out_records, out_bytes, nullptr, status});
 }
 
 int vk_bam_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* first_record,
                         const int32_t* n_ref, uint32_t nfiles, const uint32_t* stream_file, const uint32_t* stream_select,
                         uint32_t nstreams, uint32_t exclude, uint32_t flags, void* d_out, const uint64_t* out_offsets,
                         const uint64_t* out_caps, uint64_t* out_lengths, uint32_t* status) {
-    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
-        return VK_EINVAL;
-    if ((nstreams && (!d_out || !out_offsets || !out_caps || !out_lengths)) || (nfiles && !status)) return VK_EINVAL;
-    ctx->bam_segments = ctx->bam_rewalked = 0;
-    if (nfiles == 0) return VK_OK;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    BamState st;
-    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select,
-                       nstreams, out_offsets, out_caps, exclude, flags, &st);
-    if (rc) return rc;
-    if (st.stream_segs) {
-        hipLaunchKernelGGL(vk_bam_emit_kernel, dim3(static_cast<uint32_t>(st.stream_segs)), dim3(kBamEmitThreads), 0, ctx->stream,
-                           static_cast<const uint8_t*>(d_bam), st.m, st.ss, exclude, st.d_segs, st.d_starts, st.d_files,
-                           static_cast<uint8_t*>(d_out));
-        VK_HIP(ctx, hipGetLastError());
-    }
-    rc = bam_finish(ctx, nfiles, &st);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st.files[i].status;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        const uint64_t n = bam_host_pick(st.files[stream_file[s]].bytes, stream_select[s]);
-        out_lengths[s] = n <= out_caps[s] ? n : 0;
-        if (n > out_caps[s]) rc = VK_ENOSPC;
-    }
-    return rc;
+    const BamCall c{static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, nullptr,
+                    stream_file, stream_select, nullptr, nstreams, static_cast<uint8_t*>(d_out), out_offsets, out_caps, exclude, flags,
+                    false, true};
+    return bam_run(ctx, c, BamWant{nullptr, nullptr, out_lengths, status});
 }
 
 int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked) {
@@ -3058,215 +3131,6 @@ int vk_last_bam_frame(const vk_ctx* ctx, uint64_t* segments, uint64_t* rewalked)
     return VK_OK;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- BAM read groups (vk_bam_groups.h) ----------------
-
-namespace {
-
-// What a grouped call's sizes come to: of its tables, its notes and its rows.
-struct BgCounts {
-    uint64_t groups = 0, id_bytes = 0, slots = 0, map = 0, segs = 0, scap = 0, panels = 0, rows = 0;
-    uint32_t max_ls = 0;
-    std::vector<uint32_t> nls;   // [nfiles]: a file's streams
-};
-
-BgCounts bg_counts(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first,
-                   const uint32_t* stream_file, uint32_t nstreams, uint32_t seg, uint32_t panel) {
-    BgCounts c;
-    c.nls.assign(nfiles, 0);
-    for (uint32_t s = 0; s < nstreams; ++s) c.nls[stream_file[s]] += 1;
-    c.groups = nfiles ? group_first[nfiles] : 0;
-    c.id_bytes = c.groups ? id_first[c.groups] : 0;
-    c.scap = seg / kBamMinRecord + 2;   // (bam_starts_cap)
-    for (uint32_t f = 0; f < nfiles; ++f) {
-        const uint32_t ng = group_first[f + 1] - group_first[f];
-        c.slots += bam_table_slots(ng);
-        c.map += 3ull * (ng + 1);
-        uint64_t nseg = (lengths[f] + seg - 1) / seg;
-        if (nseg == 0) nseg = 1;
-        const uint64_t npan = (nseg + panel - 1) / panel;
-        c.segs += nseg;
-        c.panels += npan;
-        c.rows += npan * c.nls[f];
-        c.max_ls = std::max(c.max_ls, c.nls[f]);
-    }
-    return c;
-}
-
-// The descriptors (made on the host, uploaded as one block) and the device-only pieces of a grouped call.
-struct BgPieces {
-    uint8_t* ids;
-    uint32_t *group_first, *id_first, *slots, *slot_first, *map_first, *ls_first, *ls_stream, *stream_file, *stream_local;
-    uint16_t* map;
-    uint64_t *pan_first, *row_first, *out_offs, *out_caps;
-    size_t desc_bytes;
-    uint32_t* aux_bad;
-    unsigned long long* counters;
-    uint16_t* notes;
-    BamRow *rows, *totals;
-};
-
-void bg_take(WsTake& take, BgPieces& p, uint32_t nfiles, uint32_t nstreams, const BgCounts& c) {
-    take(p.ids, c.id_bytes);
-    take(p.group_first, nfiles + 1ull);
-    take(p.id_first, c.groups + 1);
-    take(p.slots, c.slots);
-    take(p.slot_first, nfiles);
-    take(p.map_first, nfiles);
-    take(p.ls_first, nfiles + 1ull);
-    take(p.ls_stream, nstreams);
-    take(p.stream_file, nstreams);
-    take(p.stream_local, nstreams);
-    take(p.map, c.map);
-    take(p.pan_first, nfiles + 1ull);
-    take(p.row_first, nfiles);
-    take(p.out_offs, nstreams);
-    take(p.out_caps, nstreams);
-    p.desc_bytes = take.at;
-    take(p.aux_bad, nfiles);
-    take(p.counters, 1);
-    take(p.notes, c.segs * c.scap);
-    take(p.rows, c.rows);
-    take(p.totals, nstreams);
-}
-
-bool bg_args_ok(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first, const uint8_t* id_bytes,
-                const uint32_t* stream_file, const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams) {
-    if (nfiles && (!group_first || !id_first || !lengths)) return false;
-    if (nstreams && !stream_group) return false;
-    if (nfiles && group_first[0] != 0) return false;
-    for (uint32_t f = 0; f < nfiles; ++f)
-        if (group_first[f + 1] < group_first[f] || group_first[f + 1] - group_first[f] > kBamMaxGroups) return false;
-    const uint32_t tg = nfiles ? group_first[nfiles] : 0;
-    if (tg && (!id_bytes || id_first[0] != 0)) return false;
-    for (uint32_t g = 0; g < tg; ++g)
-        if (id_first[g + 1] <= id_first[g] || id_first[g + 1] - id_first[g] > kBamMaxId) return false;
-    for (uint32_t f = 0; f < nfiles; ++f) {   // an ID names one group of its file
-        std::vector<std::string> ids;
-        for (uint32_t g = group_first[f]; g < group_first[f + 1]; ++g)
-            ids.emplace_back(reinterpret_cast<const char*>(id_bytes) + id_first[g], id_first[g + 1] - id_first[g]);
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return false;
-    }
-    std::vector<uint8_t> kinds(nfiles, 0);   // 1: a stream of VK_BAM_ALL, 2: one of a class
-    std::vector<std::pair<uint64_t, uint32_t>> keys;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        const uint32_t f = stream_file[s], g = stream_group[s];
-        if (g != kBamUngrouped && g >= group_first[f + 1] - group_first[f]) return false;
-        kinds[f] |= stream_select[s] == kBamAll ? 1 : 2;
-        if (kinds[f] == 3) return false;
-        keys.emplace_back(static_cast<uint64_t>(f) << 32 | g, stream_select[s]);
-    }
-    std::sort(keys.begin(), keys.end());
-    return std::adjacent_find(keys.begin(), keys.end()) == keys.end();
-}
-
-struct BgState {
-    BgPieces d{};
-    BgCounts c;
-    BamGroupsMeta G{};
-};
-
-// Behind bam_frame: the tables, the count pass and the scan (out_offsets, out_caps: null for the framing call).
-int bg_count(vk_ctx* ctx, const uint8_t* d_bam, const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first,
-             const uint32_t* id_first, const uint8_t* id_bytes, const uint32_t* stream_file, const uint32_t* stream_select,
-             const uint32_t* stream_group, uint32_t nstreams, const uint64_t* out_offsets, const uint64_t* out_caps, uint32_t exclude,
-             const BamState& st, BgState* bg) {
-    const uint32_t seg = st.m.seg_bytes, panel = ctx->bam_panel_segs ? ctx->bam_panel_segs : kBamPanelSegs;
-    bg->c = bg_counts(lengths, nfiles, group_first, id_first, stream_file, nstreams, seg, panel);
-    const BgCounts& c = bg->c;
-    WsTake size{nullptr, 0};
-    BgPieces h{};
-    bg_take(size, h, nfiles, nstreams, c);
-    std::vector<uint8_t> host(h.desc_bytes, 0);
-    WsTake on_host{host.data(), 0};
-    bg_take(on_host, h, nfiles, nstreams, c);
-    if (c.id_bytes) memcpy(h.ids, id_bytes, c.id_bytes);
-    memcpy(h.group_first, group_first, (nfiles + 1ull) * sizeof(uint32_t));
-    if (c.groups) memcpy(h.id_first, id_first, (c.groups + 1) * sizeof(uint32_t));
-    else h.id_first[0] = 0;
-    uint32_t slot_at = 0, map_at = 0;
-    uint64_t row_at = 0;
-    h.ls_first[0] = 0;
-    h.pan_first[0] = 0;
-    for (uint32_t f = 0; f < nfiles; ++f) {
-        const uint32_t g0 = group_first[f], ng = group_first[f + 1] - g0, nslots = bam_table_slots(ng);
-        h.slot_first[f] = slot_at;
-        for (uint32_t g = 0; g < ng; ++g) {
-            uint32_t hash = kBamHashSeed;
-            for (uint32_t i = id_first[g0 + g]; i < id_first[g0 + g + 1]; ++i) hash = bam_hash_step(hash, id_bytes[i]);
-            uint32_t i = hash & (nslots - 1);
-            while (h.slots[slot_at + i]) i = (i + 1) & (nslots - 1);
-            h.slots[slot_at + i] = g + 1;
-        }
-        slot_at += nslots;
-        h.map_first[f] = map_at;
-        for (uint32_t i = 0; i < 3 * (ng + 1); ++i) h.map[map_at + i] = kBamNoStream;
-        map_at += 3 * (ng + 1);
-        h.ls_first[f + 1] = h.ls_first[f] + c.nls[f];
-        uint64_t nseg = (lengths[f] + seg - 1) / seg;
-        if (nseg == 0) nseg = 1;
-        const uint64_t npan = (nseg + panel - 1) / panel;
-        h.pan_first[f + 1] = h.pan_first[f] + npan;
-        h.row_first[f] = row_at;
-        row_at += npan * c.nls[f];
-    }
-    std::vector<uint32_t> seen(nfiles, 0);
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        const uint32_t f = stream_file[s], ng = group_first[f + 1] - group_first[f], local = seen[f]++;
-        h.stream_file[s] = f;
-        h.stream_local[s] = local;
-        h.ls_stream[h.ls_first[f] + local] = s;
-        const uint32_t slot = stream_group[s] == kBamUngrouped ? ng : stream_group[s];
-        uint16_t* map = h.map + h.map_first[f];
-        for (uint32_t cls = 1; cls <= 3; ++cls)
-            if (stream_select[s] == kBamAll || stream_select[s] == cls) map[(cls - 1) * (ng + 1) + slot] = static_cast<uint16_t>(local);
-        h.out_offs[s] = out_offsets ? out_offsets[s] : 0;
-        h.out_caps[s] = out_caps ? out_caps[s] : 0;
-    }
-    int rc = ws_carve(ctx, &ctx->d_bamgws, &ctx->bamgws_cap, [&](WsTake& take) { bg_take(take, bg->d, nfiles, nstreams, c); });
-    if (rc) return rc;
-    const BgPieces& d = bg->d;
-    // (a pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(ctx->d_bamgws, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d.aux_bad, 0, nfiles * sizeof(uint32_t), ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d.counters, 0, sizeof(unsigned long long), ctx->stream));
-    bg->G = BamGroupsMeta{d.ids, d.group_first, d.id_first, d.slots, d.slot_first, d.map, d.map_first, d.ls_first, d.ls_stream,
-                          d.pan_first, d.row_first, panel};
-    hipLaunchKernelGGL(vk_bam_groups_count_kernel, dim3(static_cast<uint32_t>(c.panels)), dim3(kBamCountThreads),
-                       c.max_ls * 2 * sizeof(unsigned long long), ctx->stream, d_bam, st.m, bg->G, exclude, st.d_segs, st.d_starts,
-                       st.d_files, d.notes, d.rows, d.aux_bad, d.counters);
-    VK_HIP(ctx, hipGetLastError());
-    if (nstreams) {
-        hipLaunchKernelGGL(vk_bam_groups_scan_kernel, dim3((nstreams + 3) / 4), dim3(256), 0, ctx->stream, st.m, bg->G, d.stream_file,
-                           d.stream_local, nstreams, st.d_files, d.aux_bad, d.rows, d.totals);
-        VK_HIP(ctx, hipGetLastError());
-    }
-    return VK_OK;
-}
-
-// The results of a grouped call on the host: totals[nstreams], status[nfiles]; synchronises.
-int bg_finish(vk_ctx* ctx, uint32_t nfiles, uint32_t nstreams, BamState* st, const BgState& bg, std::vector<BamRow>* totals,
-              uint32_t* status) {
-    totals->assign(nstreams, BamRow{0, 0});
-    std::vector<uint32_t> aux_bad(nfiles, 0);
-    unsigned long long walked = 0;
-    if (nstreams)
-        VK_HIP(ctx, hipMemcpyAsync(totals->data(), bg.d.totals, nstreams * sizeof(BamRow), hipMemcpyDeviceToHost, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(aux_bad.data(), bg.d.aux_bad, nfiles * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(&walked, bg.d.counters, sizeof(walked), hipMemcpyDeviceToHost, ctx->stream));
-    int rc = bam_finish(ctx, nfiles, st);
-    if (rc) return rc;
-    ctx->bam_groups_walked = walked;
-    for (uint32_t i = 0; i < nfiles; ++i) status[i] = st->files[i].status ? st->files[i].status : aux_bad[i] ? kBamBadAux : 0u;
-    return VK_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int vk_bam_groups_workspace_size(const uint64_t* lengths, uint32_t nfiles, const uint32_t* group_first, const uint32_t* id_first,
                                  const uint32_t* stream_file, uint32_t nstreams, uint32_t seg_bytes, uint32_t panel_segs,
                                  uint64_t* bytes) {
@@ -3274,12 +3138,14 @@ int vk_bam_groups_workspace_size(const uint64_t* lengths, uint32_t nfiles, const
     if ((seg_bytes && (seg_bytes < 64 || seg_bytes > kBamSegBytes)) || panel_segs > 4096) return VK_EINVAL;
     for (uint32_t s = 0; s < nstreams; ++s)
         if (stream_file[s] >= nfiles) return VK_EINVAL;
-    const BgCounts c = bg_counts(lengths, nfiles, group_first, id_first, stream_file, nstreams, seg_bytes ? seg_bytes : kBamSegBytes,
-                                 panel_segs ? panel_segs : kBamPanelSegs);
-    WsTake size{nullptr, 0};
-    BgPieces p{};
-    bg_take(size, p, nfiles, nstreams, c);
-    *bytes = size.at;
+    BamCall c{};
+    c.lengths = lengths;
+    c.nfiles = nfiles;
+    c.group_first = group_first;
+    c.id_first = id_first;
+    c.stream_file = stream_file;
+    c.nstreams = nstreams;
+    *bytes = bg_workspace_bytes(c, seg_bytes ? seg_bytes : kBamSegBytes, panel_segs ? panel_segs : kBamPanelSegs);
     return VK_OK;
 }
 
@@ -3288,29 +3154,9 @@ int vk_bam_groups_frame_device(vk_ctx* ctx, const void* d_bam, const uint64_t* o
                                const uint32_t* id_first, const uint8_t* id_bytes, const uint32_t* stream_file,
                                const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams, uint32_t exclude,
                                uint32_t flags, uint64_t* out_records, uint64_t* out_bytes, uint32_t* status) {
-    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
-        return VK_EINVAL;
-    if ((nstreams && (!out_records || !out_bytes)) || (nfiles && !status)) return VK_EINVAL;
-    if (!bg_args_ok(lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select, stream_group, nstreams)) return VK_EINVAL;
-    ctx->bam_segments = ctx->bam_rewalked = ctx->bam_groups_wgs = ctx->bam_groups_walked = 0;
-    if (nfiles == 0) return VK_OK;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    BamState st;
-    BgState bg;
-    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, 0, nullptr,
-                       nullptr, exclude, flags, &st);
-    if (rc) return rc;
-    rc = bg_count(ctx, static_cast<const uint8_t*>(d_bam), lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select,
-                  stream_group, nstreams, nullptr, nullptr, exclude, st, &bg);
-    if (rc) return rc;
-    std::vector<BamRow> totals;
-    rc = bg_finish(ctx, nfiles, nstreams, &st, bg, &totals, status);
-    if (rc) return rc;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        out_records[s] = totals[s].recs;
-        out_bytes[s] = totals[s].bytes;
-    }
-    return VK_OK;
+    const BamCall c{static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, group_first, id_first, id_bytes,
+                    stream_file, stream_select, stream_group, nstreams, nullptr, nullptr, nullptr, exclude, flags, true, false};
+    return bam_run(ctx, c, BamWant{out_records, out_bytes, nullptr, status});
 }
 
 int vk_bam_groups_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* offsets, const uint64_t* lengths,
@@ -3319,37 +3165,10 @@ int vk_bam_groups_fastq_device(vk_ctx* ctx, const void* d_bam, const uint64_t* o
                                const uint32_t* stream_select, const uint32_t* stream_group, uint32_t nstreams, uint32_t exclude,
                                uint32_t flags, void* d_out, const uint64_t* out_offsets, const uint64_t* out_caps, uint64_t* out_lengths,
                                uint32_t* status) {
-    if (!bam_args_ok(ctx, d_bam, offsets, lengths, first_record, n_ref, nfiles, stream_file, stream_select, nstreams, flags))
-        return VK_EINVAL;
-    if ((nstreams && (!d_out || !out_offsets || !out_caps || !out_lengths)) || (nfiles && !status)) return VK_EINVAL;
-    if (!bg_args_ok(lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select, stream_group, nstreams)) return VK_EINVAL;
-    ctx->bam_segments = ctx->bam_rewalked = ctx->bam_groups_wgs = ctx->bam_groups_walked = 0;
-    if (nfiles == 0) return VK_OK;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    BamState st;
-    BgState bg;
-    int rc = bam_frame(ctx, static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, nullptr, nullptr, 0, nullptr,
-                       nullptr, exclude, flags, &st);
-    if (rc) return rc;
-    rc = bg_count(ctx, static_cast<const uint8_t*>(d_bam), lengths, nfiles, group_first, id_first, id_bytes, stream_file, stream_select,
-                  stream_group, nstreams, out_offsets, out_caps, exclude, st, &bg);
-    if (rc) return rc;
-    if (nstreams) {   // a workgroup per panel: the grid does not depend on the streams
-        hipLaunchKernelGGL(vk_bam_groups_emit_kernel, dim3(static_cast<uint32_t>(bg.c.panels)), dim3(kBamEmitThreads),
-                           bg.c.max_ls * sizeof(unsigned long long), ctx->stream, static_cast<const uint8_t*>(d_bam), st.m, bg.G,
-                           bg.d.out_offs, bg.d.out_caps, st.d_segs, st.d_starts, bg.d.notes, st.d_files, bg.d.aux_bad, bg.d.rows,
-                           bg.d.totals, static_cast<uint8_t*>(d_out));
-        VK_HIP(ctx, hipGetLastError());
-        ctx->bam_groups_wgs = bg.c.panels;
-    }
-    std::vector<BamRow> totals;
-    rc = bg_finish(ctx, nfiles, nstreams, &st, bg, &totals, status);
-    if (rc) return rc;
-    for (uint32_t s = 0; s < nstreams; ++s) {
-        out_lengths[s] = totals[s].bytes <= out_caps[s] ? totals[s].bytes : 0;
-        if (totals[s].bytes > out_caps[s]) rc = VK_ENOSPC;
-    }
-    return rc;
+    const BamCall c{static_cast<const uint8_t*>(d_bam), offsets, lengths, first_record, n_ref, nfiles, group_first, id_first, id_bytes,
+                    stream_file, stream_select, stream_group, nstreams, static_cast<uint8_t*>(d_out), out_offsets, out_caps, exclude,
+                    flags, true, true};
+    return bam_run(ctx, c, BamWant{nullptr, nullptr, out_lengths, status});
 }
 
 int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* walked) {

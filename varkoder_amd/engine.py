@@ -89,6 +89,31 @@ MAPPED_BELOW_THREADS = 16
 PNG_CALL_BYTES = 512 << 20
 
 
+def slots16(sizes):
+    """Slots for texts of `sizes` bytes one after another, each at a multiple of 16 bytes (as upload() lays samples out):
+    (offsets uint64, the bytes of all slots together)."""
+    rounded = (np.asarray(sizes, dtype=np.uint64) + np.uint64(15)) // np.uint64(16) * np.uint64(16)
+    offs = np.zeros(len(rounded), dtype=np.uint64)
+    if len(rounded) > 1:
+        offs[1:] = np.cumsum(rounded[:-1])
+    return offs, int(rounded.sum())
+
+
+def _bam_group_args(nfiles, groups):
+    """groups: per file the list of its group IDs (bytes) -> (group_first uint32 [nfiles + 1], id_first uint32
+    [groups + 1], the ID bytes uint8 (never empty: ctypes wants an address))."""
+    groups = [list(g) for g in groups]
+    if len(groups) != nfiles:
+        raise ValueError("groups: one list of IDs per file")
+    gfirst = np.zeros(nfiles + 1, dtype=np.uint32)
+    gfirst[1:] = np.cumsum([len(g) for g in groups])
+    ids = [bytes(i) for g in groups for i in g]
+    ifirst = np.zeros(len(ids) + 1, dtype=np.uint32)
+    ifirst[1:] = np.cumsum([len(i) for i in ids])
+    raw = np.frombuffer(b"".join(ids) + b"\0", dtype=np.uint8).copy()
+    return gfirst, ifirst, raw
+
+
 def bam_groups_workspace_size(lengths, groups, stream_file, seg_bytes=0, panel_segs=0, L=None):
     """Bytes of workspace vk_bam_groups_frame_device / vk_bam_groups_fastq_device take beyond the ungrouped calls
     (vk_bam_groups_workspace_size: host only, no context) for files of `lengths` inflated bytes whose groups are
@@ -97,10 +122,7 @@ def bam_groups_workspace_size(lengths, groups, stream_file, seg_bytes=0, panel_s
     L = L or _capi.lib()
     lens = np.ascontiguousarray(lengths, dtype=np.uint64)
     sf = np.ascontiguousarray(stream_file, dtype=np.uint32)
-    gfirst = np.zeros(len(lens) + 1, dtype=np.uint32)
-    gfirst[1:] = np.cumsum([len(g) for g in groups])
-    ifirst = np.zeros(int(gfirst[-1]) + 1, dtype=np.uint32)
-    ifirst[1:] = np.cumsum([len(i) for g in groups for i in g])
+    gfirst, ifirst, _ = _bam_group_args(len(lens), groups)
     out = C.c_uint64()
     st = L.vk_bam_groups_workspace_size(_u64(lens), len(lens), _u32(gfirst), _u32(ifirst), _u32(sf), len(sf), int(seg_bytes),
                                         int(panel_segs), C.byref(out))
@@ -697,7 +719,11 @@ class ImageEngine:
         return hist
 
     # -- BAM ---------------------------------------------------------------------
-    def _bam_args(self, offsets, lengths, first_record, n_ref, stream_file, stream_select):
+    def _bam_call(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags, groups=None,
+                  stream_group=None, out=None, out_offsets=None, out_caps=None):
+        """One of the four BAM calls, marshalled and issued: with `groups` a grouped one, with `out` a text call.  A
+        framing call returns (records uint64 [nstreams], text bytes uint64 [nstreams], status uint32 [nfiles]), a text
+        call (text lengths uint64 [nstreams], status uint32 [nfiles]); on the host, synchronised."""
         offs, lens = self._desc(offsets, lengths)
         first = np.ascontiguousarray(first_record, dtype=np.uint64)
         nref = np.ascontiguousarray(n_ref, dtype=np.int32)
@@ -705,54 +731,66 @@ class ImageEngine:
         sel = np.ascontiguousarray(stream_select, dtype=np.uint32)
         if first.shape != offs.shape or nref.shape != offs.shape or sf.ndim != 1 or sf.shape != sel.shape:
             raise ValueError("first_record and n_ref: one per file; stream_file and stream_select: one per stream")
-        return offs, lens, first, nref, sf, sel
+        args = [self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first), nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs)]
+        if groups is not None:
+            gfirst, ifirst, raw = _bam_group_args(len(offs), groups)
+            sg = np.ascontiguousarray(stream_group, dtype=np.uint32)
+            if sg.shape != sf.shape:
+                raise ValueError("stream_group: one per stream")
+            args += [_u32(gfirst), _u32(ifirst), raw.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(sf), _u32(sel), _u32(sg)]
+        else:
+            args += [_u32(sf), _u32(sel)]
+        args += [len(sf), int(exclude), int(flags)]
+        status = np.zeros(len(offs), dtype=np.uint32)
+        if out is not None:
+            oo, oc = self._desc(out_offsets, out_caps)
+            if oo.shape != sf.shape:
+                raise ValueError("out_offsets and out_caps: one per stream")
+            got = np.zeros(len(sf), dtype=np.uint64)
+            args += [self._ptr(out), _u64(oo), _u64(oc), _u64(got), _u32(status)]
+            res = (got, status)
+        else:
+            recs = np.zeros(len(sf), dtype=np.uint64)
+            nbytes = np.zeros(len(sf), dtype=np.uint64)
+            args += [_u64(recs), _u64(nbytes), _u32(status)]
+            res = (recs, nbytes, status)
+        name = {(False, False): "vk_bam_frame_device", (False, True): "vk_bam_fastq_device",
+                (True, False): "vk_bam_groups_frame_device", (True, True): "vk_bam_groups_fastq_device"}[groups is not None, out is not None]
+        _capi.check(self.ctx, getattr(self.L, name)(*args), name)
+        return res
+
+    def _bam_text(self, frame, fastq, a, exclude, flags):
+        """A text buffer sized by the framing call `frame` (every stream at a multiple of 16 bytes, as upload() lays
+        samples out) and filled by the text call `fastq`, both on the arguments `a`: (records, out, offsets, lengths,
+        status)."""
+        recs, nbytes, _ = frame(*a, exclude, flags)
+        oo, total = slots16(nbytes)
+        torch = _torch()
+        out = torch.zeros(total + 16, dtype=torch.uint8, device=self.device)
+        got, status = fastq(*a, out, oo, nbytes, exclude, flags)
+        return recs, out, oo, got, status
 
     def bam_frame(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude=0x900, flags=0):
         """The reads of BAM files whose inflated bytes lie in HBM (vk_bam_frame_device; the rule: INTEGRATION.md,
         "--from-bam: the rule"): stream s takes the reads stream_select[s] (VK_BAM_ALL / READ1 / READ2 / SINGLE) of file
         stream_file[s].  Returns (records uint64 [nstreams], text bytes uint64 [nstreams], status uint32 [nfiles] of
         VK_BAM_* bits) on the host; synchronises."""
-        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
-        recs = np.zeros(len(sf), dtype=np.uint64)
-        nbytes = np.zeros(len(sf), dtype=np.uint64)
-        status = np.zeros(len(offs), dtype=np.uint32)
-        st = self.L.vk_bam_frame_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
-                                        nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(sf), _u32(sel), len(sf),
-                                        int(exclude), int(flags), _u64(recs), _u64(nbytes), _u32(status))
-        _capi.check(self.ctx, st, "vk_bam_frame_device")
-        return recs, nbytes, status
+        return self._bam_call(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags)
 
     def bam_fastq(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, out, out_offsets, out_caps,
                   exclude=0x900, flags=0):
         """The FASTQ text of those streams (vk_bam_fastq_device) into `out` (uint8 device tensor) at out_offsets, at most
         out_caps bytes each.  Returns (text lengths uint64 [nstreams], status uint32 [nfiles]) on the host;
         synchronises."""
-        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
-        oo, oc = self._desc(out_offsets, out_caps)
-        if oo.shape != sf.shape:
-            raise ValueError("out_offsets and out_caps: one per stream")
-        got = np.zeros(len(sf), dtype=np.uint64)
-        status = np.zeros(len(offs), dtype=np.uint32)
-        st = self.L.vk_bam_fastq_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
-                                        nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(sf), _u32(sel), len(sf),
-                                        int(exclude), int(flags), self._ptr(out), _u64(oo), _u64(oc), _u64(got), _u32(status))
-        _capi.check(self.ctx, st, "vk_bam_fastq_device")
-        return got, status
+        return self._bam_call(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags, out=out,
+                              out_offsets=out_offsets, out_caps=out_caps)
 
     def bam_to_fastq(self, bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude=0x900, flags=0):
         """bam_frame, a text buffer sized by it (every stream at a multiple of 16 bytes, as upload() lays samples out), and
         bam_fastq: (text uint8 device tensor, offsets uint64 [nstreams], lengths uint64 [nstreams], status uint32
         [nfiles]).  `bam` stays the caller's."""
-        torch = _torch()
-        _, nbytes, _ = self.bam_frame(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags)
-        oo = np.zeros(len(nbytes), dtype=np.uint64)
-        pos = 0
-        for i, n in enumerate(nbytes):
-            oo[i] = pos
-            pos += (int(n) + 15) // 16 * 16
-        out = torch.zeros(pos + 16, dtype=torch.uint8, device=self.device)
-        got, status = self.bam_fastq(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, out, oo, nbytes,
-                                     exclude, flags)
+        a = (bam, offsets, lengths, first_record, n_ref, stream_file, stream_select)
+        _, out, oo, got, status = self._bam_text(self.bam_frame, self.bam_fastq, a, exclude, flags)
         return out, oo, got, status
 
     def last_bam_frame(self):
@@ -762,23 +800,6 @@ class ImageEngine:
         return seg.value, re.value
 
     # -- BAM, split by read group ---------------------------------------------------
-    def _bam_group_args(self, nfiles, groups, stream_group, nstreams):
-        """groups: per file the list of its group IDs (bytes) -> (group_first uint32 [nfiles + 1], id_first uint32
-        [groups + 1], the ID bytes uint8 (never empty: ctypes wants an address), stream_group uint32 [nstreams])."""
-        groups = [list(g) for g in groups]
-        if len(groups) != nfiles:
-            raise ValueError("groups: one list of IDs per file")
-        gfirst = np.zeros(nfiles + 1, dtype=np.uint32)
-        gfirst[1:] = np.cumsum([len(g) for g in groups])
-        ids = [bytes(i) for g in groups for i in g]
-        ifirst = np.zeros(len(ids) + 1, dtype=np.uint32)
-        ifirst[1:] = np.cumsum([len(i) for i in ids])
-        raw = np.frombuffer(b"".join(ids) + b"\0", dtype=np.uint8).copy()
-        sg = np.ascontiguousarray(stream_group, dtype=np.uint32)
-        if sg.shape != (nstreams,):
-            raise ValueError("stream_group: one per stream")
-        return gfirst, ifirst, raw, sg
-
     def bam_groups_frame(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group,
                          exclude=0x900, flags=0):
         """bam_frame with the reads split by read group (vk_bam_groups_frame_device; the rule: INTEGRATION.md, "--from-bam
@@ -786,60 +807,29 @@ class ImageEngine:
         stream_select[s] of group stream_group[s] (an index into groups[stream_file[s]], or VK_BAM_UNGROUPED) of file
         stream_file[s].  Returns (records uint64 [nstreams], text bytes uint64 [nstreams], status uint32 [nfiles]: VK_BAM_*,
         VK_BAM_BAD_AUX among them) on the host; synchronises."""
-        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
-        gfirst, ifirst, raw, sg = self._bam_group_args(len(offs), groups, stream_group, len(sf))
-        recs = np.zeros(len(sf), dtype=np.uint64)
-        nbytes = np.zeros(len(sf), dtype=np.uint64)
-        status = np.zeros(len(offs), dtype=np.uint32)
-        st = self.L.vk_bam_groups_frame_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
-                                               nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(gfirst), _u32(ifirst),
-                                               raw.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(sf), _u32(sel), _u32(sg), len(sf),
-                                               int(exclude), int(flags), _u64(recs), _u64(nbytes), _u32(status))
-        _capi.check(self.ctx, st, "vk_bam_groups_frame_device")
-        return recs, nbytes, status
+        return self._bam_call(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags, groups=groups,
+                              stream_group=stream_group)
 
     def bam_groups_fastq(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group, out,
                          out_offsets, out_caps, exclude=0x900, flags=0):
         """The FASTQ text of those streams (vk_bam_groups_fastq_device) into `out` (uint8 device tensor) at out_offsets, at
         most out_caps bytes each.  Returns (text lengths uint64 [nstreams], status uint32 [nfiles]) on the host;
         synchronises."""
-        offs, lens, first, nref, sf, sel = self._bam_args(offsets, lengths, first_record, n_ref, stream_file, stream_select)
-        gfirst, ifirst, raw, sg = self._bam_group_args(len(offs), groups, stream_group, len(sf))
-        oo, oc = self._desc(out_offsets, out_caps)
-        if oo.shape != sf.shape:
-            raise ValueError("out_offsets and out_caps: one per stream")
-        got = np.zeros(len(sf), dtype=np.uint64)
-        status = np.zeros(len(offs), dtype=np.uint32)
-        st = self.L.vk_bam_groups_fastq_device(self.ctx, self._ptr(bam), _u64(offs), _u64(lens), _u64(first),
-                                               nref.ctypes.data_as(C.POINTER(C.c_int32)), len(offs), _u32(gfirst), _u32(ifirst),
-                                               raw.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(sf), _u32(sel), _u32(sg), len(sf),
-                                               int(exclude), int(flags), self._ptr(out), _u64(oo), _u64(oc), _u64(got), _u32(status))
-        _capi.check(self.ctx, st, "vk_bam_groups_fastq_device")
-        return got, status
+        return self._bam_call(bam, offsets, lengths, first_record, n_ref, stream_file, stream_select, exclude, flags, groups=groups,
+                              stream_group=stream_group, out=out, out_offsets=out_offsets, out_caps=out_caps)
 
     def bam_groups_to_fastq(self, bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group,
                             exclude=0x900, flags=0):
         """bam_groups_frame, a text buffer sized by it (every stream at a multiple of 16 bytes) and bam_groups_fastq: (text
         uint8 device tensor, offsets uint64 [nstreams], lengths uint64 [nstreams], reads uint64 [nstreams], status uint32
         [nfiles]).  `bam` stays the caller's."""
-        torch = _torch()
-        recs, nbytes, _ = self.bam_groups_frame(bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select,
-                                                stream_group, exclude, flags)
-        oo = np.zeros(len(nbytes), dtype=np.uint64)
-        pos = 0
-        for i, n in enumerate(nbytes):
-            oo[i] = pos
-            pos += (int(n) + 15) // 16 * 16
-        out = torch.zeros(pos + 16, dtype=torch.uint8, device=self.device)
-        got, status = self.bam_groups_fastq(bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select,
-                                            stream_group, out, oo, nbytes, exclude, flags)
+        a = (bam, offsets, lengths, first_record, n_ref, groups, stream_file, stream_select, stream_group)
+        recs, out, oo, got, status = self._bam_text(self.bam_groups_frame, self.bam_groups_fastq, a, exclude, flags)
         return out, oo, got, recs, status
 
     def bam_groups_workspace_size(self, lengths, groups, stream_file, seg_bytes=0, panel_segs=0):
         """Bytes of workspace the grouped calls take beyond the ungrouped ones (vk_bam_groups_workspace_size; host only)."""
-        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
-        sf = np.ascontiguousarray(stream_file, dtype=np.uint32)
-        return bam_groups_workspace_size(lens, groups, sf, seg_bytes, panel_segs, self.L)
+        return bam_groups_workspace_size(lengths, groups, stream_file, seg_bytes, panel_segs, self.L)
 
     def last_bam_groups(self):
         """(workgroups of the emit launch, records whose aux was walked) of the last bam_groups_frame / bam_groups_fastq
@@ -962,11 +952,8 @@ class ImageEngine:
                                                                    self.L.vk_clean_workspace_size)
         cap = np.zeros(nsamples, dtype=np.uint64)
         np.add.at(cap, samples.astype(np.int64), lens)
-        rounded = (cap + np.uint64(15)) // np.uint64(16) * np.uint64(16)
-        out_offs = np.zeros(nsamples, dtype=np.uint64)
-        if nsamples > 1:
-            out_offs[1:] = np.cumsum(rounded[:-1])
-        total = int(rounded.sum()) + 16
+        out_offs, total = slots16(cap)
+        total += 16
         out = torch.empty(total, dtype=torch.uint8, device=self.device)
         out_lens = torch.empty(nsamples, dtype=torch.int64, device=self.device)
         stats = torch.empty((nsamples, _capi.VK_CL_NSTAT), dtype=torch.int64, device=self.device)

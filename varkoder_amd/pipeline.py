@@ -755,10 +755,8 @@ def _bam_group_texts(eng, dev, doffs, dlens, first, n_ref, groups, files, stream
     full = [k for k in range(len(streams)) if nbytes[k]]
     text = None
     if full:
-        pos = 0
-        for k in full:
-            oo[k] = pos
-            pos += (int(nbytes[k]) + 15) // 16 * 16
+        from .engine import slots16
+        oo[full], pos = slots16(nbytes[full])
         import torch
         text = torch.zeros(pos + 16, dtype=torch.uint8, device=eng.device)
         got, status = eng.bam_groups_fastq(dev, doffs, dlens, first, n_ref, groups, [streams[k][0] for k in full],
