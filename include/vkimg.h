@@ -710,6 +710,44 @@ int vk_qc_workspace_size(const uint64_t* records, const uint64_t* lengths, uint3
 int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
                  uint32_t nstreams, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
+/* `image / query --kmer-spectrum`: the k-mer spectrum of cleaned FASTQ samples in HBM -- how many distinct canonical
+ * k-mers occur once, twice, ... -- from which depth, genome size and error rate are estimated (varkoder_amd/spectrum.py).
+ * The rule is this project's ("`--kmer-spectrum`: the rule", and tests/spectrum_ref.py); neither the
+ * reference nor any other call here counts k-mers of this size.
+ *
+ * Samples as for vk_screen_device: sample i is d_text[offsets[i] .. + lengths[i]) (offsets[i] a multiple of 16, any other
+ * returns VK_EINVAL before anything is read), records[i] its lines over 4.  A read's windows are taken from its sequence
+ * line as the screen takes them (a base is ACGT of either case, a trailing '\r' is no part of the line, the quality line
+ * is not looked at): every window of k (16 .. 31) unbroken bases gives a key, the smaller of the window and its reverse
+ * complement as 2k-bit integers.  A key is taken when the high half of the library's 64-bit mix of it is a multiple of
+ * `every` (>= 1; 1 takes every key and is exact): selection is by key, so every occurrence of a taken key counts and the
+ * taken keys' spectrum is a 1/every sample of the whole.
+ *
+ * Tables: sample i owns slots slot_base[i] .. + nslots[i] of d_keys (u64) and d_counts (u32), both caller-allocated;
+ * nslots[i] is a power of two of at least VK_SCREEN_MIN_SLOTS, the samples' ranges do not overlap, and the call
+ * initialises them.  slot_base and nslots are host arrays.
+ *
+ * d_rows[nsamples][VK_SPEC_NSTAT], u64 in this order:
+ *     0 reads   1 bases (sequence bytes, '\r' excluded)   2 windows   3 taken_windows   4 distinct (taken keys)
+ *     VK_SPEC_HIST  256: hist[c - 1] = distinct taken keys of multiplicity c = 1 .. 255, hist[255] those of 256 and more
+ * sum(hist) == distinct; the sum over c <= 255 of c hist[c - 1] <= taken_windows, equal when hist[255] == 0.
+ * d_status[nsamples]: VK_ST_*, VK_EM_TOO_LARGE, VK_EM_BAD_RECORDS as vk_ladder_emit_device reports them, and
+ * VK_SPEC_TABLE_FULL when a key of the sample found no slot (the probe ends after nslots[i] slots; it never spins).  A
+ * sample with a status gets an all-zero row and disturbs no other.  Results are integers and do not depend on the launch.
+ * d_ws: caller-allocated device workspace of vk_spectrum_workspace_size bytes (same records and lengths).  VK_EINVAL for a
+ * null pointer, nsamples 0, k outside 16 .. 31, every 0, an nslots[i] that is no power of two or below 1,024, an
+ * unaligned offset, a sample of more than 2^33 bytes (a multiplicity is 32-bit) or a workspace that is too small.  The
+ * call allocates no device memory and does not synchronise: it is enqueued on the context's stream (its host arrays
+ * have been read when it returns). */
+#define VK_SPEC_NSTAT 261u
+#define VK_SPEC_HIST 5u
+#define VK_SPEC_TABLE_FULL 32u
+int vk_spectrum_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes);
+int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                       const uint64_t* records, uint32_t nsamples, int k, uint32_t every, uint64_t* d_keys,
+                       uint32_t* d_counts, const uint64_t* slot_base, const uint64_t* nslots, uint64_t* d_rows,
+                       uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
+
 /* `compare`: exact squared Euclidean distances between images and the nearest neighbours of every query among the
  * references (the rule: INTEGRATION.md, "`compare`: the rule", and tests/dist_ref.py).  Neither the reference nor any
  * other call here compares images.

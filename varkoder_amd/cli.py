@@ -119,6 +119,7 @@ def setup_parser():
     add_adapter_flags(p)
     add_screen_flags(p)
     add_qc_flag(p)
+    add_spectrum_flags(p)
     q = sub.add_parser("query", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Query raw reads, cleaned reads or images against a trained network (cli.py:327-446).")
     q.add_argument("input", help="folder with cleaned reads (`<sample>.fq[.gz]`, e.g. <int>/clean_reads); with --from-raw, "
@@ -182,6 +183,7 @@ def setup_parser():
     add_adapter_flags(q)
     add_screen_flags(q)
     add_qc_flag(q)
+    add_spectrum_flags(q)
     q.add_argument("-b", "--max-batch-size", type=int, default=64, help="maximum batch size for predictions.")
     c = sub.add_parser("convert", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Convert images between different kmer mappings.")          # cli.py:447-482
@@ -322,6 +324,31 @@ def add_qc_flag(p):
                         "quality and base-content curves of the reads before and after cleaning, counted on the GPU where "
                         "their text lies, and add their columns to stats.csv; where the run starts from cleaned reads "
                         "the report has the `after` sections only (rule: INTEGRATION.md, \"--qc-report: the rule\")")
+
+
+SPECTRUM_K_DEFAULT, SPECTRUM_K_MIN, SPECTRUM_K_MAX = 21, 16, 31
+
+
+def add_spectrum_flags(p):
+    p.add_argument("--kmer-spectrum", default=argparse.SUPPRESS, metavar="DIR",   # (absent = nothing is counted)
+                   help="write DIR/<sample>.spectrum.json: the k-mer spectrum of the cleaned reads (behind the screen, once "
+                        "per sample), counted on the GPU where their text lies, with estimates of k-mer and base coverage, "
+                        "the genome's distinct k-mers, the error rate and the share of high-copy k-mers, and add their "
+                        "columns to stats.csv (--from-raw, --from-bam, --from-clean; query's cleaned reads; rule and limits: "
+                        "INTEGRATION.md, \"`--kmer-spectrum`: the rule\")")
+    p.add_argument("--spectrum-k", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help=f"with --kmer-spectrum: the k-mer size, {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX} ({SPECTRUM_K_DEFAULT} when absent)")
+    p.add_argument("--spectrum-every", type=int, default=argparse.SUPPRESS, metavar="M",
+                   help="with --kmer-spectrum: count the k-mers whose hash is a multiple of M, a 1/M sample of the spectrum "
+                        "in a table M times smaller (1 when absent: every k-mer, exact)")
+
+
+def spectrum_options(args):
+    """pipeline.Spectrum of `--kmer-spectrum`, None without it."""
+    if not hasattr(args, "kmer_spectrum"):
+        return None
+    from .pipeline import Spectrum
+    return Spectrum(Path(args.kmer_spectrum), getattr(args, "spectrum_k", SPECTRUM_K_DEFAULT), getattr(args, "spectrum_every", 1))
 
 
 def qc_options(args):
@@ -473,6 +500,23 @@ def parse_args(argv=None):
         if args.command == "image" and not (args.from_raw or args.from_clean or from_bam):
             parser.error("--qc-report: only with --from-raw, --from-bam or --from-clean (the default entry takes "
                          "subsamples that are drawn already)")
+    if args.command in ("image", "query"):
+        for name, flag in (("spectrum_k", "--spectrum-k"), ("spectrum_every", "--spectrum-every")):
+            if hasattr(args, name) and not hasattr(args, "kmer_spectrum"):
+                parser.error(f"{flag}: only with --kmer-spectrum")
+        if hasattr(args, "kmer_spectrum"):
+            # only where cleaned reads lie in HBM as FASTQ text whole
+            if getattr(args, "from_fasta", False):
+                parser.error("--kmer-spectrum: not with --from-fasta (the spectrum of reads tells depth; an assembly has none)")
+            if args.command == "query" and args.images:
+                parser.error("--kmer-spectrum: not with -I/--images (no reads)")
+            if args.command == "image" and not (args.from_raw or args.from_clean or from_bam):
+                parser.error("--kmer-spectrum: only with --from-raw, --from-bam or --from-clean (the default entry takes "
+                             "subsamples that are drawn already)")
+            if hasattr(args, "spectrum_k") and not SPECTRUM_K_MIN <= args.spectrum_k <= SPECTRUM_K_MAX:
+                parser.error(f"--spectrum-k: {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX}")
+            if hasattr(args, "spectrum_every") and args.spectrum_every < 1:
+                parser.error("--spectrum-every: at least 1")
     if getattr(args, "gpu_png", False):
         if args.command == "query" and not args.keep_images:
             parser.error("--gpu-png: only with -m/--keep-images")
@@ -691,7 +735,7 @@ def run_query(args):
                 found = clean_to_query([(s, inputs[i]) for i, s in wanted], max_bp=max_bp, seeds=seeds, engine=eng,
                                        k=args.kmer_size, mapping_code=args.kmer_mapping,
                                        io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args),
-                                       qc_dir=qc_options(args))
+                                       qc_dir=qc_options(args), spectrum=spectrum_options(args))
                 images = found_images(found, wanted, {})
         if rank == 0:
             if args.single_label:
@@ -806,7 +850,8 @@ class RawPlan:
         from .shard import io_threads_per_rank, shard_by_size
         args = self.args
         common = dict(k=args.kmer_size, mapping_code=args.kmer_mapping, max_bp=max_bp_of(args), seeds=self.seeds, engine=eng,
-                      io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args), qc_dir=qc_options(args))
+                      io_threads=io_threads_per_rank(args.n_threads), screen=screen_options(args), qc_dir=qc_options(args),
+                      spectrum=spectrum_options(args))
         found = {}
         if self.raw:
             found.update(raw_to_query(self.raw, weights=raw_weights, rank=rank, world=world, clean_dir=self.clean_dir,
@@ -867,7 +912,7 @@ def run_image_from_clean(args, outdir, rank, world, local_rank):
                                      base_sd=base_sd, **split_options(args), gpu_gzip=getattr(args, "gpu_gzip", False),
                                      device=local_rank, rank=rank, world=world, io_threads=io_threads_per_rank(args.n_threads),
                                      verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), screen=screen_options(args),
-                                     qc_dir=qc_options(args))
+                                     qc_dir=qc_options(args), spectrum=spectrum_options(args))
         for s, v in per_sample.items():
             v["base_frequencies_sd"] = base_sd.get(s, 0)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives
@@ -932,7 +977,7 @@ def run_image_from_raw(args, outdir, rank, world, local_rank):
                       seeds=plan.seeds, labels=plan.labels, device=local_rank, rank=rank, world=world,
                       io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, **split_options(args),
                       gpu_gzip=getattr(args, "gpu_gzip", False), gpu_png=getattr(args, "gpu_png", False),
-                      screen=screen_options(args), qc_dir=qc_options(args))
+                      screen=screen_options(args), qc_dir=qc_options(args), spectrum=spectrum_options(args))
         if plan.raw:
             got, sds = raw_to_images(plan.raw, outdir, weights=weights, clean_dir=plan.clean_dir, bam=plan.bam, **cleaning,
                                      **common)

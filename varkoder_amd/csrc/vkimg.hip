@@ -33,6 +33,7 @@
 //   vk_bam_groups_*_kernel (vk_bam_groups.h): the same split by read group (`--bam-read-groups`): one emit workgroup per panel.
 //   vk_dist_*_kernel (vk_dist.h): exact distances between images and nearest neighbours (`compare`): centred i8 rows, tiles on the i8 matrix cores, a workgroup's selection per row.
 //   vk_qc_*_kernel (vk_qc.h): quality profiles of FASTQ streams (`--qc-report`): wave per record, lanes on cycles, counters in LDS merged per workgroup.
+//   vk_sp_*_kernel (vk_spectrum.h): the k-mer spectrum of cleaned reads (`--kmer-spectrum`): wave per record, scattered atomics into a counting table in HBM, its histogram.
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,7 @@
 #include "vk_bam_groups.h"
 #include "vk_bamplan.h"
 #include "vk_screen.h"
+#include "vk_spectrum.h"
 #include "vk_qc.h"
 #include "vk_dist.h"
 
@@ -175,6 +177,8 @@ struct vk_ctx {
     uint32_t qc_merge = 0;         // VKIMG_QC_MERGE=n: records per workgroup of the QC count kernel, 1 to VK_QC_MERGE (tests: many merges in small cases; 0 = VK_QC_MERGE)
     uint32_t dist_strip = 0;       // VKIMG_DIST_STRIP=n: query rows of a strip of vk_dist_device, from 1 up to what the workspace holds (tests: strip seams in small inputs; 0 = what the workspace holds)
     uint32_t screen_tile = 0;      // VKIMG_SCREEN_TILE=n: bases of a wavefront's tile of the screen's match kernel, a multiple of 64 from 64 to 4096 (tests: tile seams in short reads; 0 = 4096)
+    uint32_t spectrum_tile = 0;    // VKIMG_SPECTRUM_TILE=n: the same for the spectrum's count kernel
+    uint32_t spectrum_merge = kSpMergeDefault;   // VKIMG_SPECTRUM_MERGE=0|1|2: how the count kernel merges equal keys of a wave instruction (SpParams::merge; tools/spectrum_time.py)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -681,6 +685,14 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
         if (ctx->screen_tile < 64) ctx->screen_tile = 64;
         if (ctx->screen_tile > kScMaxTile) ctx->screen_tile = kScMaxTile;
     }
+    env_uint("VKIMG_SPECTRUM_TILE", &ctx->spectrum_tile);
+    if (ctx->spectrum_tile) {
+        ctx->spectrum_tile = ctx->spectrum_tile / 64 * 64;
+        if (ctx->spectrum_tile < 64) ctx->spectrum_tile = 64;
+        if (ctx->spectrum_tile > kScMaxTile) ctx->spectrum_tile = kScMaxTile;
+    }
+    env_uint("VKIMG_SPECTRUM_MERGE", &ctx->spectrum_merge);
+    if (ctx->spectrum_merge > 2) ctx->spectrum_merge = kSpMergeDefault;
     env_uint("VKIMG_QC_MERGE", &ctx->qc_merge);
     if (ctx->qc_merge > kQcMerge) ctx->qc_merge = kQcMerge;
     env_uint("VKIMG_DIST_STRIP", &ctx->dist_strip);
@@ -3349,6 +3361,110 @@ int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, 
                            nrec, L.c.recs, L.oprefix, d_out);
     hipLaunchKernelGGL(vk_sc_pad_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.rec_base,
                        L.out_offs, nsamples, L.oprefix, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- the k-mer spectrum of cleaned reads (vk_spectrum.h) ------
+
+namespace {
+
+// the pieces of a vk_spectrum_device workspace: the record index in vk_clean_device's layout (the pieces of it that
+// cl_index_run fills), then the samples' tables
+struct SpLayout {
+    ClLayout c;
+    EmSample* samples;
+    uint64_t *rec_base, *block_base, *slot_base, *nslots;
+    size_t total;
+};
+
+SpLayout sp_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
+    SpLayout L{};
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
+        L.c.nrec += records[i];
+    }
+    const uint64_t nb = (L.c.nchunks + kClScanBlock - 1) / kClScanBlock;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.c.files, nsamples);
+    take(L.c.fchunk, nsamples);
+    take(L.c.ccount, L.c.nchunks);
+    take(L.c.cprefix, L.c.nchunks + 1);
+    take(L.c.sums, nb + 1);
+    take(L.c.recs, L.c.nrec);
+    take(L.samples, nsamples);
+    take(L.rec_base, nsamples + 1ull);
+    take(L.block_base, nsamples + 1ull);
+    take(L.slot_base, nsamples);
+    take(L.nslots, nsamples);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_spectrum_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes) {
+    if (!bytes || (nsamples && (!records || !lengths))) return VK_EINVAL;
+    *bytes = sp_layout(nullptr, records, nsamples, lengths).total;
+    return VK_OK;
+}
+
+int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+                       uint32_t nsamples, int k, uint32_t every, uint64_t* d_keys, uint32_t* d_counts, const uint64_t* slot_base,
+                       const uint64_t* nslots, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nsamples == 0 || !d_text || !offsets || !lengths || !records || !d_keys || !d_counts || !slot_base || !nslots ||
+        !d_rows || !d_status || !d_ws)
+        return VK_EINVAL;
+    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
+    std::vector<uint64_t> block_base(nsamples + 1ull, 0), rec_base(nsamples + 1ull, 0);
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        // (a sample of more than 2^33 bytes: a multiplicity is 32-bit)
+        if (offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i])) return VK_EINVAL;
+        block_base[i + 1] = block_base[i] + (nslots[i] + kSpSlotsPerBlock - 1) / kSpSlotsPerBlock;
+        rec_base[i + 1] = rec_base[i] + records[i];
+    }
+    const uint64_t nrec = rec_base[nsamples], nrblocks = (nrec + kScRecsPerBlock - 1) / kScRecsPerBlock;
+    if (block_base[nsamples] >= (1ull << 31) || nrblocks >= (1ull << 31)) return VK_EINVAL;
+    const SpLayout L = sp_layout(d_ws, records, nsamples, lengths);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    // a sample is one file of the record index
+    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
+    std::vector<EmSample> smp(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i)
+        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
+                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kSpNstat * sizeof(uint64_t), ctx->stream));
+    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                       L.samples, nsamples, L.c.recs, L.c.cprefix, d_status);
+    const dim3 tgrid(static_cast<uint32_t>(block_base[nsamples]));
+    auto* rows = reinterpret_cast<unsigned long long*>(d_rows);
+    hipLaunchKernelGGL(vk_sp_init_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots, d_keys,
+                       d_counts);
+    if (nrec) {
+        const SpParams P{d_keys, d_counts, L.slot_base, L.nslots, static_cast<uint32_t>(k), every,
+                         ctx->spectrum_tile ? ctx->spectrum_tile : kScMaxTile, ctx->spectrum_merge};
+        hipLaunchKernelGGL(vk_sp_count_kernel, dim3(static_cast<uint32_t>(nrblocks)), dim3(kClThreads), 0, ctx->stream, text, L.rec_base,
+                           nsamples, nrec, L.c.recs, d_status, P, rows);
+    }
+    hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
+                       d_counts, d_status, rows);
+    hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

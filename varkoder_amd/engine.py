@@ -1129,6 +1129,87 @@ class ImageEngine:
         # (the copies below wait for the kernels: the workspace is free after them)
         return rows.cpu().numpy().view(np.uint64), status.cpu().numpy().astype(np.uint32)
 
+    @staticmethod
+    def spectrum_slots(length, every=1):
+        """The table of a sample of `length` bytes of FASTQ text: the smallest power of two that is at least max(1024,
+        2 ceil(length / 2 / every)).  A record's sequence is less than half its bytes, so at every = 1 the load stays
+        below a half and the table cannot fill."""
+        want = max(_capi.VK_SCREEN_MIN_SLOTS, 2 * -(-int(length) // (2 * int(every))))
+        return 1 << (want - 1).bit_length()
+
+    def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30):
+        """The k-mer spectra of cleaned samples in HBM (vk_spectrum_device; the rule: INTEGRATION.md, "`--kmer-spectrum`:
+        the rule"): sample i is text[offs[i] .. + lens[i]), k in 16..31, a key is taken when the high half of its mix is
+        a multiple of `every`.  records: the samples' record counts (None: clean_lines here).  Returns (rows
+        uint64[n, VK_SPEC_NSTAT], status uint32[n]); a sample with a status has an all-zero row.
+
+        slots=None: sample i's table has spectrum_slots(lens[i], every) slots; with every > 1 a sample that comes back
+        VK_SPEC_TABLE_FULL is counted again with four times the slots, up to spectrum_slots(lens[i], 1), where it
+        cannot happen.  slots=int forces every sample's table (tests).  The samples are counted in groups whose tables
+        together stay under table_bytes at 12 bytes a slot; a sample whose table alone is larger gets a group of its own.
+        Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        k, every = int(k), int(every)
+        if not _capi.VK_SCREEN_MIN_K <= k <= _capi.VK_SCREEN_MAX_K:
+            raise ValueError(f"the spectrum's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
+        if every < 1:
+            raise ValueError("every is at least 1")
+        rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        if n == 0:
+            return rows, status
+        if records is None:
+            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        if len(recs) != n:
+            raise ValueError("one record count per sample")
+        if slots is None:
+            want = [self.spectrum_slots(x, every) for x in lens]
+            most = [self.spectrum_slots(x, 1) for x in lens]
+        else:
+            want = most = [int(slots)] * n
+        todo = list(range(n))
+        while todo:
+            # a group: samples in order while their tables fit
+            group, total = [], 0
+            while todo and (not group or total + want[todo[0]] * 12 <= int(table_bytes)):
+                total += want[todo[0]] * 12
+                group.append(todo.pop(0))
+            g = np.asarray(group, dtype=np.int64)
+            nsl = np.asarray([want[i] for i in group], dtype=np.uint64)
+            base = np.zeros(len(group), dtype=np.uint64)
+            base[1:] = np.cumsum(nsl[:-1])
+            try:
+                keys = torch.empty(int(nsl.sum()), dtype=torch.int64, device=self.device)
+                counts = torch.empty(int(nsl.sum()), dtype=torch.int32, device=self.device)
+            except RuntimeError as e:   # (torch.cuda.OutOfMemoryError is one)
+                raise MemoryError(f"no memory for a k-mer table of {int(nsl.sum())} slots ({int(nsl.sum()) * 12} bytes): "
+                                  "count a sample of the keys with a larger --spectrum-every") from e
+            o, l, r = offs[g].copy(), lens[g].copy(), recs[g].copy()
+            ws_bytes = C.c_uint64()
+            _capi.check(self.ctx, self.L.vk_spectrum_workspace_size(_u64(r), len(group), _u64(l), C.byref(ws_bytes)),
+                        "vk_spectrum_workspace_size")
+            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+            d_rows = torch.empty((len(group), _capi.VK_SPEC_NSTAT), dtype=torch.int64, device=self.device)
+            d_status = torch.empty(len(group), dtype=torch.int32, device=self.device)
+            st = self.L.vk_spectrum_device(self.ctx, self._ptr(text), _u64(o), _u64(l), _u64(r), len(group), k, every,
+                                           self._ptr(keys), self._ptr(counts), _u64(base), _u64(nsl), self._ptr(d_rows),
+                                           self._ptr(d_status), self._ptr(ws), ws.numel())
+            _capi.check(self.ctx, st, "vk_spectrum_device")
+            # (the copies below wait for the kernels: the tables and the workspace are free after them)
+            rows[g] = d_rows.cpu().numpy().view(np.uint64)
+            status[g] = d_status.cpu().numpy().astype(np.uint32)
+            del keys, counts, ws
+            # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
+            # the slots -- a bounded loop over a status; at spectrum_slots(., 1) it cannot fill
+            again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
+            for i in again:
+                want[i] = min(4 * want[i], most[i])
+            todo = again + todo
+        return rows, status
+
     def neighbours(self, q, r, n=10, qgroup=None, rgroup=None, matrix=False):
         """The n nearest references of every query image by exact squared Euclidean distance (vk_dist_device; the rule:
         INTEGRATION.md, "`compare`: the rule").  q, r: uint8 device tensors [nq, side, side] or [nq, P] of equal P; `q is

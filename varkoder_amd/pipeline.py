@@ -334,7 +334,7 @@ def fastqs_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, base_s
 def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp=None, is_query=False, seeds=None,
                     labels=None, base_sd=None, subfolder_levels=0, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, split_dir=None, overwrite=False, no_image=False,
-                    gpu_gzip=False, gpu_png=False, screen=None, qc_dir=None):
+                    gpu_gzip=False, gpu_png=False, screen=None, qc_dir=None, spectrum=None):
     """Steps C+D+E of run_clean2img (commands/image.py:1006-1127) for cleaned, UNSPLIT read files
     `<sample>.fq[.gz]` (the reference's `<int_folder>/clean_reads/`): the 1-2-5 ladder of subsamples
     is drawn on the GPU (subsample.ladder_counts) instead of writing one file per size with
@@ -346,7 +346,8 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     (SplitSink).  gpu_png: the images' IDAT chunks are made on the GPU (PngSink).  screen (Screen): the uploaded reads are
     screened in HBM before the ladder (`--exclude-fasta` / `--keep-fasta`); the stats gain its three columns.  qc_dir
     (`--qc-report`): `<qc_dir>/<sample>.qc.json` of the uploaded reads (behind the screen), its `after` sections only, and
-    qc.columns' columns in the stats.
+    qc.columns' columns in the stats.  spectrum (Spectrum, `--kmer-spectrum`): `<dir>/<sample>.spectrum.json` of the
+    uploaded reads (behind the screen), counted once per sample, and spectrum.columns' columns in the stats.
 
     seeds: {sample: int} (default 0).  Returns {sample: OrderedDict(stats)} with the reference's
     keys `splitting_bp_per_file`, `<k>mer_counting_time`, `k<k>_img_time`, or `failed_step`."""
@@ -368,6 +369,9 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
             if qc_dir is not None:
                 for f, row in zip(batch, QcReport.after(eng, dev, offs, lens)):
                     QcReport(qc_dir).emit(stem(f), None, row, stats.setdefault(stem(f), OrderedDict()), pool, reports)
+            if spectrum is not None:
+                for f, row in zip(batch, spectrum.after(eng, dev, offs, lens)):
+                    spectrum.emit(stem(f), row, stats.setdefault(stem(f), OrderedDict()), pool, reports)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
                                     splits=splits, no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=is_query)
             if verbose:
@@ -461,6 +465,31 @@ class QcReport:
         if stats_row is not None:
             stats_row.update(qc.columns(qc.add_rows(before.values()) if before else None, after))
         writes.append(pool.submit(qc.write_report, self.dir, sample, qc.report(before, after)))
+
+
+@dataclass
+class Spectrum:
+    """`--kmer-spectrum DIR`: the k-mer spectrum of a sample's cleaned text as the ladder sees it -- behind the screen,
+    once per sample, never per ladder step -- counted where the text lies in HBM (ImageEngine.spectrum; the rule:
+    INTEGRATION.md, "`--kmer-spectrum`: the rule"), written as `DIR/<sample>.spectrum.json` (spectrum.report) with its
+    stats.csv columns (spectrum.columns)."""
+    dir: object
+    k: int = 21
+    every: int = 1
+
+    def after(self, eng, text, offs, lens):
+        """The rows of cleaned samples in HBM.  A sample the count refuses (its framing) is reported and has a zero row."""
+        rows, status = eng.spectrum(text, offs, lens, k=self.k, every=self.every)
+        for j in np.flatnonzero(status):
+            eprint("SPECTRUM FAIL: sample", int(j), "of its batch - status", int(status[j]))
+        return rows
+
+    def emit(self, sample, row, stats_row, pool, writes):
+        """A sample's file queued on the pool (its future goes to `writes`) and its columns into stats_row (None: none)."""
+        from . import spectrum
+        if stats_row is not None:
+            stats_row.update(spectrum.columns(row, self.k, self.every))
+        writes.append(pool.submit(spectrum.write_report, self.dir, sample, spectrum.report(row, self.k, self.every)))
 
 
 def _seed_groups(names, seeds):
@@ -675,6 +704,7 @@ class Cleaning:
     gpu_gzip: bool = False
     screen: object = None   # `--exclude-fasta` / `--keep-fasta`: a Screen, applied right after the cleaning
     qc: object = None   # `--qc-report`: a QcReport
+    spectrum: object = None   # `--kmer-spectrum`: a Spectrum
     bam: object = None   # `--from-bam`: {"pairs": bool, "exclude": int, "groups": None or {sample: group}}; the plans then hold (file, role, select[, group, sample])
 
 
@@ -883,6 +913,10 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
         if opt.qc is not None:   # (behind the screen: what the ladder sees)
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
             qc_after = dict(zip(good, opt.qc.after(eng, out, ooffs[good], olens[good])))
+        spec_rows = {}
+        if opt.spectrum is not None:   # (behind the screen, once per sample: what the ladder sees)
+            good = [j for j in range(len(batch)) if not status[j] and j not in failed]
+            spec_rows = dict(zip(good, opt.spectrum.after(eng, out, ooffs[good], olens[good])))
         packed = {}
         if clean_dir is not None and opt.gpu_gzip:   # the cleaned text compressed where it lies: only the files' bytes come back
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
@@ -908,6 +942,8 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
                 st.update(opt.screen.columns(srows[j]))
             if opt.qc is not None:
                 opt.qc.emit(s, qc_before[j], qc_after[j], st, pool, writes)
+            if opt.spectrum is not None:
+                opt.spectrum.emit(s, spec_rows[j], st, pool, writes)
             if clean_dir is not None:
                 text = packed[j] if opt.gpu_gzip else out[int(ooffs[j]):int(ooffs[j]) + int(olens[j])].cpu().numpy().tobytes()
                 cutting = None
@@ -929,7 +965,7 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
                   merge=True, dedup=True, seeds=None, labels=None, subfolder_levels=0, device=0, rank=0, world=1,
                   batch_bytes=None, io_threads=8, engine=None, verbose=False, weights=None, clean_dir=None, adapters=None,
                   detect_adapters=False, split_dir=None, overwrite=False, no_image=False, gpu_gzip=False, bam=None,
-                  gpu_png=False, screen=None, qc_dir=None):
+                  gpu_png=False, screen=None, qc_dir=None, spectrum=None):
     """Steps B+C+D+E of run_clean2img (commands/image.py:938-1127) for RAW reads: samples = [(sample, [files])] as
     rawinput.process_input lists them.  A batch of samples is uploaded (a .gz inflated in HBM), cleaned on the GPU
     (ImageEngine.clean: vk_clean_device) and the cleaned text goes straight to the ladder of clean_to_images, without
@@ -953,12 +989,15 @@ def raw_to_images(samples, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
     qc_dir: `--qc-report` -- `<qc_dir>/<sample>.qc.json` (QcReport) of the raw texts under their read budget and of the
     cleaned text behind the screen; the stats gain qc.columns' columns.
 
+    spectrum (Spectrum): `--kmer-spectrum` -- `<dir>/<sample>.spectrum.json` of the cleaned text behind the screen, counted
+    once per sample (never per ladder step); the stats gain spectrum.columns' columns.
+
     Returns ({sample: OrderedDict(stats)}, {sample: base-frequency sd}) with the reference's keys `clean_basepairs`
     (nan with neither adapter trimming nor merging, commands/image.py:551-565), `cleaning_time`, then those of
     clean_to_images, or `failed_step`."""
     mine = _raw_plans(samples, weights, rank, world, bam)
     opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen,
-                   None if qc_dir is None else QcReport(qc_dir), bam)
+                   None if qc_dir is None else QcReport(qc_dir), spectrum, bam)
     stats, base_sd, writes = OrderedDict(), {}, []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         sink = PngSink(outdir, pool, k, mapping_code, labels or {}, base_sd, subfolder_levels, eng if gpu_png else None)
@@ -990,16 +1029,16 @@ def _query_rungs(eng, text, offs, lens, names, sources, seeds, max_bp, base_sd, 
 def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), adapter=True, merge=True, dedup=True,
                  seeds=None, device=0, rank=0, world=1, batch_bytes=None, io_threads=8, engine=None, verbose=False,
                  weights=None, clean_dir=None, adapters=None, detect_adapters=False, gpu_gzip=False, bam=None, screen=None,
-                 qc_dir=None):
+                 qc_dir=None, spectrum=None):
     """Steps B+C of run_clean2img as `varKoder query` runs it (commands/query.py:97-178): raw_to_images' batches, each
     cleaned sample subsampled once (-M) and counted.  Returns {sample: (bp, histogram uint32[4^k] on the device,
     base-frequency sd)} for this rank's samples in the order they were dealt; one that fails in clean or split is
     reported (CLEAN FAIL / SPLIT FAIL) and left out, the others go on.  Nothing is written except, with clean_dir,
     the cleaned reads and their reports as raw_to_images writes them (gpu_gzip: compressed on the GPU), and with qc_dir
-    the samples' `.qc.json`.  bam, screen, qc_dir: as raw_to_images takes them."""
+    the samples' `.qc.json`, with spectrum their `.spectrum.json`.  bam, screen, qc_dir, spectrum: as raw_to_images takes them."""
     mine = _raw_plans(samples, weights, rank, world, bam)
     opt = Cleaning(trim, adapter, merge, dedup, adapters, detect_adapters, clean_dir, max_bp, gpu_gzip, screen,
-                   None if qc_dir is None else QcReport(qc_dir), bam)
+                   None if qc_dir is None else QcReport(qc_dir), spectrum, bam)
     stats, base_sd, found, writes = OrderedDict(), {}, OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
         for out, ooffs, olens, names, _ in _clean_batches(eng, mine, pool, writes, stats, base_sd, opt,
@@ -1011,11 +1050,12 @@ def raw_to_query(samples, k=7, mapping_code="cgr", max_bp=None, trim=(10, 10), a
 
 
 def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, k=7, mapping_code="cgr", device=0,
-                   batch_bytes=None, io_threads=8, screen=None, qc_dir=None):
+                   batch_bytes=None, io_threads=8, screen=None, qc_dir=None, spectrum=None):
     """raw_to_query's result for samples = [(sample, its cleaned read file)] that an earlier run left in clean_dir
     (this rank's share, the files as they are; base_sd: their figures, image.base_sd_table).  screen (Screen): the
     uploaded reads are screened in HBM before they are subsampled.  qc_dir (`--qc-report`): `<qc_dir>/<sample>.qc.json`
-    of the uploaded reads (behind the screen), its `after` sections only."""
+    of the uploaded reads (behind the screen), its `after` sections only.  spectrum (Spectrum, `--kmer-spectrum`):
+    `<dir>/<sample>.spectrum.json` of the uploaded reads (behind the screen)."""
     samples = [(s, Path(f)) for s, f in samples]
     found, reports = OrderedDict(), []
     with engine_scope(engine, k, mapping_code, device, io_threads) as (eng, pool):
@@ -1027,6 +1067,9 @@ def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, 
             if qc_dir is not None:
                 for (s, _), row in zip(batch, QcReport.after(eng, dev, offs, lens)):
                     QcReport(qc_dir).emit(s, None, row, None, pool, reports)
+            if spectrum is not None:
+                for (s, _), row in zip(batch, spectrum.after(eng, dev, offs, lens)):
+                    spectrum.emit(s, row, None, pool, reports)
             _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], files, seeds or {}, max_bp, base_sd or {}, found)
         for w in reports:
             w.result()
