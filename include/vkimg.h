@@ -748,6 +748,39 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
                        uint32_t* d_counts, const uint64_t* slot_base, const uint64_t* nslots, uint64_t* d_rows,
                        uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
+/* `image / query --spectrum-sketch` and `distance`: a bottom-s MinHash sketch of each sample, taken from its spectrum
+ * table while that lies in HBM, and every pair of sketches compared.  The rule is this project's (INTEGRATION.md,
+ * "`--spectrum-sketch` and `distance`: the rule", and tests/sketch_ref.py); the reference has no such command.
+ *
+ * vk_sketch_device, after vk_spectrum_device and with its table arguments: sample i owns slots slot_base[i] .. +
+ * nslots[i] of d_keys (u64, a free slot all ones) and d_counts (u32); slot_base and nslots are host arrays, d_status
+ * u32[nsamples] is the spectrum's status array on the device.  (On tables made otherwise nslots[i] is any number from
+ * 1 to 2^31.)  A held slot is eligible when its count is at least min_count (>= 1).  d_hashes[nsamples][s], u64: the
+ * min(s, eligible) smallest values of the library's 64-bit mix (splitmix64's finaliser, a bijection) over the eligible
+ * keys, ascending, the rest of the row all ones.  d_info[nsamples][2], u64: eligible and length = min(s, eligible).  A
+ * sample with a status has eligible = length = 0 and disturbs no other.  The held keys of a table are distinct; if a
+ * key lies in several eligible slots its hash counts once per slot.  Results are integers and do not depend on the
+ * launch; the number of passes over a table does depend on its contents (two for spread hashes, at most seven) and is
+ * bounded.  d_ws: caller-allocated device workspace of vk_sketch_workspace_size bytes (same nslots, nsamples and s).
+ * VK_EINVAL for a null pointer, nsamples 0, min_count 0, s outside VK_SKETCH_MIN .. VK_SKETCH_MAX, an nslots[i] of 0 or
+ * above 2^31, or a workspace that is too small.  The call allocates no device memory and does not synchronise: it is
+ * enqueued on the context's stream (its host arrays have been read when it returns).
+ *
+ * vk_sketch_pairs_device: d_q u64[nq][s] with d_qlen u64[nq] (a length above s counts as s), d_r and d_rlen likewise
+ * (d_q == d_r is allowed); every row strictly ascending in its first length entries, all made with the same s.  For
+ * query i and reference j, with Sa and Sb their sketches: d_seen[i][j] = min(s, |Sa u Sb|) and d_shared[i][j] = the
+ * number of values among the d_seen[i][j] smallest of Sa u Sb that lie in both, u32 each; empty against empty gives 0
+ * and 0.  VK_EINVAL for a null pointer, s outside VK_SKETCH_MIN .. VK_SKETCH_MAX, nq or nr of 0 or above 2^20, or
+ * nq * nr above 2^32.  Allocates nothing and does not synchronise. */
+#define VK_SKETCH_MIN 64u
+#define VK_SKETCH_MAX (1u << 20)
+int vk_sketch_workspace_size(const uint64_t* nslots, uint32_t nsamples, uint32_t s, uint64_t* bytes);
+int vk_sketch_device(vk_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, const uint64_t* slot_base,
+                     const uint64_t* nslots, uint32_t nsamples, const uint32_t* d_status, uint32_t min_count, uint32_t s,
+                     uint64_t* d_hashes, uint64_t* d_info, void* d_ws, uint64_t ws_bytes);
+int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
+                           const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen);
+
 /* `compare`: exact squared Euclidean distances between images and the nearest neighbours of every query among the
  * references (the rule: INTEGRATION.md, "`compare`: the rule", and tests/dist_ref.py).  Neither the reference nor any
  * other call here compares images.

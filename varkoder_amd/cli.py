@@ -268,6 +268,20 @@ def setup_parser():
     m.add_argument("-n", "--n-threads", type=int, default=1, help="accepted for parity and inert: the files are read in turn")
     m.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
     m.add_argument("-v", "--verbose", action="store_true", default=False)
+    d = sub.add_parser("distance", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                       help="Genomic distances between samples from the sketches that `--kmer-spectrum DIR "
+                            "--spectrum-sketch S` wrote, every pair compared on the GPU (not in the reference; rule and "
+                            "limits: INTEGRATION.md, \"`--spectrum-sketch` and `distance`: the rule\").")
+    d.add_argument("input", help="path to the folder with the samples' .spectrum.json and .sketch.npy files (SPECTRA).")
+    d.add_argument("outdir", help="path to the folder where distances.csv will be written (OUT).")
+    d.add_argument("--against", metavar="REF_SPECTRA",
+                   help="folder of reference samples: the neighbours of every sample of SPECTRA are looked for among these. "
+                        "By default SPECTRA is compared with itself, a sample never with itself.")
+    d.add_argument("-N", "--neighbours", type=int, default=10, help="neighbours per sample, 1 at least.")
+    d.add_argument("--matrix", action="store_true", default=False,
+                   help="also write every pair: shared.npy, seen.npy (uint32), corrected_distance.npy (float64, NaN where "
+                        "there is none) with distances_rows.txt and distances_cols.txt.")
+    d.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
     return main
 
 
@@ -327,6 +341,7 @@ def add_qc_flag(p):
 
 
 SPECTRUM_K_DEFAULT, SPECTRUM_K_MIN, SPECTRUM_K_MAX = 21, 16, 31
+SKETCH_MIN, SKETCH_MAX = 64, 1 << 20
 
 
 def add_spectrum_flags(p):
@@ -341,6 +356,13 @@ def add_spectrum_flags(p):
     p.add_argument("--spectrum-every", type=int, default=argparse.SUPPRESS, metavar="M",
                    help="with --kmer-spectrum: count the k-mers whose hash is a multiple of M, a 1/M sample of the spectrum "
                         "in a table M times smaller (1 when absent: every k-mer, exact)")
+    p.add_argument("--spectrum-sketch", type=int, default=argparse.SUPPRESS, metavar="S",
+                   help=f"with --kmer-spectrum: also write DIR/<sample>.sketch.npy, the S ({SKETCH_MIN} to {SKETCH_MAX}) smallest "
+                        "hashes of the sample's distinct k-mers, taken on the GPU from the table the spectrum was counted "
+                        "in, and a \"sketch\" object in its .spectrum.json: what `distance` compares")
+    p.add_argument("--spectrum-sketch-min-count", type=int, default=argparse.SUPPRESS, metavar="M",
+                   help="with --spectrum-sketch: sketch the k-mers seen M times and more (1 when absent; 2 leaves most "
+                        "error k-mers out of a deep sample)")
 
 
 def spectrum_options(args):
@@ -348,7 +370,8 @@ def spectrum_options(args):
     if not hasattr(args, "kmer_spectrum"):
         return None
     from .pipeline import Spectrum
-    return Spectrum(Path(args.kmer_spectrum), getattr(args, "spectrum_k", SPECTRUM_K_DEFAULT), getattr(args, "spectrum_every", 1))
+    return Spectrum(Path(args.kmer_spectrum), getattr(args, "spectrum_k", SPECTRUM_K_DEFAULT), getattr(args, "spectrum_every", 1),
+                    getattr(args, "spectrum_sketch", None), getattr(args, "spectrum_sketch_min_count", 1))
 
 
 def qc_options(args):
@@ -411,6 +434,10 @@ def parse_args(argv=None):
             parser.error("-N/--neighbours: 1 to 64")
         if args.same_sample and args.against:
             parser.error("--same-sample: not with --against (nothing is excluded there)")
+        return args
+    if args.command == "distance":
+        if args.neighbours < 1:
+            parser.error("-N/--neighbours: at least 1")
         return args
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
@@ -501,7 +528,9 @@ def parse_args(argv=None):
             parser.error("--qc-report: only with --from-raw, --from-bam or --from-clean (the default entry takes "
                          "subsamples that are drawn already)")
     if args.command in ("image", "query"):
-        for name, flag in (("spectrum_k", "--spectrum-k"), ("spectrum_every", "--spectrum-every")):
+        for name, flag in (("spectrum_k", "--spectrum-k"), ("spectrum_every", "--spectrum-every"),
+                           ("spectrum_sketch", "--spectrum-sketch"),
+                           ("spectrum_sketch_min_count", "--spectrum-sketch-min-count")):
             if hasattr(args, name) and not hasattr(args, "kmer_spectrum"):
                 parser.error(f"{flag}: only with --kmer-spectrum")
         if hasattr(args, "kmer_spectrum"):
@@ -517,6 +546,13 @@ def parse_args(argv=None):
                 parser.error(f"--spectrum-k: {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX}")
             if hasattr(args, "spectrum_every") and args.spectrum_every < 1:
                 parser.error("--spectrum-every: at least 1")
+            if hasattr(args, "spectrum_sketch") and not SKETCH_MIN <= args.spectrum_sketch <= SKETCH_MAX:
+                parser.error(f"--spectrum-sketch: {SKETCH_MIN} to {SKETCH_MAX}")
+            if hasattr(args, "spectrum_sketch_min_count"):
+                if not hasattr(args, "spectrum_sketch"):
+                    parser.error("--spectrum-sketch-min-count: only with --spectrum-sketch")
+                if not 1 <= args.spectrum_sketch_min_count < 2 ** 32:
+                    parser.error("--spectrum-sketch-min-count: at least 1")
     if getattr(args, "gpu_png", False):
         if args.command == "query" and not args.keep_images:
             parser.error("--gpu-png: only with -m/--keep-images")
@@ -1154,6 +1190,9 @@ def main(argv=None):
     elif args.command == "compare":
         from .compare import run_compare
         run_compare(args)
+    elif args.command == "distance":
+        from .distance import run_distance
+        run_distance(args)
     eprint("DONE")
 
 

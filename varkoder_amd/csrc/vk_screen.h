@@ -49,7 +49,9 @@ __device__ inline uint32_t sc_code(uint32_t b) {   // A0 C1 G2 T3 in either case
     return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
 }
 
-__device__ inline uint64_t sc_mix(uint64_t z) {   // (splitmix64's finaliser; no result depends on it)
+// splitmix64's finaliser, a bijection on u64.  It defines the content of a file: the values of `<sample>.sketch.npy`
+// (vk_sketch.h, "hash": "splitmix64-finaliser", version 1) are these, so the mix stays as it is.
+__device__ inline uint64_t sc_mix(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);

@@ -34,6 +34,7 @@
 //   vk_dist_*_kernel (vk_dist.h): exact distances between images and nearest neighbours (`compare`): centred i8 rows, tiles on the i8 matrix cores, a workgroup's selection per row.
 //   vk_qc_*_kernel (vk_qc.h): quality profiles of FASTQ streams (`--qc-report`): wave per record, lanes on cycles, counters in LDS merged per workgroup.
 //   vk_sp_*_kernel (vk_spectrum.h): the k-mer spectrum of cleaned reads (`--kmer-spectrum`): wave per record, scattered atomics into a counting table in HBM, its histogram.
+//   vk_sk_*_kernel (vk_sketch.h): bottom-s MinHash sketches from the spectrum's tables (`--spectrum-sketch`: radix select, compaction, LDS runs, merge path) and all pairs of sketches compared (`distance`: a wavefront per pair).
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
 
@@ -76,6 +77,7 @@
 #include "vk_bamplan.h"
 #include "vk_screen.h"
 #include "vk_spectrum.h"
+#include "vk_sketch.h"
 #include "vk_qc.h"
 #include "vk_dist.h"
 
@@ -3465,6 +3467,133 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
     hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
                        d_counts, d_status, rows);
     hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- sketches from the spectrum's tables, and their pairs (vk_sketch.h) ------
+
+namespace {
+
+// the pieces of a vk_sketch_device workspace
+struct SkLayout {
+    uint64_t *block_base, *slot_base, *nslots;
+    SkState* state;
+    uint32_t* hist;
+    uint64_t *cand, *cand2;   // the candidates, and the merges' other buffer
+    uint64_t ncand;           // hashes of all the samples' buffers
+    uint64_t max_cap;
+    size_t total;
+};
+
+uint64_t sk_cap(uint64_t nslots, uint32_t s) {
+    return (s + std::max(kSkMinSlack, nslots >> kSkDigitBits) + kSkRun - 1) / kSkRun * kSkRun;
+}
+
+uint64_t sk_per_block(uint64_t nslots) {
+    return std::max(kSkMinPerBlock, (nslots + kSkMaxBlocksPerSample - 1) / kSkMaxBlocksPerSample);
+}
+
+bool sk_args_ok(const uint64_t* nslots, uint32_t nsamples, uint32_t s) {
+    if (!nslots || nsamples == 0 || s < kSkMinS || s > kSkMaxS) return false;
+    for (uint32_t i = 0; i < nsamples; ++i)
+        if (nslots[i] < 1 || nslots[i] > kSkMaxSlots) return false;
+    return true;
+}
+
+SkLayout sk_layout(void* d_ws, const uint64_t* nslots, uint32_t nsamples, uint32_t s) {
+    SkLayout L{};
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        L.ncand += sk_cap(nslots[i], s);
+        L.max_cap = std::max(L.max_cap, sk_cap(nslots[i], s));
+    }
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.block_base, nsamples + 1ull);
+    take(L.slot_base, nsamples);
+    take(L.nslots, nsamples);
+    take(L.state, nsamples);
+    take(L.hist, static_cast<size_t>(nsamples) * kSkBins);
+    take(L.cand, L.ncand);
+    take(L.cand2, L.ncand);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_sketch_workspace_size(const uint64_t* nslots, uint32_t nsamples, uint32_t s, uint64_t* bytes) {
+    if (!bytes || !sk_args_ok(nslots, nsamples, s)) return VK_EINVAL;
+    *bytes = sk_layout(nullptr, nslots, nsamples, s).total;
+    return VK_OK;
+}
+
+int vk_sketch_device(vk_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, const uint64_t* slot_base, const uint64_t* nslots,
+                     uint32_t nsamples, const uint32_t* d_status, uint32_t min_count, uint32_t s, uint64_t* d_hashes, uint64_t* d_info,
+                     void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || !d_keys || !d_counts || !slot_base || !d_status || !d_hashes || !d_info || !d_ws || min_count < 1 ||
+        !sk_args_ok(nslots, nsamples, s))
+        return VK_EINVAL;
+    const SkLayout L = sk_layout(d_ws, nslots, nsamples, s);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    std::vector<uint64_t> block_base(nsamples + 1ull, 0);
+    std::vector<SkState> state(nsamples);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        SkState S{};
+        S.cand_base = at;
+        S.per_block = sk_per_block(nslots[i]);
+        S.mode = kSkAll;
+        S.cap = static_cast<uint32_t>(sk_cap(nslots[i], s));
+        at += S.cap;
+        state[i] = S;
+        block_base[i + 1] = block_base[i] + (nslots[i] + S.per_block - 1) / S.per_block;
+    }
+    // the sort's and the row's workgroups: a sample's chunks of kSkRun candidates, of kClThreads row entries
+    const uint64_t chunks = L.max_cap / kSkRun, row_blocks = (s + kClThreads - 1) / kClThreads;
+    if (block_base[nsamples] >= (1ull << 31) || chunks * nsamples >= (1ull << 31) || row_blocks * nsamples >= (1ull << 31))
+        return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.state, state.data(), nsamples * sizeof(SkState), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(L.hist, 0, static_cast<size_t>(nsamples) * kSkBins * sizeof(uint32_t), ctx->stream));
+    const dim3 tgrid(static_cast<uint32_t>(block_base[nsamples]));
+    for (uint32_t round = 0; round < kSkRounds; ++round) {
+        hipLaunchKernelGGL(vk_sk_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
+                           d_keys, d_counts, d_status, min_count, round, L.state, L.hist);
+        hipLaunchKernelGGL(vk_sk_pick_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, round, s, L.state, L.hist);
+    }
+    hipLaunchKernelGGL(vk_sk_compact_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
+                       d_keys, d_counts, d_status, min_count, L.state, L.cand);
+    const dim3 sgrid(static_cast<uint32_t>(chunks * nsamples));
+    hipLaunchKernelGGL(vk_sk_run_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, d_status, L.state, static_cast<uint32_t>(chunks),
+                       L.cand);
+    uint64_t *src = L.cand, *dst = L.cand2;
+    for (uint64_t width = kSkRun; width < L.max_cap; width *= 2) {
+        hipLaunchKernelGGL(vk_sk_merge_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, d_status, L.state,
+                           static_cast<uint32_t>(chunks), static_cast<uint32_t>(width), src, dst);
+        std::swap(src, dst);
+    }
+    hipLaunchKernelGGL(vk_sk_finish_kernel, dim3(static_cast<uint32_t>(row_blocks * nsamples)), dim3(kClThreads), 0, ctx->stream,
+                       d_status, L.state, static_cast<uint32_t>(row_blocks), s, src, d_hashes, d_info);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
+                           const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen) {
+    if (!ctx || !d_q || !d_qlen || !d_r || !d_rlen || !d_shared || !d_seen || s < kSkMinS || s > kSkMaxS) return VK_EINVAL;
+    if (nq < 1 || nr < 1 || nq > kSkMaxSide || nr > kSkMaxSide || nq * nr > kSkMaxPairs) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t blocks = (nq * nr + kSkPairsPerBlock - 1) / kSkPairsPerBlock;   // (2^30 at most)
+    hipLaunchKernelGGL(vk_sk_pairs_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kClThreads), 0, ctx->stream, d_q, d_qlen,
+                       static_cast<uint32_t>(nq), d_r, d_rlen, static_cast<uint32_t>(nr), s, d_shared, d_seen);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

@@ -1137,7 +1137,7 @@ class ImageEngine:
         want = max(_capi.VK_SCREEN_MIN_SLOTS, 2 * -(-int(length) // (2 * int(every))))
         return 1 << (want - 1).bit_length()
 
-    def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30):
+    def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30, sketch=None):
         """The k-mer spectra of cleaned samples in HBM (vk_spectrum_device; the rule: INTEGRATION.md, "`--kmer-spectrum`:
         the rule"): sample i is text[offs[i] .. + lens[i]), k in 16..31, a key is taken when the high half of its mix is
         a multiple of `every`.  records: the samples' record counts (None: clean_lines here).  Returns (rows
@@ -1147,7 +1147,11 @@ class ImageEngine:
         VK_SPEC_TABLE_FULL is counted again with four times the slots, up to spectrum_slots(lens[i], 1), where it
         cannot happen.  slots=int forces every sample's table (tests).  The samples are counted in groups whose tables
         together stay under table_bytes at 12 bytes a slot; a sample whose table alone is larger gets a group of its own.
-        Synchronises."""
+
+        sketch=(s, m): also the samples' bottom-s MinHash sketches over the keys of multiplicity m and more (sketch_tables;
+        the rule: INTEGRATION.md, "`--spectrum-sketch` and `distance`: the rule"), taken from each group's tables before
+        they are freed -- a sample counted again from the attempt that succeeded.  Returns (rows, status, hashes
+        uint64[n, s], info uint64[n, 2] = eligible, length) then.  Synchronises."""
         torch = _torch()
         offs, lens = self._desc(offs, lens)
         n = len(offs)
@@ -1158,8 +1162,12 @@ class ImageEngine:
             raise ValueError("every is at least 1")
         rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
         status = np.zeros(n, dtype=np.uint32)
+        if sketch is not None:
+            sk_s, sk_m = self._sketch_args(*sketch)
+            hashes = np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64)
+            info = np.zeros((n, 2), dtype=np.uint64)
         if n == 0:
-            return rows, status
+            return (rows, status) if sketch is None else (rows, status, hashes, info)
         if records is None:
             records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
         recs = np.ascontiguousarray(records, dtype=np.uint64)
@@ -1199,6 +1207,8 @@ class ImageEngine:
                                            self._ptr(d_status), self._ptr(ws), ws.numel())
             _capi.check(self.ctx, st, "vk_spectrum_device")
             # (the copies below wait for the kernels: the tables and the workspace are free after them)
+            if sketch is not None:   # (while the tables lie there)
+                hashes[g], info[g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk_s, sk_m)
             rows[g] = d_rows.cpu().numpy().view(np.uint64)
             status[g] = d_status.cpu().numpy().astype(np.uint32)
             del keys, counts, ws
@@ -1208,7 +1218,70 @@ class ImageEngine:
             for i in again:
                 want[i] = min(4 * want[i], most[i])
             todo = again + todo
-        return rows, status
+        return (rows, status) if sketch is None else (rows, status, hashes, info)
+
+    @staticmethod
+    def _sketch_args(s, m):
+        s, m = int(s), int(m)
+        if not _capi.VK_SKETCH_MIN <= s <= _capi.VK_SKETCH_MAX:
+            raise ValueError(f"a sketch holds {_capi.VK_SKETCH_MIN}..{_capi.VK_SKETCH_MAX} hashes: {s}")
+        if not 1 <= m < 2 ** 32:
+            raise ValueError(f"the sketch's minimum multiplicity is at least 1: {m}")
+        return s, m
+
+    def sketch_tables(self, keys, counts, base, nslots, status, s, m=1):
+        """The bottom-s MinHash sketches of counting tables in HBM (vk_sketch_device): sample i owns slots base[i] .. +
+        nslots[i] of keys (int64 device tensor, a free slot all ones) and counts (int32 device tensor), status an int32
+        device tensor [n] (a sample with a status gets an empty sketch); a held slot is eligible when its count is at
+        least m.  Returns (hashes uint64[n, s]: the min(s, eligible) smallest mixes of eligible keys, ascending, then all
+        ones; info uint64[n, 2]: eligible, length).  Synchronises."""
+        torch = _torch()
+        s, m = self._sketch_args(s, m)
+        base = np.ascontiguousarray(base, dtype=np.uint64)
+        nslots = np.ascontiguousarray(nslots, dtype=np.uint64)
+        n = len(nslots)
+        if len(base) != n or int(status.numel()) != n:
+            raise ValueError("one base, one slot count and one status per sample")
+        if n and int((base + nslots).max()) > min(int(keys.numel()), int(counts.numel())):
+            raise ValueError("a sample's slots lie past the tables")
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_sketch_workspace_size(_u64(nslots), n, s, C.byref(ws_bytes)), "vk_sketch_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        d_hashes = torch.empty((n, s), dtype=torch.int64, device=self.device)
+        d_info = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        st = self.L.vk_sketch_device(self.ctx, self._ptr(keys), self._ptr(counts), _u64(base), _u64(nslots), n, self._ptr(status),
+                                     m, s, self._ptr(d_hashes), self._ptr(d_info), self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_sketch_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        return d_hashes.cpu().numpy().view(np.uint64), d_info.cpu().numpy().view(np.uint64)
+
+    def sketch_pairs(self, q, qlen, r, rlen, s):
+        """Every query sketch against every reference sketch (vk_sketch_pairs_device): q uint64[nq, s] with lengths
+        qlen[nq], r and rlen likewise (NumPy arrays, rows ascending in their first length entries; `r is q` compares a set
+        with itself).  Returns (shared uint32[nq, nr], seen uint32[nq, nr]): seen = min(s, |Sa u Sb|), shared = the values
+        among the seen smallest of the union that lie in both.  Synchronises."""
+        torch = _torch()
+        s = self._sketch_args(s, 1)[0]
+
+        def up(h, ln):
+            h = np.ascontiguousarray(h, dtype=np.uint64)
+            ln = np.ascontiguousarray(ln, dtype=np.uint64)
+            if h.ndim != 2 or h.shape[1] != s or ln.shape != (h.shape[0],):
+                raise ValueError(f"sketches are uint64 [n, {s}] with one length each")
+            if len(ln) and int(ln.max()) > s:
+                raise ValueError("a sketch is longer than its row")
+            return (torch.from_numpy(h.view(np.int64)).to(self.device), torch.from_numpy(ln.view(np.int64)).to(self.device))
+        dq, dql = up(q, qlen)
+        dr, drl = (dq, dql) if r is q else up(r, rlen)
+        nq, nr = int(dq.shape[0]), int(dr.shape[0])
+        if nq == 0 or nr == 0:
+            return np.zeros((nq, nr), dtype=np.uint32), np.zeros((nq, nr), dtype=np.uint32)
+        shared = torch.empty((nq, nr), dtype=torch.int32, device=self.device)
+        seen = torch.empty((nq, nr), dtype=torch.int32, device=self.device)
+        st = self.L.vk_sketch_pairs_device(self.ctx, self._ptr(dq), self._ptr(dql), nq, self._ptr(dr), self._ptr(drl), nr, s,
+                                           self._ptr(shared), self._ptr(seen))
+        _capi.check(self.ctx, st, "vk_sketch_pairs_device")
+        return shared.cpu().numpy().view(np.uint32), seen.cpu().numpy().view(np.uint32)
 
     def neighbours(self, q, r, n=10, qgroup=None, rgroup=None, matrix=False):
         """The n nearest references of every query image by exact squared Euclidean distance (vk_dist_device; the rule:

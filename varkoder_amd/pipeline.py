@@ -476,20 +476,34 @@ class Spectrum:
     dir: object
     k: int = 21
     every: int = 1
+    sketch_size: object = None    # `--spectrum-sketch S`: also `DIR/<sample>.sketch.npy` and the json's "sketch" object
+    sketch_min_count: int = 1     # `--spectrum-sketch-min-count M`
 
     def after(self, eng, text, offs, lens):
-        """The rows of cleaned samples in HBM.  A sample the count refuses (its framing) is reported and has a zero row."""
-        rows, status = eng.spectrum(text, offs, lens, k=self.k, every=self.every)
+        """The rows of cleaned samples in HBM.  A sample the count refuses (its framing) is reported and has a zero row.
+        With a sketch size every row comes as (row, the sketch's hashes, its eligible count)."""
+        if self.sketch_size is None:
+            rows, status = eng.spectrum(text, offs, lens, k=self.k, every=self.every)
+        else:
+            rows, status, hashes, info = eng.spectrum(text, offs, lens, k=self.k, every=self.every,
+                                                      sketch=(self.sketch_size, self.sketch_min_count))
         for j in np.flatnonzero(status):
             eprint("SPECTRUM FAIL: sample", int(j), "of its batch - status", int(status[j]))
-        return rows
+        if self.sketch_size is None:
+            return rows
+        return [(rows[j], hashes[j, :int(info[j, 1])].copy(), int(info[j, 0])) for j in range(len(rows))]
 
     def emit(self, sample, row, stats_row, pool, writes):
         """A sample's file queued on the pool (its future goes to `writes`) and its columns into stats_row (None: none)."""
-        from . import spectrum
+        from . import sketch, spectrum
+        sk = None
+        if self.sketch_size is not None:
+            row, hashes, eligible = row
+            sk = sketch.meta(self.sketch_size, self.sketch_min_count, eligible, len(hashes))
+            writes.append(pool.submit(sketch.write_sketch, self.dir, sample, hashes))
         if stats_row is not None:
             stats_row.update(spectrum.columns(row, self.k, self.every))
-        writes.append(pool.submit(spectrum.write_report, self.dir, sample, spectrum.report(row, self.k, self.every)))
+        writes.append(pool.submit(spectrum.write_report, self.dir, sample, spectrum.report(row, self.k, self.every, sketch=sk)))
 
 
 def _seed_groups(names, seeds):

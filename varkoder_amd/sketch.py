@@ -1,0 +1,68 @@
+"""`--spectrum-sketch` and `distance`: what two samples' bottom-s sketches (ImageEngine.spectrum(sketch=...),
+ImageEngine.sketch_pairs) say about the distance between their genomes, and the files that carry a sketch.  The rule, its
+derivation and its limits: INTEGRATION.md, "`--spectrum-sketch` and `distance`: the rule".  Pure Python: everything here
+works from the pair's integers and the spectrum's estimates alone."""
+import math
+from pathlib import Path
+
+import numpy as np
+
+HASH, VERSION = "splitmix64-finaliser", 1
+META_KEYS = ("size", "min_count", "hash", "version")   # what two sketches must share, beside the spectrum's k and every
+
+
+def jaccard(shared, seen):
+    """shared / seen; None when nothing was seen (two empty sketches)."""
+    return None if seen == 0 else shared / seen
+
+
+def mash_distance(j, k):
+    """-(1/k) ln(2J / (1 + J)): the Mash distance of a raw Jaccard index; 1.0 when J = 0, None when J is."""
+    if j is None:
+        return None
+    return 1.0 if j <= 0 else max(0.0, -math.log(2.0 * j / (1.0 + j)) / k)
+
+
+def seen_fraction(lam, m):
+    """eta = P(Poisson(lam) >= m): the share of a genome's k-mers that a library of k-mer coverage lam shows m times or more."""
+    term, below = math.exp(-lam), 0.0
+    for c in range(m):
+        below += term
+        term *= lam / (c + 1)
+    return max(0.0, 1.0 - below)
+
+
+def corrected_distance(j, k, every, m, a1, est1, a2, est2):
+    """The distance between the genomes behind two samples, corrected for their depths.  a_i: sample i's eligible count
+    (measured: error k-mers are in it); est_i: its spectrum estimates (spectrum.estimate: kmer_coverage lambda_i,
+    genome_kmers G_i).  The observed intersection is I = J (a1 + a2) / (1 + J); a k-mer of both genomes is seen in both
+    samples with probability eta_1 eta_2 and taken with probability 1 / every, so (1 - D)^k = 2 every I / (eta_1 eta_2 (G_1
+    + G_2)) and D = 1 - min(1, that)^(1/k).  None when J is, or when either sample's estimates are."""
+    if j is None or est1 is None or est2 is None:
+        return None
+    lam1, g1, lam2, g2 = est1.get("kmer_coverage"), est1.get("genome_kmers"), est2.get("kmer_coverage"), est2.get("genome_kmers")
+    if lam1 is None or g1 is None or lam2 is None or g2 is None:
+        return None
+    eta = seen_fraction(lam1, m) * seen_fraction(lam2, m)
+    if eta <= 0.0 or g1 + g2 <= 0.0:
+        return None
+    inter = j * (a1 + a2) / (1.0 + j)
+    x = 2.0 * every * inter / (eta * (g1 + g2))
+    return 1.0 - min(1.0, x) ** (1.0 / k)
+
+
+def meta(size, min_count, eligible, length):
+    """The `"sketch"` object of `<sample>.spectrum.json`."""
+    return {"size": int(size), "min_count": int(min_count), "eligible": int(eligible), "length": int(length), "hash": HASH,
+            "version": VERSION}
+
+
+def sketch_path(folder, sample):
+    return Path(folder) / (sample + ".sketch.npy")
+
+
+def write_sketch(folder, sample, hashes):
+    """`<folder>/<sample>.sketch.npy`: the sketch's `length` hashes, u64, ascending."""
+    path = sketch_path(folder, sample)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    np.save(path, np.ascontiguousarray(hashes, dtype=np.uint64))

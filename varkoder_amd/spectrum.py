@@ -48,15 +48,19 @@ def estimate(row, k, every=1):
     return out
 
 
-def report(row, k, every=1):
-    """The object of `<sample>.spectrum.json`."""
+def report(row, k, every=1, sketch=None):
+    """The object of `<sample>.spectrum.json`.  sketch (`--spectrum-sketch`: sketch.meta) becomes its `"sketch"` object;
+    without one the object has no such key."""
     row = np.asarray(row, dtype=np.uint64)
     hist = [int(x) for x in row[HIST_AT:HIST_AT + BINS - 1]]
     while hist and hist[-1] == 0:
         hist.pop()
-    return {"k": int(k), "every": int(every), "reads": int(row[READS]), "bases": int(row[BASES]),
-            "windows": int(row[WINDOWS]), "taken_windows": int(row[TAKEN_WINDOWS]), "distinct": int(row[DISTINCT]),
-            "histogram": hist, "histogram_256_and_more": int(row[HIST_AT + BINS - 1]), "estimates": estimate(row, k, every)}
+    out = {"k": int(k), "every": int(every), "reads": int(row[READS]), "bases": int(row[BASES]),
+           "windows": int(row[WINDOWS]), "taken_windows": int(row[TAKEN_WINDOWS]), "distinct": int(row[DISTINCT]),
+           "histogram": hist, "histogram_256_and_more": int(row[HIST_AT + BINS - 1]), "estimates": estimate(row, k, every)}
+    if sketch is not None:
+        out["sketch"] = dict(sketch)
+    return out
 
 
 def columns(row, k, every=1):
