@@ -781,6 +781,42 @@ int vk_sketch_device(vk_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_coun
 int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
                            const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen);
 
+/* `image / query --kmer-spectrum --depth-filter`: cleaned reads kept by the depth of their own k-mers in their sample's
+ * spectrum table, while that lies in HBM.  The rule is this project's ("`--depth-filter`: the rule", and
+ * tests/depth_ref.py); neither the reference nor any other call here filters reads by depth.
+ *
+ * vk_depth_device, after vk_spectrum_device on the same text and with its arguments: samples, k and every as there;
+ * sample i owns slots slot_base[i] .. + nslots[i] of d_keys and d_counts as that call left them (they are only read);
+ * d_table_status u32[nsamples] is the spectrum's status array on the device.  A read's windows and keys are the
+ * spectrum's; the depth of a taken window is the count in the slot that holds its key, 0 when none does (the probe stops
+ * at a free slot or after nslots[i] slots; it never spins and never writes).  With n the taken windows of a record, its
+ * depth m is 0 for n == 0 and else the lower median of their depths, the element at index (n - 1) / 2 of the sorted
+ * depths.  The record is kept when lo[i] <= m <= hi[i] (host arrays, u32, both ends included; 2^32 - 1 is an open upper
+ * end); the decision is exact for any bounds.  A kept record is copied byte for byte and kept records stay in input
+ * order; the output is laid out as vk_screen_device lays it out (d_out, out_offsets, out_capacity, d_out_lengths as
+ * there).
+ *
+ * d_rows[nsamples][VK_DEPTH_NSTAT], u64 in this order:
+ *     0 records in   1 records kept   2 sequence bases in   3 sequence bases kept   4 records without a taken window
+ *     VK_DEPTH_HIST  256: hist[min(m, 255)] over all records in, kept or not
+ * d_status[nsamples]: VK_ST_*, VK_EM_TOO_LARGE, VK_EM_BAD_RECORDS as vk_ladder_emit_device reports them, joined with
+ * d_table_status[i] (VK_SPEC_TABLE_FULL: a table that filled is no table).  A sample with a status gets no text and an
+ * all-zero row and disturbs no other.  Results are integers and do not depend on the launch.  d_ws: caller-allocated
+ * device workspace of vk_depth_workspace_size bytes (same records and lengths).  VK_EINVAL, before anything is read or
+ * written, for a null pointer, nsamples 0, k outside 16 .. 31, every 0, an nslots[i] that is no power of two or below
+ * 1,024, an unaligned offset or output offset, a sample of more than 2^33 bytes, lo[i] > hi[i], an output region that
+ * does not end within out_capacity, or a workspace that is too small.  The call allocates no device memory and does not
+ * synchronise: it is enqueued on the context's stream (its host arrays have been read when it returns). */
+#define VK_DEPTH_NSTAT 261u
+#define VK_DEPTH_HIST 5u
+int vk_depth_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes);
+int vk_depth_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths,
+                    const uint64_t* records, uint32_t nsamples, int k, uint32_t every, const uint64_t* d_keys,
+                    const uint32_t* d_counts, const uint64_t* slot_base, const uint64_t* nslots,
+                    const uint32_t* d_table_status, const uint32_t* lo, const uint32_t* hi, uint8_t* d_out,
+                    const uint64_t* out_offsets, uint64_t out_capacity, uint64_t* d_out_lengths, uint64_t* d_rows,
+                    uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
+
 /* `compare`: exact squared Euclidean distances between images and the nearest neighbours of every query among the
  * references (the rule: INTEGRATION.md, "`compare`: the rule", and tests/dist_ref.py).  Neither the reference nor any
  * other call here compares images.

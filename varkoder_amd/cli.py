@@ -363,6 +363,14 @@ def add_spectrum_flags(p):
     p.add_argument("--spectrum-sketch-min-count", type=int, default=argparse.SUPPRESS, metavar="M",
                    help="with --spectrum-sketch: sketch the k-mers seen M times and more (1 when absent; 2 leaves most "
                         "error k-mers out of a deep sample)")
+    p.add_argument("--depth-filter", default=argparse.SUPPRESS, metavar="LO:HI",
+                   help="with --kmer-spectrum: keep the reads whose median k-mer depth in their own sample's spectrum lies in "
+                        "LO..HI, decided on the GPU against the table the spectrum was counted in; the files, the QC's after "
+                        "section and the images see what is kept.  Either end may be empty; an end is a multiplicity (:4 "
+                        "images the low-copy, nuclear reads of a skim, 20: the organelle and repeat reads) or a multiple of "
+                        "the sample's estimated k-mer coverage (3x:).  The sample's .spectrum.json gains a \"depth_filter\" "
+                        "object with the histogram of the reads' median depths (rule: INTEGRATION.md, \"`--depth-filter`: "
+                        "the rule\")")
 
 
 def spectrum_options(args):
@@ -371,7 +379,8 @@ def spectrum_options(args):
         return None
     from .pipeline import Spectrum
     return Spectrum(Path(args.kmer_spectrum), getattr(args, "spectrum_k", SPECTRUM_K_DEFAULT), getattr(args, "spectrum_every", 1),
-                    getattr(args, "spectrum_sketch", None), getattr(args, "spectrum_sketch_min_count", 1))
+                    getattr(args, "spectrum_sketch", None), getattr(args, "spectrum_sketch_min_count", 1),
+                    getattr(args, "depth_band", None))
 
 
 def qc_options(args):
@@ -530,7 +539,8 @@ def parse_args(argv=None):
     if args.command in ("image", "query"):
         for name, flag in (("spectrum_k", "--spectrum-k"), ("spectrum_every", "--spectrum-every"),
                            ("spectrum_sketch", "--spectrum-sketch"),
-                           ("spectrum_sketch_min_count", "--spectrum-sketch-min-count")):
+                           ("spectrum_sketch_min_count", "--spectrum-sketch-min-count"),
+                           ("depth_filter", "--depth-filter")):
             if hasattr(args, name) and not hasattr(args, "kmer_spectrum"):
                 parser.error(f"{flag}: only with --kmer-spectrum")
         if hasattr(args, "kmer_spectrum"):
@@ -553,6 +563,12 @@ def parse_args(argv=None):
                     parser.error("--spectrum-sketch-min-count: only with --spectrum-sketch")
                 if not 1 <= args.spectrum_sketch_min_count < 2 ** 32:
                     parser.error("--spectrum-sketch-min-count: at least 1")
+            if hasattr(args, "depth_filter"):
+                from . import depth
+                try:
+                    args.depth_band = depth.parse_band(args.depth_filter)
+                except ValueError as e:
+                    parser.error(f"--depth-filter: {e}")
     if getattr(args, "gpu_png", False):
         if args.command == "query" and not args.keep_images:
             parser.error("--gpu-png: only with -m/--keep-images")

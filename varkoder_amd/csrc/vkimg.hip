@@ -78,6 +78,7 @@
 #include "vk_screen.h"
 #include "vk_spectrum.h"
 #include "vk_sketch.h"
+#include "vk_depth.h"
 #include "vk_qc.h"
 #include "vk_dist.h"
 
@@ -181,6 +182,7 @@ struct vk_ctx {
     uint32_t screen_tile = 0;      // VKIMG_SCREEN_TILE=n: bases of a wavefront's tile of the screen's match kernel, a multiple of 64 from 64 to 4096 (tests: tile seams in short reads; 0 = 4096)
     uint32_t spectrum_tile = 0;    // VKIMG_SPECTRUM_TILE=n: the same for the spectrum's count kernel
     uint32_t spectrum_merge = kSpMergeDefault;   // VKIMG_SPECTRUM_MERGE=0|1|2: how the count kernel merges equal keys of a wave instruction (SpParams::merge; tools/spectrum_time.py)
+    uint32_t depth_merge = kDpMergeDefault;   // VKIMG_DEPTH_MERGE=0|1: how the depth filter's match kernel adds to its LDS histogram (DpParams::merge; tools/depth_time.py)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -695,6 +697,8 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     }
     env_uint("VKIMG_SPECTRUM_MERGE", &ctx->spectrum_merge);
     if (ctx->spectrum_merge > 2) ctx->spectrum_merge = kSpMergeDefault;
+    env_uint("VKIMG_DEPTH_MERGE", &ctx->depth_merge);
+    if (ctx->depth_merge > 1) ctx->depth_merge = kDpMergeDefault;
     env_uint("VKIMG_QC_MERGE", &ctx->qc_merge);
     if (ctx->qc_merge > kQcMerge) ctx->qc_merge = kQcMerge;
     env_uint("VKIMG_DIST_STRIP", &ctx->dist_strip);
@@ -3467,6 +3471,107 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
     hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
                        d_counts, d_status, rows);
     hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- reads kept by their k-mers' depth in the spectrum's tables (vk_depth.h) ------
+
+namespace {
+
+// the pieces of a vk_depth_device workspace: the screen's, then the samples' tables and bands
+struct DpLayout {
+    ScLayout s;
+    uint64_t *slot_base, *nslots;
+    uint32_t *lo, *hi;
+    size_t total;
+};
+
+DpLayout dp_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
+    DpLayout L{};
+    L.s = sc_layout(d_ws, records, nsamples, lengths);
+    WsTake take{static_cast<uint8_t*>(d_ws), L.s.total};
+    take(L.slot_base, nsamples);
+    take(L.nslots, nsamples);
+    take(L.lo, nsamples);
+    take(L.hi, nsamples);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_depth_workspace_size(const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, uint64_t* bytes) {
+    if (!bytes || (nsamples && (!records || !lengths))) return VK_EINVAL;
+    *bytes = dp_layout(nullptr, records, nsamples, lengths).total;
+    return VK_OK;
+}
+
+int vk_depth_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records,
+                    uint32_t nsamples, int k, uint32_t every, const uint64_t* d_keys, const uint32_t* d_counts,
+                    const uint64_t* slot_base, const uint64_t* nslots, const uint32_t* d_table_status, const uint32_t* lo,
+                    const uint32_t* hi, uint8_t* d_out, const uint64_t* out_offsets, uint64_t out_capacity, uint64_t* d_out_lengths,
+                    uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nsamples == 0 || !d_text || !offsets || !lengths || !records || !d_keys || !d_counts || !slot_base || !nslots ||
+        !d_table_status || !lo || !hi || !d_out || !out_offsets || !d_out_lengths || !d_rows || !d_status || !d_ws)
+        return VK_EINVAL;
+    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
+    std::vector<uint64_t> rec_base(nsamples + 1ull, 0);
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        if (offsets[i] % 16 || out_offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i]) || lo[i] > hi[i])
+            return VK_EINVAL;
+        // (a region as large as the sample's input, before anything is written)
+        if (out_offsets[i] > out_capacity || (lengths[i] + 15) / 16 * 16 > out_capacity - out_offsets[i]) return VK_EINVAL;
+        rec_base[i + 1] = rec_base[i] + records[i];
+    }
+    const uint64_t nrec = rec_base[nsamples], nrblocks = (nrec + kScRecsPerBlock - 1) / kScRecsPerBlock;
+    if (nrblocks >= (1ull << 31)) return VK_EINVAL;
+    const DpLayout L = dp_layout(d_ws, records, nsamples, lengths);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    // a sample is one file of the record index
+    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
+    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
+    std::vector<EmSample> smp(nsamples);
+    for (uint32_t i = 0; i < nsamples; ++i)
+        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
+                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_text);
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.s.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.s.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.s.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.lo, lo, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.hi, hi, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kDpNstat * sizeof(uint64_t), ctx->stream));
+    int rc = cl_index_run(ctx, text, ix, L.s.c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    const dim3 sgrid((nsamples + kClThreads - 1) / kClThreads);
+    hipLaunchKernelGGL(vk_em_status_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, text, L.s.samples, nsamples, L.s.c.recs,
+                       L.s.c.cprefix, d_status);
+    hipLaunchKernelGGL(vk_dp_status_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, d_table_status, nsamples, d_status);
+    const uint32_t nblocks = static_cast<uint32_t>(nrblocks);
+    if (nrec) {
+        const DpParams P{d_keys, d_counts, L.slot_base, L.nslots, L.lo, L.hi, static_cast<uint32_t>(k), every,
+                         ctx->spectrum_tile ? ctx->spectrum_tile : kScMaxTile, ctx->depth_merge};
+        hipLaunchKernelGGL(vk_dp_match_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.s.samples, L.s.rec_base,
+                           nsamples, nrec, L.s.c.recs, d_status, P, L.s.obytes, reinterpret_cast<unsigned long long*>(d_rows));
+    }
+    VK_HIP(ctx, hipGetLastError());
+    rc = cl_scan(ctx, L.s.obytes, nrec, L.s.c.sums, L.s.oprefix);
+    if (rc) return rc;
+    if (nrec)
+        hipLaunchKernelGGL(vk_sc_write_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.s.rec_base, L.s.out_offs,
+                           nsamples, nrec, L.s.c.recs, L.s.oprefix, d_out);
+    hipLaunchKernelGGL(vk_sc_pad_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, L.s.rec_base, L.s.out_offs, nsamples, L.s.oprefix,
+                       d_out, d_out_lengths);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

@@ -1137,7 +1137,7 @@ class ImageEngine:
         want = max(_capi.VK_SCREEN_MIN_SLOTS, 2 * -(-int(length) // (2 * int(every))))
         return 1 << (want - 1).bit_length()
 
-    def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30, sketch=None):
+    def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30, sketch=None, depth=None):
         """The k-mer spectra of cleaned samples in HBM (vk_spectrum_device; the rule: INTEGRATION.md, "`--kmer-spectrum`:
         the rule"): sample i is text[offs[i] .. + lens[i]), k in 16..31, a key is taken when the high half of its mix is
         a multiple of `every`.  records: the samples' record counts (None: clean_lines here).  Returns (rows
@@ -1151,7 +1151,16 @@ class ImageEngine:
         sketch=(s, m): also the samples' bottom-s MinHash sketches over the keys of multiplicity m and more (sketch_tables;
         the rule: INTEGRATION.md, "`--spectrum-sketch` and `distance`: the rule"), taken from each group's tables before
         they are freed -- a sample counted again from the attempt that succeeded.  Returns (rows, status, hashes
-        uint64[n, s], info uint64[n, 2] = eligible, length) then.  Synchronises."""
+        uint64[n, s], info uint64[n, 2] = eligible, length) then.
+
+        depth: also the samples' reads filtered by their median k-mer depth (depth_filter; the rule: INTEGRATION.md,
+        "`--depth-filter`: the rule") against each group's tables before they are freed -- a sample counted again from the
+        attempt that succeeded.  One band for every sample or a list of one per sample; a band is a depth.Band or its
+        text (resolved per sample from the row's estimates: depth.resolve) or a pair of integers (lo, hi).  The return
+        value then also carries (out uint8 device tensor, out_offs uint64[n], out_lens uint64[n], depth_rows
+        uint64[n, VK_DEPTH_NSTAT], bands = per sample (lo, hi, applied, reason)); sample i's kept text is out[out_offs[i]
+        .. + out_lens[i]), laid out as screen() lays its output out; a sample with a status gets no text and a zero row.
+        The spectrum and the sketch describe the text before the filter.  Synchronises."""
         torch = _torch()
         offs, lens = self._desc(offs, lens)
         n = len(offs)
@@ -1166,8 +1175,25 @@ class ImageEngine:
             sk_s, sk_m = self._sketch_args(*sketch)
             hashes = np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64)
             info = np.zeros((n, 2), dtype=np.uint64)
+        ret = lambda: (rows, status) + (() if sketch is None else (hashes, info)) + (() if depth is None else dp)   # noqa: E731
+        if depth is not None:
+            from . import depth as depth_rules
+            asked = list(depth) if isinstance(depth, list) else [depth] * n
+            if len(asked) != n:
+                raise ValueError("one band per sample")
+            asked = [depth_rules.parse_band(b) if isinstance(b, str) else b for b in asked]
+            rounded = (lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)
+            out_offs = np.zeros(n, dtype=np.uint64)
+            if n > 1:
+                out_offs[1:] = np.cumsum(rounded[:-1])
+            # (one text for all n samples, allocated once: a group writes its samples' regions)
+            out = torch.empty(int(rounded.sum()) + 16, dtype=torch.uint8, device=self.device)
+            out_lens = np.zeros(n, dtype=np.uint64)
+            depth_rows = np.zeros((n, _capi.VK_DEPTH_NSTAT), dtype=np.uint64)
+            bands = [None] * n
+            dp = (out, out_offs, out_lens, depth_rows, bands)
         if n == 0:
-            return (rows, status) if sketch is None else (rows, status, hashes, info)
+            return ret()
         if records is None:
             records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
         recs = np.ascontiguousarray(records, dtype=np.uint64)
@@ -1211,6 +1237,15 @@ class ImageEngine:
                 hashes[g], info[g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk_s, sk_m)
             rows[g] = d_rows.cpu().numpy().view(np.uint64)
             status[g] = d_status.cpu().numpy().astype(np.uint32)
+            if depth is not None:   # (while the tables lie there; the bands from the rows just read)
+                from . import spectrum as spectrum_rules
+                for i in group:
+                    b = asked[i]
+                    bands[i] = (depth_rules.resolve(b, spectrum_rules.estimate(rows[i], k, every))
+                                if isinstance(b, depth_rules.Band) else (int(b[0]), int(b[1]), True, None))
+                out_lens[g], depth_rows[g], _ = self.depth_filter(text, o, l, keys, counts, base, nsl, d_status,
+                                                                  [bands[i][0] for i in group], [bands[i][1] for i in group],
+                                                                  k, every, r, out, out_offs[g].copy())
             del keys, counts, ws
             # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
             # the slots -- a bounded loop over a status; at spectrum_slots(., 1) it cannot fill
@@ -1218,7 +1253,42 @@ class ImageEngine:
             for i in again:
                 want[i] = min(4 * want[i], most[i])
             todo = again + todo
-        return (rows, status) if sketch is None else (rows, status, hashes, info)
+        return ret()
+
+    def depth_filter(self, text, offs, lens, keys, counts, base, nslots, table_status, lo, hi, k, every, records, out, out_offs):
+        """Cleaned samples in HBM filtered record by record by their median k-mer depth in counting tables that lie in HBM
+        (vk_depth_device; the rule: INTEGRATION.md, "`--depth-filter`: the rule"): the samples, k, every and records as
+        spectrum() counted them, keys / counts / base / nslots / table_status (an int32 device tensor [n]) as
+        vk_spectrum_device left them, lo and hi the samples' bands (integers, both ends included).  Sample i's kept text
+        goes to out[out_offs[i] ..), a region of lens[i] rounded up to 16 bytes.  Returns (out_lens uint64[n], rows
+        uint64[n, VK_DEPTH_NSTAT], status uint32[n]).  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        base = np.ascontiguousarray(base, dtype=np.uint64)
+        nslots = np.ascontiguousarray(nslots, dtype=np.uint64)
+        out_offs = np.ascontiguousarray(out_offs, dtype=np.uint64)
+        lo = np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = np.ascontiguousarray(hi, dtype=np.uint32)
+        if not (len(recs) == len(base) == len(nslots) == len(out_offs) == len(lo) == len(hi) == n) or int(table_status.numel()) != n:
+            raise ValueError("one record count, base, slot count, status, band and output offset per sample")
+        if n and int((base + nslots).max()) > min(int(keys.numel()), int(counts.numel())):
+            raise ValueError("a sample's slots lie past the tables")
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, self.L.vk_depth_workspace_size(_u64(recs), n, _u64(lens), C.byref(ws_bytes)), "vk_depth_workspace_size")
+        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        d_lens = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        d_rows = torch.empty((max(n, 1), _capi.VK_DEPTH_NSTAT), dtype=torch.int64, device=self.device)
+        d_status = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        st = self.L.vk_depth_device(self.ctx, self._ptr(text), _u64(offs), _u64(lens), _u64(recs), n, int(k), int(every),
+                                    self._ptr(keys), self._ptr(counts), _u64(base), _u64(nslots), self._ptr(table_status),
+                                    _u32(lo), _u32(hi), self._ptr(out), _u64(out_offs), int(out.numel()), self._ptr(d_lens),
+                                    self._ptr(d_rows), self._ptr(d_status), self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_depth_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        return (d_lens[:n].cpu().numpy().astype(np.uint64), d_rows[:n].cpu().numpy().view(np.uint64),
+                d_status[:n].cpu().numpy().astype(np.uint32))
 
     @staticmethod
     def _sketch_args(s, m):

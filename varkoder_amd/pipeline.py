@@ -366,11 +366,16 @@ def clean_to_images(files, outdir, k=7, mapping_code="cgr", min_bp=50000, max_bp
             dev, offs, lens = eng.upload_files(batch, pool)
             if screen is not None:
                 dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [stem(f) for f in batch], stats, pool)
+            spec_rows = None
+            if spectrum is not None:   # (before the qc: with `--depth-filter` the qc and the ladder see what is kept)
+                spec_rows = spectrum.after(eng, dev, offs, lens)
+                if spectrum.band is not None:
+                    spec_rows, dev, offs, lens = spec_rows
             if qc_dir is not None:
                 for f, row in zip(batch, QcReport.after(eng, dev, offs, lens)):
                     QcReport(qc_dir).emit(stem(f), None, row, stats.setdefault(stem(f), OrderedDict()), pool, reports)
             if spectrum is not None:
-                for f, row in zip(batch, spectrum.after(eng, dev, offs, lens)):
+                for f, row in zip(batch, spec_rows):
                     spectrum.emit(stem(f), row, stats.setdefault(stem(f), OrderedDict()), pool, reports)
             t1, t2 = _ladder_images(eng, dev, offs, lens, [stem(f) for f in batch], batch, t0, sink, stats, seeds or {},
                                     splits=splits, no_image=no_image, min_bp=min_bp, max_bp=max_bp, is_query=is_query)
@@ -478,32 +483,53 @@ class Spectrum:
     every: int = 1
     sketch_size: object = None    # `--spectrum-sketch S`: also `DIR/<sample>.sketch.npy` and the json's "sketch" object
     sketch_min_count: int = 1     # `--spectrum-sketch-min-count M`
+    band: object = None           # `--depth-filter LO:HI` (depth.Band): the reads behind the spectrum are those whose median k-mer depth lies in it
 
     def after(self, eng, text, offs, lens):
         """The rows of cleaned samples in HBM.  A sample the count refuses (its framing) is reported and has a zero row.
-        With a sketch size every row comes as (row, the sketch's hashes, its eligible count)."""
-        if self.sketch_size is None:
-            rows, status = eng.spectrum(text, offs, lens, k=self.k, every=self.every)
-        else:
-            rows, status, hashes, info = eng.spectrum(text, offs, lens, k=self.k, every=self.every,
-                                                      sketch=(self.sketch_size, self.sketch_min_count))
+        With a sketch size every row comes as (row, the sketch's hashes, its eligible count).
+
+        With a band: (rows, text, offsets, lengths) -- the samples' reads filtered by depth (INTEGRATION.md,
+        "`--depth-filter`: the rule"), laid out as the input was, for everything behind the spectrum to see in place of
+        the input; every row then comes as (the row as without a band, the depth row, the sample's resolved band)."""
+        kw = {}
+        if self.sketch_size is not None:
+            kw["sketch"] = (self.sketch_size, self.sketch_min_count)
+        if self.band is not None:
+            kw["depth"] = self.band
+        rows, status, *rest = eng.spectrum(text, offs, lens, k=self.k, every=self.every, **kw)
         for j in np.flatnonzero(status):
             eprint("SPECTRUM FAIL: sample", int(j), "of its batch - status", int(status[j]))
-        if self.sketch_size is None:
+        if self.sketch_size is not None:
+            hashes, info, *rest = rest
+            rows = [(rows[j], hashes[j, :int(info[j, 1])].copy(), int(info[j, 0])) for j in range(len(rows))]
+        if self.band is None:
             return rows
-        return [(rows[j], hashes[j, :int(info[j, 1])].copy(), int(info[j, 0])) for j in range(len(rows))]
+        out, ooffs, olens, drows, bands = rest
+        for j, b in enumerate(bands):
+            if not status[j] and not b[2]:
+                eprint("DEPTH FILTER SKIPPED: sample", int(j), "of its batch -", b[3])
+        return [(rows[j], drows[j], bands[j]) for j in range(len(rows))], out, ooffs, olens
 
     def emit(self, sample, row, stats_row, pool, writes):
         """A sample's file queued on the pool (its future goes to `writes`) and its columns into stats_row (None: none)."""
-        from . import sketch, spectrum
-        sk = None
+        from . import depth, sketch, spectrum
+        sk = dp = None
+        if self.band is not None:
+            row, drow, band = row
+            dp = depth.report(drow, self.band, band[:2], band[2], band[3])
         if self.sketch_size is not None:
             row, hashes, eligible = row
             sk = sketch.meta(self.sketch_size, self.sketch_min_count, eligible, len(hashes))
             writes.append(pool.submit(sketch.write_sketch, self.dir, sample, hashes))
         if stats_row is not None:
             stats_row.update(spectrum.columns(row, self.k, self.every))
-        writes.append(pool.submit(spectrum.write_report, self.dir, sample, spectrum.report(row, self.k, self.every, sketch=sk)))
+            if dp is not None:
+                stats_row.update(depth.columns(drow))
+        obj = spectrum.report(row, self.k, self.every, sketch=sk)
+        if dp is not None:
+            obj["depth_filter"] = dp
+        writes.append(pool.submit(spectrum.write_report, self.dir, sample, obj))
 
 
 def _seed_groups(names, seeds):
@@ -923,14 +949,19 @@ def _clean_batches(eng, mine, pool, writes, stats, base_sd, opt, batch_bytes, ve
         srows = None
         if opt.screen is not None:   # the cleaned text screened where it lies: the files and the ladder see what is kept
             out, ooffs, olens, srows = opt.screen.apply(eng, out, ooffs, olens, [s for s, _ in batch], None, pool)
-        qc_after = {}
-        if opt.qc is not None:   # (behind the screen: what the ladder sees)
-            good = [j for j in range(len(batch)) if not status[j] and j not in failed]
-            qc_after = dict(zip(good, opt.qc.after(eng, out, ooffs[good], olens[good])))
         spec_rows = {}
         if opt.spectrum is not None:   # (behind the screen, once per sample: what the ladder sees)
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
-            spec_rows = dict(zip(good, opt.spectrum.after(eng, out, ooffs[good], olens[good])))
+            got = opt.spectrum.after(eng, out, ooffs[good], olens[good])
+            if opt.spectrum.band is not None:   # `--depth-filter`: the files, the qc and the ladder see what is kept
+                got, out, goffs, glens = got
+                ooffs, olens = np.zeros_like(ooffs), np.zeros_like(olens)   # (a sample that failed is not looked at again)
+                ooffs[good], olens[good] = goffs, glens
+            spec_rows = dict(zip(good, got))
+        qc_after = {}
+        if opt.qc is not None:   # (behind the screen and the depth filter: what the ladder sees)
+            good = [j for j in range(len(batch)) if not status[j] and j not in failed]
+            qc_after = dict(zip(good, opt.qc.after(eng, out, ooffs[good], olens[good])))
         packed = {}
         if clean_dir is not None and opt.gpu_gzip:   # the cleaned text compressed where it lies: only the files' bytes come back
             good = [j for j in range(len(batch)) if not status[j] and j not in failed]
@@ -1078,11 +1109,16 @@ def clean_to_query(samples, base_sd=None, max_bp=None, seeds=None, engine=None, 
             dev, offs, lens = eng.upload_files(files, pool)
             if screen is not None:
                 dev, offs, lens, _ = screen.apply(eng, dev, offs, lens, [s for s, _ in batch], None, pool)
+            spec_rows = None
+            if spectrum is not None:   # (before the qc: with `--depth-filter` the qc and the rung see what is kept)
+                spec_rows = spectrum.after(eng, dev, offs, lens)
+                if spectrum.band is not None:
+                    spec_rows, dev, offs, lens = spec_rows
             if qc_dir is not None:
                 for (s, _), row in zip(batch, QcReport.after(eng, dev, offs, lens)):
                     QcReport(qc_dir).emit(s, None, row, None, pool, reports)
             if spectrum is not None:
-                for (s, _), row in zip(batch, spectrum.after(eng, dev, offs, lens)):
+                for (s, _), row in zip(batch, spec_rows):
                     spectrum.emit(s, row, None, pool, reports)
             _query_rungs(eng, dev, offs, lens, [s for s, _ in batch], files, seeds or {}, max_bp, base_sd or {}, found)
         for w in reports:
