@@ -856,6 +856,12 @@ int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uin
  * and last piece of every wavefront's range), and about how many pieces there were.  Synchronises. */
 int vk_last_count_general(vk_ctx* ctx, uint64_t* general_pieces, uint64_t* pieces);
 
+/* Introspection (tests): the last vk_count_device call with k <= 7 ran as resident workgroups that own samples and pull
+ * their byte ranges (the default; VKIMG_K1_STATIC=1 keeps one workgroup per sample and part).  *helpers: how many
+ * workgroups may join a sample beside its owner; flushes[i], i < nsamples: how many workgroups added their histogram
+ * to sample i's row, between 1 and 1 + *helpers (all 0, like *helpers: the call was no such launch).  Synchronises. */
+int vk_last_count_pull(vk_ctx* ctx, uint32_t* helpers, uint32_t* flushes, uint32_t nsamples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,10 @@
 """A/B timing of experimental builds of the count kernel: python tools/k1_ab.py lib1.so lib2.so ...
 Each library runs in its own child process (one ctypes load per process).  Prints the K1 launch
 time for 1000 samples x 1M x 150 bp (--pool distinct samples, default 64; --k, --samples, --dist), first for the
-library in the tree with its default kernel and with VKIMG_K1_CLASSIC=1, then for every library named; the hash
-of the first 64 histograms shows whether the builds agree."""
+library in the tree with its default kernel and with VKIMG_K1_CLASSIC=1 (--only: not these two), then for every library
+named, in the order given (name a pair several times to alternate them); the hash of the first 64 histograms shows
+whether the builds agree.  A name may end in @classic, @static (VKIMG_K1_STATIC=1: the launch of one workgroup per sample
+and part) or @helpers=N (VKIMG_K1_HELPERS=N)."""
 import subprocess
 import sys
 
@@ -29,7 +31,7 @@ for _ in range(3):
     ts.append(time.perf_counter() - t0)
 h = hashlib.sha256(hist[:64].cpu().numpy().tobytes()).hexdigest()[:16]
 import os
-print(f"{sys.argv[1] + ('@classic' if os.environ.get('VKIMG_K1_CLASSIC') == '1' else ''):40s} k={k} dist={dist} pool={pool} K1 {min(ts)*1e3:8.2f} ms (min of 3; {[round(t*1e3,1) for t in ts]}) bad={int((status!=0).sum())} sha={h}", flush=True)
+print(f"{sys.argv[1] + os.environ.get('K1_AB_TAG', ''):40s} k={k} dist={dist} pool={pool} K1 {min(ts)*1e3:8.2f} ms (min of 3; {[round(t*1e3,1) for t in ts]}) bad={int((status!=0).sum())} sha={h}", flush=True)
 """
 
 if __name__ == "__main__":
@@ -45,11 +47,16 @@ if __name__ == "__main__":
         if a.startswith("--pool="): pool = int(a[7:])
     rc = 0
     import os
-    for lib in ["default", "default@classic"] + libs:
+    for lib in ([] if "--only" in sys.argv else ["default", "default@classic"]) + libs:
         env = dict(os.environ)
-        if lib.endswith("@classic"):  # the same library with VKIMG_K1_CLASSIC=1 (every byte through the heavy stage)
+        lib, _, tag = lib.partition("@")
+        env["K1_AB_TAG"] = "@" + tag if tag else ""
+        if tag == "classic":  # the same library with VKIMG_K1_CLASSIC=1 (every byte through the heavy stage)
             env["VKIMG_K1_CLASSIC"] = "1"
-            lib = lib[:-8]
+        elif tag == "static":
+            env["VKIMG_K1_STATIC"] = "1"
+        elif tag.startswith("helpers="):
+            env["VKIMG_K1_HELPERS"] = tag[8:]
         r = subprocess.run([sys.executable, "-c", CHILD, lib, str(k), str(samples), str(dist), str(pool)], env=env)
         rc |= r.returncode
     sys.exit(rc)

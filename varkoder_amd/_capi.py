@@ -48,7 +48,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_spectrum_workspace_size", "vk_spectrum_device",
            "vk_sketch_workspace_size", "vk_sketch_device", "vk_sketch_pairs_device",
            "vk_depth_workspace_size", "vk_depth_device",
-           "vk_dist_workspace_size", "vk_dist_device")
+           "vk_dist_workspace_size", "vk_dist_device", "vk_last_count_pull")
 
 _lib = None
 
@@ -159,6 +159,8 @@ def lib():
     L.vk_dist_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64]
     L.vk_last_count_general.argtypes = [vp, u64p, u64p]
     L.vk_last_count_launch.argtypes = [vp, u32p, u32p, u32p]
+    if hasattr(L, "vk_last_count_pull"):   # (tools/k1_ab.py also loads libraries built from older trees)
+        L.vk_last_count_pull.argtypes = [vp, u32p, u32p, C.c_uint32]
     L.vk_preprocess_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float, vp]
     L.vk_train_batch_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_float, C.c_float,
                                         C.c_uint32, u32p, u32p, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

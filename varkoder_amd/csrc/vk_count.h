@@ -1243,12 +1243,33 @@ __global__ __launch_bounds__(kCountThreads, 8) void vk_aside_kernel(const uint8_
 // INDEX: the launch also fills the read index of its samples (vk_ladder.h) -- every read's anchor, the bytes of all
 // sequence lines -- so that a ladder of subsamples needs no pass of its own for it: an anchor falls out of the line pass
 // (seq_span's s_raw), the sequence bytes out of the heavy stage's masks; the general path and vk_aside_kernel add theirs.
-template <int K, bool INDEX>
+//
+// PULL: the launch is as many workgroups as the device keeps resident, and who runs a byte range is settled while it
+// runs.  The ranges are those of the static launch -- range (part, wave) of a sample is its CHUNK part * kWaves + wave,
+// and writes the slots of wavephase, aside and aside_n that unit (sample, part), wave writes there -- but a workgroup
+// keeps ONE sample's histogram in LDS for as long as the sample has chunks, and each of its wavefronts pulls chunk
+// numbers from the sample's cursor (pull.words[2 + smp]: one returning atomic per chunk) until the cursor has passed the
+// sample's chunks: one zeroed histogram, one flush and two barriers per sample and workgroup instead of per kWaves
+// chunks, and no wavefront waits for another's range -- it takes another chunk.  A workgroup OWNS the samples it claims
+// from pull.words[0]; when none is left it HELPS: it draws tickets from pull.words[1] (`helpers` per sample, the samples
+// claimed last first, for they have the most left), joins a sample whose cursor still has chunks, and flushes with the
+// same atomics.  Nobody waits for anybody: a workgroup that comes late finds cursors and tickets spent and leaves, so
+// any number of resident workgroups counts the same sums.  pull.words[2 + nsamples + smp] counts the sample's flushes (at most 1 +
+// helpers).  The host zeroes the words before the launch.
+struct PullParams {
+    uint32_t* words;     // [0] samples claimed, [1] helper tickets drawn, then per sample: [2 + smp] chunks handed out,
+                         // [2 + nsamples + smp] histograms flushed (one array: one pointer to keep in scalar registers)
+    uint32_t helpers;    // tickets per sample
+};
+__host__ __device__ constexpr size_t pull_words(uint32_t nsamples) { return 2 + 2 * static_cast<size_t>(nsamples); }
+
+template <int K, bool INDEX, bool PULL = false>
 __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kernel(
     const uint8_t* __restrict__ fastq, const uint64_t* __restrict__ offs,
     const uint64_t* __restrict__ lens, uint32_t nsamples, uint32_t parts,
     uint32_t* __restrict__ hist_out, uint32_t* __restrict__ wavephase, int atomic_flush,
-    uint32_t* __restrict__ aside, uint32_t aside_cap, uint32_t* __restrict__ aside_n, IndexParams ip) {   // aside[grid * kWaves][aside_cap]: the waves' lists of lanes set aside; aside_n[grid * kWaves]: their lengths
+    uint32_t* __restrict__ aside, uint32_t aside_cap, uint32_t* __restrict__ aside_n, IndexParams ip, PullParams pull) {   // aside[grid * kWaves][aside_cap]: the waves' lists of lanes set aside; aside_n[grid * kWaves]: their lengths
+    static_assert(!(PULL && INDEX), "the index launch keeps its static split");
     constexpr uint32_t NCODE = 1u << (2 * K);
     static_assert(NCODE <= kMaxBins, "LDS histogram too large");
     // (one block, so that general_piece finds the exchange buffers behind the histogram it is handed)
@@ -1260,17 +1281,54 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
     uint32_t (&hist)[NCODE] = dlds.hist;
     uint4 (&xbuf)[kWaves][64] = dlds.xbuf;
 
-    const uint32_t unit = blockIdx.x;
-    const uint32_t smp = unit / parts;
-    const uint32_t part = unit % parts;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (The two loops below are PULL's; the static launch goes through each body once, and the bodies keep their indentation.
+    // Each loop has ONE way out, at its end, on a scalar: with a return and a break in their middle hipcc routed the exits
+    // through lane masks, as if the lanes left one by one.)
+    constexpr uint32_t kNoSample = 0xFFFFFFFFu;
+    auto add0 = [&](uint32_t* p, uint32_t v) __attribute__((always_inline)) {   // lane 0's returning atomic, for the whole wavefront
+        uint32_t r = 0;
+        if (lane == 0) r = atomicAdd(p, v);
+        return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(r)));
+    };
+    uint32_t smp = blockIdx.x / parts;
+    do {   // PULL: the samples this workgroup owns or helps with, a histogram each
+    if constexpr (PULL) {
+        // The next sample: one to own, then one to help with, kNoSample when the tickets are spent too.  Wave 0 asks (the whole
+        // wavefront: scalar branches) and leaves the answer in its own exchange buffer, idle between samples.
+        uint32_t* const word = reinterpret_cast<uint32_t*>(&xbuf[0][0]);
+        if (wave == 0) {
+            uint32_t got = add0(&pull.words[0], 1u);
+            if (got >= nsamples) {
+                got = kNoSample;
+                const uint64_t tickets = static_cast<uint64_t>(nsamples) * pull.helpers;
+                uint32_t t;
+                do {
+                    t = add0(&pull.words[1], 1u);
+                    if (t < tickets) {
+                        const uint32_t s = nsamples - 1u - t % nsamples;
+                        if (add0(&pull.words[2u + s], 0u) < parts * kWaves) got = s;   // (an atomic: the cursor as the device sees it now)
+                    }
+                } while (t < tickets && got == kNoSample);
+            }
+            if (lane == 0) *word = got;
+        }
+        __syncthreads();   // (also between the flush before and the zeroing below)
+        smp = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(*word)));
+    }
+    if (!PULL || smp != kNoSample) {
 
     for (uint32_t i = tid; i < NCODE; i += kCountThreads) hist[i] = 0u;
-    __syncthreads();
+    __syncthreads();   // (PULL: also every wave's read of the claim, before xbuf[0] carries granules again)
 
-    const WaveRange wr = wave_range(lens[smp], parts, part, wave);
+    uint32_t chunk = PULL ? add0(&pull.words[2u + smp], 1u) : 0u;   // PULL: the chunks this wavefront pulls
+    if (!PULL || chunk < parts * kWaves) do {
+    const uint32_t part = PULL ? chunk / kWaves : blockIdx.x % parts;
+    const int cwave = PULL ? static_cast<int>(chunk % kWaves) : wave;   // the chunk's wave of the static launch: its byte range and its slots
+    const uint32_t unit = smp * parts + part;
+    const WaveRange wr = wave_range(lens[smp], parts, part, cwave);
     uint32_t ph_start = 0, ph_end = 0, general_pieces = 0, aside_count = 0, anchors = 0;
     if (!wr.empty) {
         const uint32_t hist_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
@@ -1322,11 +1380,11 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
         bool hot = false;
         uint32_t tick = 0;    // calls of the low-complexity probe
         uint32_t ngeneral = 0;  // pieces that took the general path (reported in the wave's phase word, bits 8..31)
-        uint32_t* const alist = aside + (static_cast<uint64_t>(unit) * kWaves + static_cast<uint32_t>(wave)) * aside_cap;
+        uint32_t* const alist = aside + (static_cast<uint64_t>(unit) * kWaves + static_cast<uint32_t>(cwave)) * aside_cap;
         uint32_t naside = 0;    // entries in alist
         uint32_t aside63 = 0;   // lane 63 of the piece before was set aside (wave-uniform)
         // INDEX: the wave's segment of the sample's anchor list
-        uint32_t* const iseg = INDEX ? ip.anchors + uniform64(index_segment(ip, smp, w0, part, wave)) : nullptr;
+        uint32_t* const iseg = INDEX ? ip.anchors + uniform64(index_segment(ip, smp, w0, part, cwave)) : nullptr;
         const uint32_t icap = INDEX ? static_cast<uint32_t>(index_segment_cap(w1 - w0)) : 0u;
         uint32_t nanch = 0, nsite = 0;   // anchors stored; this lane's sequence bytes so far
         bool ifull = false;
@@ -1379,8 +1437,9 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
         VK_STAMP(st_prev);
 #endif
 #ifndef VK_DIAG_K1_NO_PACE
-        const uint32_t pace_at = npieces - (npieces >> 2);   // (>= 1: the first piece of a range of under four runs at 1 too)
-        __builtin_amdgcn_s_setprio(1);
+        // (PULL: no pacing -- a wavefront that is through its range takes the next chunk, nobody waits for it until the sample ends)
+        [[maybe_unused]] const uint32_t pace_at = npieces - (npieces >> 2);   // (>= 1: the first piece of a range of under four runs at 1 too)
+        if constexpr (!PULL) __builtin_amdgcn_s_setprio(1);
 #endif
         for (uint32_t it = 0; it < npieces; ++it) {
 #ifndef VK_DIAG_K1_NO_PACE
@@ -1389,7 +1448,7 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
             // (the inflate chunk decoder, vk_inflate.h, showed the effect at its largest).  The first three quarters of a range
             // run at priority 1, the last at 0: who is behind passes who is ahead.  -1 % (60.7 -> 60.0 ms; four levels the same,
             // the levels the other way round nothing: profiles/ab/r06_inflate_pacing.txt).
-            if (it == pace_at) __builtin_amdgcn_s_setprio(0);
+            if (!PULL && it == pace_at) __builtin_amdgcn_s_setprio(0);
 #endif
 #ifdef VK_STAMPS
             VK_STAMP(st_t0);
@@ -1613,7 +1672,7 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
         // kernel of its own -- the arrangement that made the K = 5 build lose the loop's own counts.  Not shipped.
         if constexpr (!INDEX) {
             __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the list's stores
-            const uint32_t* list = aside + static_cast<uint64_t>(unit * kWaves + static_cast<uint32_t>(wave)) * aside_cap;
+            const uint32_t* list = aside + static_cast<uint64_t>(unit * kWaves + static_cast<uint32_t>(cwave)) * aside_cap;
             const uint32_t ulane = static_cast<uint32_t>(lane);
             const uint32_t ent = ulane / 3u, j = ulane - 3u * ent;
             for (uint32_t at = 0; at < naside; at += kSetAsideBatch) {
@@ -1667,10 +1726,12 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
 #endif
     }
     if (lane == 0) {
-        wavephase[unit * kWaves + wave] = wr.empty ? 0x80u : (0x40u | ph_start | (ph_end << 2) | (general_pieces << 8));
-        aside_n[unit * kWaves + wave] = aside_count;   // (vk_aside_kernel counts the listed lanes)
-        if constexpr (INDEX) ip.count[unit * kWaves + wave] = anchors;
+        wavephase[unit * kWaves + cwave] = wr.empty ? 0x80u : (0x40u | ph_start | (ph_end << 2) | (general_pieces << 8));
+        aside_n[unit * kWaves + cwave] = aside_count;   // (vk_aside_kernel counts the listed lanes)
+        if constexpr (INDEX) ip.count[unit * kWaves + cwave] = anchors;
     }
+    if constexpr (PULL) chunk = add0(&pull.words[2u + smp], 1u);
+    } while (PULL && chunk < parts * kWaves);   // (the chunks of this wavefront)
 
     __syncthreads();
     uint32_t* out = hist_out + static_cast<uint64_t>(smp) * NCODE;
@@ -1682,6 +1743,10 @@ __global__ __launch_bounds__(kCountThreads, VK_K1_OCC) void vk_count_dense_kerne
             out[code] = v;
         }
     }
+    if constexpr (PULL)
+        if (tid == 0) atomicAdd(&pull.words[2u + nsamples + smp], 1u);
+    }
+    } while (PULL && smp != kNoSample);   // (the samples of this workgroup)
 }
 
 // ---- the packed sequence stream (written by vk_pack_kernel, vk_pack.h) --------------------------------

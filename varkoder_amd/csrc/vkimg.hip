@@ -57,6 +57,7 @@
 
 #include "vk_count.h"
 #include "vk_pack.h"
+#include "vk_countplan.h"
 #include "vk_ladder.h"
 #include "vk_image.h"
 #include "vk_inflate.h"
@@ -183,6 +184,11 @@ struct vk_ctx {
     uint32_t spectrum_tile = 0;    // VKIMG_SPECTRUM_TILE=n: the same for the spectrum's count kernel
     uint32_t spectrum_merge = kSpMergeDefault;   // VKIMG_SPECTRUM_MERGE=0|1|2: how the count kernel merges equal keys of a wave instruction (SpParams::merge; tools/spectrum_time.py)
     uint32_t depth_merge = kDpMergeDefault;   // VKIMG_DEPTH_MERGE=0|1: how the depth filter's match kernel adds to its LDS histogram (DpParams::merge; tools/depth_time.py)
+    uint32_t* d_pull = nullptr;    // k <= 7, the launch whose workgroups pull their work: its words (vk_count.h, PullParams; ct_pull)
+    size_t pull_cap = 0;
+    bool k1_static = false;        // VKIMG_K1_STATIC=1: the k <= 7 count as one workgroup per (sample, part), each wavefront its fixed range, instead of resident workgroups that pull chunks (tests, A/B timing)
+    uint32_t k1_helpers = 0xFFFFFFFFu;   // VKIMG_K1_HELPERS=n: workgroups that may join a sample beside its owner, in place of pull_plan's figure; samples of one part then pull as well (tests, A/B timing)
+    uint32_t last_helpers = 0, last_pull_samples = 0;   // of the last count call: its bound on helpers and its samples (0: no pulling launch; vk_last_count_pull)
     bool k1_classic = false;       // VKIMG_K1_CLASSIC=1: k <= 7 through vk_count_kernel (every byte through the heavy stage) instead of vk_count_dense_kernel (tests, A/B timing)
 };
 
@@ -355,10 +361,36 @@ int aside_lists(vk_ctx* ctx, const CtPlan& p, size_t nwaves, uint32_t* cap_out, 
     return VK_OK;
 }
 
+// The words of a launch whose workgroups pull their work (vk_count.h, PullParams), zeroed; its grid in *grid.  The count
+// kernels keep two workgroups of kCountThreads per CU resident.
+int ct_pull(vk_ctx* ctx, const CtPlan& p, PullParams* pp, uint32_t* grid) {
+    const PullPlan pl = pull_plan(2u * static_cast<uint32_t>(ctx->num_cus), p.nsamples, p.parts, ctx->k1_helpers);
+    *grid = pl.grid;
+    if (pl.grid == 0) return VK_OK;   // (the rule keeps the static launch for this batch)
+    int rc = ws_carve(ctx, &ctx->d_pull, &ctx->pull_cap, [&](WsTake& take) { take(pp->words, pull_words(p.nsamples)); });
+    if (rc) return rc;
+    VK_HIP(ctx, hipMemsetAsync(pp->words, 0, pull_words(p.nsamples) * sizeof(uint32_t), ctx->stream));
+    pp->helpers = pl.helpers;
+    ctx->last_helpers = pl.helpers;
+    ctx->last_pull_samples = p.nsamples;
+    return VK_OK;
+}
+
 template <int K>
 int launch_count(vk_ctx* ctx, const CtPlan& p, uint32_t* d_hist, const SubParams* sub, const IndexParams* index = nullptr) {
-    const uint32_t nsamples = p.nsamples, parts = p.parts, grid = nsamples * parts;
-    const int atomic_flush = parts > 1 ? 1 : 0;
+    const uint32_t nsamples = p.nsamples, parts = p.parts;
+    bool pulling = !sub && !index && !ctx->k1_classic && !ctx->k1_static;
+    uint32_t grid = nsamples * parts;
+    ctx->last_pull_samples = 0;
+    PullParams pp{};
+    if (pulling) {
+        const int rc = ct_pull(ctx, p, &pp, &grid);
+        if (rc) return rc;
+        pulling = grid != 0;
+        if (!pulling) grid = nsamples * parts;
+    }
+    // (pulling: owner and helpers flush into the same zeroed row; a sample nobody may help is stored by its owner alone)
+    const int atomic_flush = (pulling ? pp.helpers > 0 : parts > 1) ? 1 : 0;
     if (atomic_flush)
         VK_HIP(ctx, hipMemsetAsync(d_hist, 0, static_cast<size_t>(nsamples) * (1u << (2 * K)) * sizeof(uint32_t),
                                    ctx->stream));
@@ -383,14 +415,20 @@ int launch_count(vk_ctx* ctx, const CtPlan& p, uint32_t* d_hist, const SubParams
         if (index) {   // the count and the read index of the samples in one pass (vk_count_index_device)
             hipLaunchKernelGGL((vk_count_dense_kernel<K, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
                                p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
-                               cap, d_aside_n, *index);
+                               cap, d_aside_n, *index, PullParams{});
             VK_HIP(ctx, hipGetLastError());
             hipLaunchKernelGGL((vk_aside_kernel<K, true>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, p.fq,
                                p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_aside, cap, d_aside_n, *index, upb);
         } else {
-            hipLaunchKernelGGL((vk_count_dense_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
-                               p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
-                               cap, d_aside_n, IndexParams{});
+            if (pulling) {   // resident workgroups that own samples and pull their chunks (vk_count.h, PullParams)
+                hipLaunchKernelGGL((vk_count_dense_kernel<K, false, true>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                                   p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
+                                   cap, d_aside_n, IndexParams{}, pp);
+            } else {
+                hipLaunchKernelGGL((vk_count_dense_kernel<K, false>), dim3(grid), dim3(kCountThreads), 0, ctx->stream, p.fq,
+                                   p.d_offs, p.d_lens, nsamples, parts, d_hist, ctx->d_wavephase, atomic_flush, ctx->d_aside,
+                                   cap, d_aside_n, IndexParams{}, PullParams{});
+            }
             VK_HIP(ctx, hipGetLastError());
 #ifndef VK_DIAG_ASIDE_INLINE   // (diagnostic: the count kernel counts its own lists, vk_count.h)
             hipLaunchKernelGGL((vk_aside_kernel<K, false>), dim3(nsamples * ablocks), dim3(kCountThreads), 0, ctx->stream, p.fq,
@@ -674,6 +712,8 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     env_uint("VKIMG_CLEAN_HASH_BITS", &hash_bits);
     ctx->clean_hash_bits = hash_bits >= 1 && hash_bits <= 64 ? static_cast<uint32_t>(hash_bits) : 64u;
     ctx->k1_classic = env_flag("VKIMG_K1_CLASSIC");
+    ctx->k1_static = env_flag("VKIMG_K1_STATIC");
+    env_uint("VKIMG_K1_HELPERS", &ctx->k1_helpers);
     env_uint("VKIMG_FASTA_UNIT_BYTES", &ctx->fasta_unit_bytes);
     if (ctx->fasta_unit_bytes) {
         ctx->fasta_unit_bytes = ctx->fasta_unit_bytes / kFaLaneBytes * kFaLaneBytes;
@@ -726,7 +766,7 @@ void vk_ctx_destroy(vk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 10; ++k)
         if (ctx->d_pix[k]) (void)hipFree(ctx->d_pix[k]);
-    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin, ctx->d_bamws, ctx->d_bamgws};
+    void* ptrs[] = {ctx->d_desc, ctx->d_wavephase, ctx->d_scratch, ctx->d_spill, ctx->d_stage, ctx->d_hist1, ctx->d_status1, ctx->d_img1, ctx->d_sub, ctx->d_gzjobs, ctx->d_gzmeta, ctx->d_gzsym, ctx->d_gzwin, ctx->d_gzcrc, ctx->d_synth, ctx->d_synth_offs, ctx->d_aside, ctx->d_pull, ctx->d_index, ctx->d_walk, ctx->d_clines, ctx->d_cladapt, ctx->d_cldetect, ctx->d_fasta, ctx->d_fawin, ctx->d_bamws, ctx->d_bamgws};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
@@ -1644,6 +1684,21 @@ int vk_last_count_general(vk_ctx* ctx, uint64_t* general_pieces, uint64_t* piece
     *general_pieces = g;
     // every wave's range starts one 64-byte block early and ends with a partial piece: about one piece per wave on top
     *pieces = (ctx->last_bytes + kPiece - 1) / kPiece + active;
+    return VK_OK;
+}
+
+int vk_last_count_pull(vk_ctx* ctx, uint32_t* helpers, uint32_t* flushes, uint32_t nsamples) {
+    if (!ctx || !helpers || (nsamples && !flushes)) return VK_EINVAL;
+    *helpers = 0;
+    for (uint32_t i = 0; i < nsamples; ++i) flushes[i] = 0;
+    if (ctx->last_pull_samples == 0) return VK_OK;
+    if (nsamples > ctx->last_pull_samples) return VK_EINVAL;
+    *helpers = ctx->last_helpers;
+    if (nsamples == 0) return VK_OK;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t* d_flushes = ctx->d_pull + 2 + ctx->last_pull_samples;   // (vk_count.h, PullParams)
+    VK_HIP(ctx, hipMemcpyAsync(flushes, d_flushes, nsamples * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }
 

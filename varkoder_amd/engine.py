@@ -1551,6 +1551,12 @@ class ImageEngine:
         self.L.vk_last_count_launch(self.ctx, C.byref(g), C.byref(b), C.byref(l))
         return {"grid": g.value, "block": b.value, "lds_bytes": l.value}
 
+    def last_count_pull(self, nsamples):
+        """(helpers allowed per sample, flushes per sample) of the last k <= 7 count; every flush count 0: it was no pulling launch"""
+        h, f = C.c_uint32(), (C.c_uint32 * max(nsamples, 1))()
+        _capi.check(self.ctx, self.L.vk_last_count_pull(self.ctx, C.byref(h), f, nsamples), "vk_last_count_pull")
+        return h.value, list(f)[:nsamples]
+
     def last_count_general(self):
         """(pieces of the last k <= 7 count that took the general path, pieces in all)"""
         g, n = C.c_uint64(), C.c_uint64()
