@@ -748,6 +748,37 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
                        uint32_t* d_counts, const uint64_t* slot_base, const uint64_t* nslots, uint64_t* d_rows,
                        uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
+/* `image / query --from-fasta --genome-spectrum`: the k-mer spectrum of assemblies, counted straight from FASTA text in
+ * HBM into tables of vk_spectrum_device's layout, so that vk_sketch_device takes them as they stand.  The rule is this
+ * project's ("`--genome-spectrum`: the rule", and tests/fasta_spectrum_ref.py).
+ *
+ * The batch is laid out as for vk_count_fasta_device: sample i is d_fasta[offsets[i] .. + lengths[i]) (offsets[i] a
+ * multiple of 16, the buffer readable up to each sample's 16-byte rounded end); lines, header lines and records are read
+ * exactly as there.  Bases, windows and keys are the screen's (vk_screen_build_device): ACGT of either case, every window
+ * of k (16 .. 31) unbroken bases -- across line ends, never across a header line or any other byte -- gives a key, the
+ * smaller of the window and its reverse complement as 2k-bit integers.  A key is taken as in vk_spectrum_device, and every
+ * occurrence of a taken key counts.  Tables (d_keys, d_counts, slot_base, nslots) as for vk_spectrum_device: the caller
+ * allocates them, the call initialises them.
+ *
+ * d_rows[nsamples][VK_SPEC_NSTAT], u64, in vk_spectrum_device's layout:
+ *     0 records (header lines)   1 bases (vk_count_fasta_device's d_bases: joined sequence bytes of every class)
+ *     2 windows   3 taken_windows   4 distinct (taken keys)   VK_SPEC_HIST  256: hist[c - 1] as there
+ * A multiplicity is a copy number here, not a depth.
+ * d_status[nsamples]: VK_ST_BAD_START for a non-empty sample that does not begin with '>', VK_SPEC_TABLE_FULL when a key
+ * of the sample found no slot (the probe ends after nslots[i] slots; it never spins).  A sample with a status gets an
+ * all-zero row and disturbs no other; an empty sample has status 0 and a zero row.  Results are integers and do not depend
+ * on the launch.
+ * d_ws: caller-allocated device workspace of vk_spectrum_fasta_workspace_size bytes (same lengths).  VK_EINVAL, before
+ * anything is launched, for a null pointer, nsamples 0, k outside 16 .. 31, every 0, an nslots[i] that is no power of two
+ * or below 1,024, an unaligned offset, a sample of more than 2^33 bytes (a multiplicity is 32-bit) or a workspace that is
+ * too small.  The call allocates no device memory and does not synchronise: it is enqueued on the context's stream (its
+ * host arrays have been read when it returns).  VKIMG_FASTA_UNIT_BYTES shrinks the units as in the other FASTA calls. */
+int vk_spectrum_fasta_workspace_size(const uint64_t* lengths, uint32_t nsamples, uint64_t* bytes);
+int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
+                             uint32_t nsamples, int k, uint32_t every, uint64_t* d_keys, uint32_t* d_counts,
+                             const uint64_t* slot_base, const uint64_t* nslots, uint64_t* d_rows, uint32_t* d_status,
+                             void* d_ws, uint64_t ws_bytes);
+
 /* `image / query --spectrum-sketch` and `distance`: a bottom-s MinHash sketch of each sample, taken from its spectrum
  * table while that lies in HBM, and every pair of sketches compared.  The rule is this project's (INTEGRATION.md,
  * "`--spectrum-sketch` and `distance`: the rule", and tests/sketch_ref.py); the reference has no such command.

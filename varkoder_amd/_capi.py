@@ -46,6 +46,7 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_bam_groups_workspace_size", "vk_last_bam_groups", "vk_screen_build_workspace_size", "vk_screen_build_device",
            "vk_screen_workspace_size", "vk_screen_device", "vk_qc_workspace_size", "vk_qc_device",
            "vk_spectrum_workspace_size", "vk_spectrum_device",
+           "vk_spectrum_fasta_workspace_size", "vk_spectrum_fasta_device",
            "vk_sketch_workspace_size", "vk_sketch_device", "vk_sketch_pairs_device",
            "vk_depth_workspace_size", "vk_depth_device",
            "vk_dist_workspace_size", "vk_dist_device", "vk_last_count_pull")
@@ -149,6 +150,9 @@ def lib():
     L.vk_spectrum_workspace_size.argtypes = [u64p, C.c_uint32, u64p, u64p]
     L.vk_spectrum_device.argtypes = [vp, vp, u64p, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, vp, vp, u64p, u64p, vp, vp, vp,
                                      C.c_uint64]
+    L.vk_spectrum_fasta_workspace_size.argtypes = [u64p, C.c_uint32, u64p]
+    L.vk_spectrum_fasta_device.argtypes = [vp, vp, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, vp, vp, u64p, u64p, vp, vp, vp,
+                                           C.c_uint64]
     L.vk_sketch_workspace_size.argtypes = [u64p, C.c_uint32, C.c_uint32, u64p]
     L.vk_sketch_device.argtypes = [vp, vp, vp, u64p, u64p, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64]
     L.vk_sketch_pairs_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, vp, vp]

@@ -270,7 +270,8 @@ def setup_parser():
     m.add_argument("-v", "--verbose", action="store_true", default=False)
     d = sub.add_parser("distance", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                        help="Genomic distances between samples from the sketches that `--kmer-spectrum DIR "
-                            "--spectrum-sketch S` wrote, every pair compared on the GPU (not in the reference; rule and "
+                            "--spectrum-sketch S` (reads) and `--from-fasta --genome-spectrum DIR --spectrum-sketch S` "
+                            "(assemblies) wrote, every pair compared on the GPU (not in the reference; rule and "
                             "limits: INTEGRATION.md, \"`--spectrum-sketch` and `distance`: the rule\").")
     d.add_argument("input", help="path to the folder with the samples' .spectrum.json and .sketch.npy files (SPECTRA).")
     d.add_argument("outdir", help="path to the folder where distances.csv will be written (OUT).")
@@ -351,13 +352,19 @@ def add_spectrum_flags(p):
                         "the genome's distinct k-mers, the error rate and the share of high-copy k-mers, and add their "
                         "columns to stats.csv (--from-raw, --from-bam, --from-clean; query's cleaned reads; rule and limits: "
                         "INTEGRATION.md, \"`--kmer-spectrum`: the rule\")")
+    p.add_argument("--genome-spectrum", default=argparse.SUPPRESS, metavar="DIR",   # (absent = nothing is counted)
+                   help="with --from-fasta (whole files): write DIR/<sample>.spectrum.json, the k-mer spectrum of the "
+                        "assembly counted on the GPU from the FASTA text the image is counted from -- distinct k-mers, "
+                        "copy numbers -- with \"source\": \"assembly\"; with --spectrum-sketch also the sketch that "
+                        "`distance --against DIR` compares skims with (not in the reference; rule: INTEGRATION.md, "
+                        "\"`--genome-spectrum`: the rule\")")
     p.add_argument("--spectrum-k", type=int, default=argparse.SUPPRESS, metavar="K",
-                   help=f"with --kmer-spectrum: the k-mer size, {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX} ({SPECTRUM_K_DEFAULT} when absent)")
+                   help=f"with --kmer-spectrum or --genome-spectrum: the k-mer size, {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX} ({SPECTRUM_K_DEFAULT} when absent)")
     p.add_argument("--spectrum-every", type=int, default=argparse.SUPPRESS, metavar="M",
-                   help="with --kmer-spectrum: count the k-mers whose hash is a multiple of M, a 1/M sample of the spectrum "
+                   help="with --kmer-spectrum or --genome-spectrum: count the k-mers whose hash is a multiple of M, a 1/M sample of the spectrum "
                         "in a table M times smaller (1 when absent: every k-mer, exact)")
     p.add_argument("--spectrum-sketch", type=int, default=argparse.SUPPRESS, metavar="S",
-                   help=f"with --kmer-spectrum: also write DIR/<sample>.sketch.npy, the S ({SKETCH_MIN} to {SKETCH_MAX}) smallest "
+                   help=f"with --kmer-spectrum or --genome-spectrum: also write DIR/<sample>.sketch.npy, the S ({SKETCH_MIN} to {SKETCH_MAX}) smallest "
                         "hashes of the sample's distinct k-mers, taken on the GPU from the table the spectrum was counted "
                         "in, and a \"sketch\" object in its .spectrum.json: what `distance` compares")
     p.add_argument("--spectrum-sketch-min-count", type=int, default=argparse.SUPPRESS, metavar="M",
@@ -371,6 +378,15 @@ def add_spectrum_flags(p):
                         "the sample's estimated k-mer coverage (3x:).  The sample's .spectrum.json gains a \"depth_filter\" "
                         "object with the histogram of the reads' median depths (rule: INTEGRATION.md, \"`--depth-filter`: "
                         "the rule\")")
+
+
+def genome_spectrum_options(args):
+    """pipeline.GenomeSpectrum of `--genome-spectrum`, None without it."""
+    if not hasattr(args, "genome_spectrum"):
+        return None
+    from .pipeline import GenomeSpectrum
+    return GenomeSpectrum(Path(args.genome_spectrum), getattr(args, "spectrum_k", SPECTRUM_K_DEFAULT),
+                          getattr(args, "spectrum_every", 1), getattr(args, "spectrum_sketch", None))
 
 
 def spectrum_options(args):
@@ -542,7 +558,26 @@ def parse_args(argv=None):
                            ("spectrum_sketch_min_count", "--spectrum-sketch-min-count"),
                            ("depth_filter", "--depth-filter")):
             if hasattr(args, name) and not hasattr(args, "kmer_spectrum"):
-                parser.error(f"{flag}: only with --kmer-spectrum")
+                if not hasattr(args, "genome_spectrum"):
+                    parser.error(f"{flag}: only with --kmer-spectrum" +
+                                 (" or --genome-spectrum" if name in ("spectrum_k", "spectrum_every", "spectrum_sketch") else ""))
+                if name in ("spectrum_sketch_min_count", "depth_filter"):
+                    parser.error(f"{flag}: not with --genome-spectrum (an assembly has no error k-mers to threshold and no depth)")
+        if hasattr(args, "genome_spectrum"):
+            # only where an assembly's whole text lies in HBM
+            if hasattr(args, "kmer_spectrum"):
+                parser.error("--genome-spectrum: not with --kmer-spectrum (one counts assemblies, the other reads)")
+            if not getattr(args, "from_fasta", False):
+                parser.error("--genome-spectrum: only with --from-fasta (reads are counted with --kmer-spectrum)")
+            for name, flag in (("fragments", "--fragments"), ("per_record", "--per-record"), ("windows", "--windows")):
+                if getattr(args, name, False):
+                    parser.error(f"--genome-spectrum: not with {flag} (the spectrum is the whole file's)")
+            if hasattr(args, "spectrum_k") and not SPECTRUM_K_MIN <= args.spectrum_k <= SPECTRUM_K_MAX:
+                parser.error(f"--spectrum-k: {SPECTRUM_K_MIN} to {SPECTRUM_K_MAX}")
+            if hasattr(args, "spectrum_every") and args.spectrum_every < 1:
+                parser.error("--spectrum-every: at least 1")
+            if hasattr(args, "spectrum_sketch") and not SKETCH_MIN <= args.spectrum_sketch <= SKETCH_MAX:
+                parser.error(f"--spectrum-sketch: {SKETCH_MIN} to {SKETCH_MAX}")
         if hasattr(args, "kmer_spectrum"):
             # only where cleaned reads lie in HBM as FASTQ text whole
             if getattr(args, "from_fasta", False):
@@ -770,7 +805,7 @@ def run_query(args):
                     record_opts = dict(origin=origin, **window_options(args))
                 found = fasta_to_query([(s, inputs[i]) for i, s in wanted], engine=eng, k=args.kmer_size,
                                        mapping_code=args.kmer_mapping, io_threads=io_threads_per_rank(args.n_threads),
-                                       **record_opts)
+                                       genome=genome_spectrum_options(args), **record_opts)
                 if record_opts:   # a row per record (or window), in the order of the files and of the records within each
                     of_file = {s: [] for _, s in wanted}
                     for rs in found:
@@ -1002,7 +1037,8 @@ def run_image_from_fasta(args, outdir, rank, world, local_rank):
         failpoint(rank)
         per_sample = fasta_to_images(files, outdir, weights=weights, k=args.kmer_size, mapping_code=args.kmer_mapping,
                                      labels=labels, device=local_rank, rank=rank, world=world,
-                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False), **ladder)
+                                     io_threads=io_threads_per_rank(args.n_threads), verbose=args.verbose, gpu_png=getattr(args, "gpu_png", False),
+                                     genome=genome_spectrum_options(args), **ladder)
         for v in per_sample.values():
             v["base_frequencies_sd"] = 0   # (no cleaning report: the flag is False, as for any sample without one)
     except Exception as e:   # noqa: BLE001 -- reported by finish_image_job, once every rank is past its collectives

@@ -34,6 +34,7 @@
 //   vk_dist_*_kernel (vk_dist.h): exact distances between images and nearest neighbours (`compare`): centred i8 rows, tiles on the i8 matrix cores, a workgroup's selection per row.
 //   vk_qc_*_kernel (vk_qc.h): quality profiles of FASTQ streams (`--qc-report`): wave per record, lanes on cycles, counters in LDS merged per workgroup.
 //   vk_sp_*_kernel (vk_spectrum.h): the k-mer spectrum of cleaned reads (`--kmer-spectrum`): wave per record, scattered atomics into a counting table in HBM, its histogram.
+//   vk_fs_count_kernel (vk_fasta_spectrum.h): the k-mer spectrum of assemblies (`--genome-spectrum`): the same tables filled straight from FASTA text, lane per 64 bytes, windows rolled from registers.
 //   vk_sk_*_kernel (vk_sketch.h): bottom-s MinHash sketches from the spectrum's tables (`--spectrum-sketch`: radix select, compaction, LDS runs, merge path) and all pairs of sketches compared (`distance`: a wavefront per pair).
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
@@ -78,6 +79,7 @@
 #include "vk_bamplan.h"
 #include "vk_screen.h"
 #include "vk_spectrum.h"
+#include "vk_fasta_spectrum.h"
 #include "vk_sketch.h"
 #include "vk_depth.h"
 #include "vk_qc.h"
@@ -3522,6 +3524,93 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
                          ctx->spectrum_tile ? ctx->spectrum_tile : kScMaxTile, ctx->spectrum_merge};
         hipLaunchKernelGGL(vk_sp_count_kernel, dim3(static_cast<uint32_t>(nrblocks)), dim3(kClThreads), 0, ctx->stream, text, L.rec_base,
                            nsamples, nrec, L.c.recs, d_status, P, rows);
+    }
+    hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
+                       d_counts, d_status, rows);
+    hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- the k-mer spectrum of assemblies, from FASTA text (vk_fasta_spectrum.h) ------
+
+namespace {
+
+// the pieces of a vk_spectrum_fasta_device workspace: the FASTA plan's descriptors and header state (sized for the smallest
+// unit VKIMG_FASTA_UNIT_BYTES allows), then the samples' tables
+struct FsLayout {
+    uint64_t* meta;
+    uint32_t *ukey, *carry;
+    uint64_t *block_base, *slot_base, *nslots;
+    size_t total;
+};
+
+FsLayout fs_layout(void* d_ws, const uint64_t* lengths, uint32_t nsamples) {
+    FsLayout L{};
+    uint64_t nunits = 0;
+    for (uint32_t i = 0; i < nsamples; ++i) nunits += (lengths[i] + kFaLaneBytes - 1) / kFaLaneBytes;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.meta, 4ull * nsamples + 2);
+    take(L.ukey, nunits + 1);
+    take(L.carry, nunits + 1);
+    take(L.block_base, nsamples + 1ull);
+    take(L.slot_base, nsamples);
+    take(L.nslots, nsamples);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_spectrum_fasta_workspace_size(const uint64_t* lengths, uint32_t nsamples, uint64_t* bytes) {
+    if (!bytes || (nsamples && !lengths)) return VK_EINVAL;
+    *bytes = fs_layout(nullptr, lengths, nsamples).total;
+    return VK_OK;
+}
+
+int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
+                             int k, uint32_t every, uint64_t* d_keys, uint32_t* d_counts, const uint64_t* slot_base,
+                             const uint64_t* nslots, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || nsamples == 0 || !d_fasta || !offsets || !lengths || !d_keys || !d_counts || !slot_base || !nslots || !d_rows ||
+        !d_status || !d_ws)
+        return VK_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
+    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
+    std::vector<uint64_t> block_base(nsamples + 1ull, 0);
+    for (uint32_t i = 0; i < nsamples; ++i) {
+        // (a sample of more than 2^33 bytes: a multiplicity is 32-bit)
+        if (offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i])) return VK_EINVAL;
+        block_base[i + 1] = block_base[i] + (nslots[i] + kSpSlotsPerBlock - 1) / kSpSlotsPerBlock;
+    }
+    if (block_base[nsamples] >= (1ull << 31)) return VK_EINVAL;
+    const FsLayout L = fs_layout(d_ws, lengths, nsamples);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    FaPlan pl;
+    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    if (rc) return rc;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const auto* text = static_cast<const uint8_t*>(d_fasta);
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kSpNstat * sizeof(uint64_t), ctx->stream));
+    const FaMeta m = pl.on_device(L.meta);
+    rc = fa_header_state(ctx, text, pl, m, L.ukey, L.carry, d_status);
+    if (rc) return rc;
+    const dim3 tgrid(static_cast<uint32_t>(block_base[nsamples]));
+    auto* rows = reinterpret_cast<unsigned long long*>(d_rows);
+    hipLaunchKernelGGL(vk_sp_init_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots, d_keys,
+                       d_counts);
+    if (pl.nwg) {
+        const SpParams P{d_keys, d_counts, L.slot_base, L.nslots, static_cast<uint32_t>(k), every, 0u, 0u};
+        hipLaunchKernelGGL(vk_fs_count_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, L.carry, P,
+                           d_status, rows);
     }
     hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
                        d_counts, d_status, rows);

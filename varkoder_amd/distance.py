@@ -3,7 +3,8 @@ compares samples by their k-mers; the rule is this project's ("`
 rule").
 
 The samples are the `<sample>.spectrum.json` files of a folder that carry a `"sketch"` object, each with its
-`<sample>.sketch.npy` (`image / query --kmer-spectrum DIR --spectrum-sketch S`).  One call (ImageEngine.sketch_pairs:
+`<sample>.sketch.npy` (`image / query --kmer-spectrum DIR --spectrum-sketch S` for reads, `--from-fasta --genome-spectrum DIR
+--spectrum-sketch S` for assemblies).  One call (ImageEngine.sketch_pairs:
 vk_sketch_pairs_device, csrc/vk_sketch.h) compares every query sketch with every reference sketch; the distances
 (sketch.py) and the ranking are computed on the host from its integers.  There is no CPU path for the comparison.
 
@@ -56,15 +57,33 @@ class SketchSet:
         return tuple(rep[x] if x in ("k", "every") else rep["sketch"][x] for x in SAME)
 
 
+def is_assembly(rep):
+    """A report of `--genome-spectrum`: its sketch holds every k-mer of an assembly, whatever reads were thresholded at."""
+    return rep.get("source") == "assembly"
+
+
 def check_comparable(sets):
-    """Sketches compare only when k, every, size, min_count, hash and version agree: the first two files that differ are named."""
+    """Sketches compare only when k, every, size, hash and version agree everywhere and min_count among the samples of
+    reads (an assembly's report is exempt from that one): the first two files that differ are named."""
+    at = SAME.index("min_count")
     first = (sets[0].paths[0], sets[0].signature(0))
+    first_reads = None   # the first sample of reads: what min_count is held against
     for st in sets:
         for i, path in enumerate(st.paths):
             sig = st.signature(i)
-            if sig != first[1]:
-                what = ", ".join(f"{name} {a} and {b}" for name, a, b in zip(SAME, first[1], sig) if a != b)
-                raise Exception(f"sketches that do not compare: {first[0]} and {path} differ in {what}")
+            ref = first
+            if not is_assembly(st.reports[i]):
+                if first_reads is None:
+                    first_reads = (path, sig)
+                ref = first_reads
+            pairs = [(name, a, b) for name, a, b in zip(SAME, first[1], sig) if name != "min_count" and a != b]
+            if pairs:
+                ref = first
+            elif ref is first_reads and ref[1][at] != sig[at]:
+                pairs = [("min_count", ref[1][at], sig[at])]
+            if pairs:
+                what = ", ".join(f"{name} {a} and {b}" for name, a, b in pairs)
+                raise Exception(f"sketches that do not compare: {ref[0]} and {path} differ in {what}")
     if first[1][SAME.index("hash")] != sketch.HASH or first[1][SAME.index("version")] != sketch.VERSION:
         raise Exception(f"{first[0]}: a sketch of hash {first[1][SAME.index('hash')]!r}, version {first[1][SAME.index('version')]}; "
                         f"this program compares {sketch.HASH!r}, version {sketch.VERSION}")
@@ -74,9 +93,11 @@ def pair_values(q, r, i, j, shared, seen):
     """(jaccard, mash_distance, corrected_distance) of query i and reference j."""
     a, b = q.reports[i], r.reports[j]
     jac = sketch.jaccard(int(shared[i, j]), int(seen[i, j]))
+    eta1, g1 = sketch.sample_eta(a["estimates"], a["sketch"]["min_count"])
+    eta2, g2 = sketch.sample_eta(b["estimates"], b["sketch"]["min_count"])
     return (jac, sketch.mash_distance(jac, a["k"]),
-            sketch.corrected_distance(jac, a["k"], a["every"], a["sketch"]["min_count"], a["sketch"]["eligible"], a["estimates"],
-                                      b["sketch"]["eligible"], b["estimates"]))
+            sketch.corrected_distance_eta(jac, a["k"], a["every"], a["sketch"]["eligible"], g1, eta1, b["sketch"]["eligible"], g2,
+                                          eta2))
 
 
 def rank_neighbours(shared, seen, n, exclude_self):

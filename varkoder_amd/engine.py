@@ -1137,6 +1137,27 @@ class ImageEngine:
         want = max(_capi.VK_SCREEN_MIN_SLOTS, 2 * -(-int(length) // (2 * int(every))))
         return 1 << (want - 1).bit_length()
 
+    def _table_group(self, todo, want, table_bytes):
+        """The next group of spectrum() and spectrum_fasta(), taken off the front of `todo`: samples in order while their
+        tables of want[i] slots fit under table_bytes at 12 bytes a slot (the first always), and the group's tables.
+        Returns (group, its indices as an array, nslots, slot bases, keys int64 and counts int32 device tensors)."""
+        torch = _torch()
+        group, total = [], 0
+        while todo and (not group or total + want[todo[0]] * 12 <= int(table_bytes)):
+            total += want[todo[0]] * 12
+            group.append(todo.pop(0))
+        g = np.asarray(group, dtype=np.int64)
+        nsl = np.asarray([want[i] for i in group], dtype=np.uint64)
+        base = np.zeros(len(group), dtype=np.uint64)
+        base[1:] = np.cumsum(nsl[:-1])
+        try:
+            keys = torch.empty(int(nsl.sum()), dtype=torch.int64, device=self.device)
+            counts = torch.empty(int(nsl.sum()), dtype=torch.int32, device=self.device)
+        except RuntimeError as e:   # (torch.cuda.OutOfMemoryError is one)
+            raise MemoryError(f"no memory for a k-mer table of {int(nsl.sum())} slots ({int(nsl.sum()) * 12} bytes): "
+                              "count a sample of the keys with a larger --spectrum-every") from e
+        return group, g, nsl, base, keys, counts
+
     def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30, sketch=None, depth=None):
         """The k-mer spectra of cleaned samples in HBM (vk_spectrum_device; the rule: INTEGRATION.md, "`--kmer-spectrum`:
         the rule"): sample i is text[offs[i] .. + lens[i]), k in 16..31, a key is taken when the high half of its mix is
@@ -1206,21 +1227,7 @@ class ImageEngine:
             want = most = [int(slots)] * n
         todo = list(range(n))
         while todo:
-            # a group: samples in order while their tables fit
-            group, total = [], 0
-            while todo and (not group or total + want[todo[0]] * 12 <= int(table_bytes)):
-                total += want[todo[0]] * 12
-                group.append(todo.pop(0))
-            g = np.asarray(group, dtype=np.int64)
-            nsl = np.asarray([want[i] for i in group], dtype=np.uint64)
-            base = np.zeros(len(group), dtype=np.uint64)
-            base[1:] = np.cumsum(nsl[:-1])
-            try:
-                keys = torch.empty(int(nsl.sum()), dtype=torch.int64, device=self.device)
-                counts = torch.empty(int(nsl.sum()), dtype=torch.int32, device=self.device)
-            except RuntimeError as e:   # (torch.cuda.OutOfMemoryError is one)
-                raise MemoryError(f"no memory for a k-mer table of {int(nsl.sum())} slots ({int(nsl.sum()) * 12} bytes): "
-                                  "count a sample of the keys with a larger --spectrum-every") from e
+            group, g, nsl, base, keys, counts = self._table_group(todo, want, table_bytes)
             o, l, r = offs[g].copy(), lens[g].copy(), recs[g].copy()
             ws_bytes = C.c_uint64()
             _capi.check(self.ctx, self.L.vk_spectrum_workspace_size(_u64(r), len(group), _u64(l), C.byref(ws_bytes)),
@@ -1249,6 +1256,81 @@ class ImageEngine:
             del keys, counts, ws
             # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
             # the slots -- a bounded loop over a status; at spectrum_slots(., 1) it cannot fill
+            again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
+            for i in again:
+                want[i] = min(4 * want[i], most[i])
+            todo = again + todo
+        return ret()
+
+    @staticmethod
+    def spectrum_fasta_slots(length, every=1):
+        """The table of an assembly of `length` bytes of FASTA text: the smallest power of two that is at least max(1024,
+        2 ceil(length / every)).  Windows cannot exceed bytes, so at every = 1 the load stays at a half or below and the
+        table cannot fill."""
+        want = max(_capi.VK_SCREEN_MIN_SLOTS, 2 * -(-int(length) // int(every)))
+        return 1 << (want - 1).bit_length()
+
+    def spectrum_fasta(self, fasta, offs, lens, k=21, every=1, slots=None, table_bytes=16 << 30, sketch=None):
+        """The k-mer spectra of assemblies whose FASTA text lies in HBM, laid out as for count_fasta
+        (vk_spectrum_fasta_device; the rule: INTEGRATION.md, "`--genome-spectrum`: the rule"): k in 16..31, a key is taken
+        when the high half of its mix is a multiple of `every`.  Returns (rows uint64[n, VK_SPEC_NSTAT], status
+        uint32[n]): a row is records, bases, windows, taken windows, distinct, hist[256]; a sample with a status has an
+        all-zero row.
+
+        slots=None: sample i's table has spectrum_fasta_slots(lens[i], every) slots; with every > 1 a sample that comes
+        back VK_SPEC_TABLE_FULL is counted again with four times the slots, up to spectrum_fasta_slots(lens[i], 1), where
+        it cannot happen.  slots=int forces every sample's table (tests).  The samples are counted in groups whose tables
+        together stay under table_bytes at 12 bytes a slot; a sample whose table alone is larger gets a group of its own.
+
+        sketch=(s, 1): also the samples' bottom-s MinHash sketches (sketch_tables), taken from each group's tables before
+        they are freed -- a sample counted again from the attempt that succeeded.  Returns (rows, status, hashes
+        uint64[n, s], info uint64[n, 2] = eligible, length) then.  Synchronises."""
+        torch = _torch()
+        offs, lens = self._desc(offs, lens)
+        n = len(offs)
+        k, every = int(k), int(every)
+        if not _capi.VK_SCREEN_MIN_K <= k <= _capi.VK_SCREEN_MAX_K:
+            raise ValueError(f"the spectrum's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
+        if every < 1:
+            raise ValueError("every is at least 1")
+        rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        if sketch is not None:
+            sk_s, sk_m = self._sketch_args(*sketch)
+            if sk_m != 1:
+                raise ValueError("an assembly's sketch takes every k-mer: its minimum multiplicity is 1")
+            hashes = np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64)
+            info = np.zeros((n, 2), dtype=np.uint64)
+        ret = lambda: (rows, status) + (() if sketch is None else (hashes, info))   # noqa: E731
+        if n == 0:
+            return ret()
+        if slots is None:
+            want = [self.spectrum_fasta_slots(x, every) for x in lens]
+            most = [self.spectrum_fasta_slots(x, 1) for x in lens]
+        else:
+            want = most = [int(slots)] * n
+        todo = list(range(n))
+        while todo:
+            group, g, nsl, base, keys, counts = self._table_group(todo, want, table_bytes)
+            o, l = offs[g].copy(), lens[g].copy()
+            ws_bytes = C.c_uint64()
+            _capi.check(self.ctx, self.L.vk_spectrum_fasta_workspace_size(_u64(l), len(group), C.byref(ws_bytes)),
+                        "vk_spectrum_fasta_workspace_size")
+            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+            d_rows = torch.empty((len(group), _capi.VK_SPEC_NSTAT), dtype=torch.int64, device=self.device)
+            d_status = torch.empty(len(group), dtype=torch.int32, device=self.device)
+            st = self.L.vk_spectrum_fasta_device(self.ctx, self._ptr(fasta), _u64(o), _u64(l), len(group), k, every,
+                                                 self._ptr(keys), self._ptr(counts), _u64(base), _u64(nsl), self._ptr(d_rows),
+                                                 self._ptr(d_status), self._ptr(ws), ws.numel())
+            _capi.check(self.ctx, st, "vk_spectrum_fasta_device")
+            # (the copies below wait for the kernels: the tables and the workspace are free after them)
+            if sketch is not None:   # (while the tables lie there)
+                hashes[g], info[g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk_s, 1)
+            rows[g] = d_rows.cpu().numpy().view(np.uint64)
+            status[g] = d_status.cpu().numpy().astype(np.uint32)
+            del keys, counts, ws
+            # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
+            # the slots -- a bounded loop over a status; at spectrum_fasta_slots(., 1) it cannot fill
             again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
             for i in again:
                 want[i] = min(4 * want[i], most[i])

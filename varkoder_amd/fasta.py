@@ -328,8 +328,11 @@ def _window_batches(eng, files, pool, batch_bytes, n, s):
             yield batch, i == 0, status, rec_first, bases, samples, dups, rows, hist, t0, time.perf_counter()
 
 
-def _counted(eng, files, pool, batch_bytes):
-    """Per batch of files: (batch, histograms on the device, status, bases, the time the batch was begun, after the count)."""
+def _counted(eng, files, pool, batch_bytes, genome=None, genome_rows=None):
+    """Per batch of files: (batch, histograms on the device, status, bases, the time the batch was begun, after the count).
+    genome (pipeline.GenomeSpectrum, `--genome-spectrum`): the same upload also goes through the assemblies' k-mer spectrum,
+    behind the image count; genome_rows (a dict) receives {file: what genome.after gives for it} for the files the count
+    accepts."""
     for batch, _, t0 in batches(files, batch_bytes, size=text_bytes):
         dev, offs, lens = eng.upload_files(batch, pool)
         unread = getattr(eng, "last_upload_status", None)
@@ -337,13 +340,22 @@ def _counted(eng, files, pool, batch_bytes):
         st = status.cpu().numpy().copy()
         if unread is not None:
             st[unread != 0] |= 0x100   # (a file that could not be read or inflated is not an empty sample)
-        yield batch, hist, st, bases.cpu().numpy(), t0, time.perf_counter()
+        t1 = time.perf_counter()
+        if genome is not None:
+            for j, got in enumerate(genome.after(eng, dev, offs, lens)):
+                if st[j]:
+                    continue   # (reported by the image count)
+                if got[1]:
+                    eprint("SPECTRUM FAIL:", batch[j], "- status", got[1])
+                    continue
+                genome_rows[batch[j]] = got
+        yield batch, hist, st, bases.cpu().numpy(), t0, t1
 
 
 def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=0, rank=0, world=1, batch_bytes=None,
                     io_threads=8, engine=None, verbose=False, weights=None, fragments=False, fragment_length=150,
                     min_bp=50000, max_bp=None, seeds=None, per_record=False, min_record_length=1000, windows=False,
-                    window_length=10000, window_step=None, gpu_png=False):
+                    window_length=10000, window_step=None, gpu_png=False, genome=None):
     """This rank's share of FASTA `files`, each imaged whole.  Returns {sample: OrderedDict(stats)} with the reference's
     keys `<k>mer_counting_time` and `k<k>_img_time`, or `failed_step` for a sample that does not begin with '>', holds
     no base, or could not be read.
@@ -361,8 +373,13 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
     sample of its own (window_names; the rule: INTEGRATION.md, "--from-fasta --windows"), imaged as
     `image_name(<window sample>, window_length, k, mapping)`; stats and failures as for per_record, per window.
 
-    gpu_png: the images' IDAT chunks are made on the GPU (PngSink's encoder), in every one of these modes."""
+    gpu_png: the images' IDAT chunks are made on the GPU (PngSink's encoder), in every one of these modes.
+
+    genome (pipeline.GenomeSpectrum, `--genome-spectrum`; whole files only): every sample's `<dir>/<sample>.spectrum.json`,
+    counted from the upload the image is counted from, and spectrum.assembly_columns' columns in the stats."""
     files = [Path(f) for f in files]
+    if genome is not None and (fragments or per_record or windows):
+        raise ValueError("the genome spectrum is the whole file's: not with fragments, per_record or windows")
     if weights is None:
         weights = agreed_weights(files) if world > 1 else file_weights(files)   # (a collective when sharded)
     mine = [files[i] for i in shard_by_size(weights, rank, world)]
@@ -377,13 +394,17 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
         if windows:
             _window_images(eng, pool, mine, batch_bytes or DEFAULT_BATCH_BYTES, window_length, window_step or window_length, sink, stats,
                            verbose)
-        whole = () if fragments or per_record or windows else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES)
+        genome_rows, reports = {}, []
+        whole = () if fragments or per_record or windows else _counted(eng, mine, pool, batch_bytes or DEFAULT_BATCH_BYTES, genome,
+                                                                        genome_rows)
         for batch, hist, st, bases, t0, t1 in whole:
             nz = (hist != 0).any(dim=1).cpu().numpy()
             imgs = sink.rows(eng.images(hist))
             for j, f in enumerate(batch):
                 sample = sample_of(f)
                 s = stats.setdefault(sample, OrderedDict())
+                if f in genome_rows:
+                    genome.emit(sample, genome_rows.pop(f), s, pool, reports)
                 if st[j] or not nz[j]:
                     eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
                     s["failed_step"] = "image"
@@ -392,6 +413,8 @@ def fasta_to_images(files, outdir, k=7, mapping_code="cgr", labels=None, device=
                 sink.submit(sample, sample, image_name(sample, int(bases[j]), k, mapping_code), imgs[j])
             if verbose:
                 eprint(f"batch of {len(batch)} FASTA files: upload+count {t1 - t0:.3f}s")
+        for fut in reports:
+            fut.result()
         sink.finish(stats)
     return stats
 
@@ -485,9 +508,12 @@ def _fragment_images(eng, pool, batch, t0, sink, stats, seeds, frag_len, min_bp,
 
 
 def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batch_bytes=None, io_threads=8, per_record=False,
-                   min_record_length=1000, origin=None, windows=False, window_length=10000, window_step=None):
+                   min_record_length=1000, origin=None, windows=False, window_length=10000, window_step=None, genome=None):
     """{sample: (bp, histogram uint32[4^k] on the device, 0)} for samples = [(sample, its FASTA file)] (this rank's
     share): what pipeline.clean_to_query returns for cleaned reads.  A sample that fails is reported and left out.
+
+    genome (pipeline.GenomeSpectrum, `--genome-spectrum`; whole files only): every sample's `<dir>/<sample>.spectrum.json`,
+    counted from the upload the histogram is counted from.
 
     per_record: the same tuples keyed by record sample, one per record of min_record_length bases or more
     (fasta_to_images' rule); origin (a dict) receives {record sample: the sample of its file}.
@@ -533,11 +559,16 @@ def fasta_to_query(samples, engine=None, k=7, mapping_code="cgr", device=0, batc
                     if origin is not None:
                         origin[names[g]] = by_file[batch[int(j)]]
             return found
-        for batch, hist, st, bases, _, _ in _counted(eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES):
+        genome_rows, reports = {}, []
+        for batch, hist, st, bases, _, _ in _counted(eng, list(by_file), pool, batch_bytes or DEFAULT_BATCH_BYTES, genome, genome_rows):
             nz = (hist != 0).any(dim=1).cpu().numpy()
             for j, f in enumerate(batch):
+                if f in genome_rows:
+                    genome.emit(by_file[f], genome_rows.pop(f), None, pool, reports)
                 if st[j] or not nz[j]:
                     eprint("K-MER COUNTING FAIL, SKIPPING FILE:", f)
                     continue
                 found[by_file[f]] = (int(bases[j]), hist[j], 0)
+        for fut in reports:
+            fut.result()
     return found

@@ -532,6 +532,41 @@ class Spectrum:
         writes.append(pool.submit(spectrum.write_report, self.dir, sample, obj))
 
 
+@dataclass
+class GenomeSpectrum:
+    """`--from-fasta --genome-spectrum DIR`: the k-mer spectrum of an assembly, counted from the FASTA text where it lies
+    in HBM for the image count (ImageEngine.spectrum_fasta; the rule: INTEGRATION.md, "`--genome-spectrum`: the rule"),
+    written as `DIR/<sample>.spectrum.json` (spectrum.report, assembly=True) with its stats.csv columns
+    (spectrum.assembly_columns)."""
+    dir: object
+    k: int = 21
+    every: int = 1
+    sketch_size: object = None    # `--spectrum-sketch S`: also `DIR/<sample>.sketch.npy` and the json's "sketch" object
+
+    def after(self, eng, text, offs, lens):
+        """Per sample of a batch of FASTA text in HBM: (row, status), with a sketch size (row, status, the sketch's
+        hashes, its eligible count).  A sample with a status has a zero row."""
+        kw = {} if self.sketch_size is None else {"sketch": (self.sketch_size, 1)}
+        rows, status, *rest = eng.spectrum_fasta(text, offs, lens, k=self.k, every=self.every, **kw)
+        if self.sketch_size is None:
+            return [(rows[j], int(status[j])) for j in range(len(rows))]
+        hashes, info = rest
+        return [(rows[j], int(status[j]), hashes[j, :int(info[j, 1])].copy(), int(info[j, 0])) for j in range(len(rows))]
+
+    def emit(self, sample, got, stats_row, pool, writes):
+        """A sample's file queued on the pool (its future goes to `writes`) and its columns into stats_row (None: none)."""
+        from . import sketch, spectrum
+        row, sk = got[0], None
+        if self.sketch_size is not None:
+            hashes, eligible = got[2], got[3]
+            sk = sketch.meta(self.sketch_size, 1, eligible, len(hashes))
+            writes.append(pool.submit(sketch.write_sketch, self.dir, sample, hashes))
+        if stats_row is not None:
+            stats_row.update(spectrum.assembly_columns(row, self.k, self.every))
+        writes.append(pool.submit(spectrum.write_report, self.dir, sample, spectrum.report(row, self.k, self.every, sketch=sk,
+                                                                                           assembly=True)))
+
+
 def _seed_groups(names, seeds):
     """{seed: [indices into names]}: samples with different seeds go in separate calls."""
     by_seed = OrderedDict()

@@ -43,12 +43,33 @@ def corrected_distance(j, k, every, m, a1, est1, a2, est2):
     lam1, g1, lam2, g2 = est1.get("kmer_coverage"), est1.get("genome_kmers"), est2.get("kmer_coverage"), est2.get("genome_kmers")
     if lam1 is None or g1 is None or lam2 is None or g2 is None:
         return None
-    eta = seen_fraction(lam1, m) * seen_fraction(lam2, m)
+    return corrected_distance_eta(j, k, every, a1, g1, seen_fraction(lam1, m), a2, g2, seen_fraction(lam2, m))
+
+
+def corrected_distance_eta(j, k, every, a1, g1, eta1, a2, g2, eta2):
+    """corrected_distance in its per-sample form: sample i shows a share eta_i of its genome's G_i k-mers (sample_eta).
+    Two assemblies (eta = 1, G = every a) give D = 1 - (2J / (1 + J))^(1/k), the Mash distance's exact form.  None when J or
+    any of a sample's two values is."""
+    if j is None or g1 is None or g2 is None or eta1 is None or eta2 is None:
+        return None
+    eta = eta1 * eta2
     if eta <= 0.0 or g1 + g2 <= 0.0:
         return None
     inter = j * (a1 + a2) / (1.0 + j)
     x = 2.0 * every * inter / (eta * (g1 + g2))
     return 1.0 - min(1.0, x) ** (1.0 / k)
+
+
+def sample_eta(est, m):
+    """(eta, G) of a sample from its spectrum estimates: eta is `seen_fraction` when the estimates state it (an assembly:
+    1.0), else P(Poisson(kmer_coverage) >= m) with m the sample's own min_count; (None, None) without estimates."""
+    if est is None or est.get("genome_kmers") is None:
+        return None, None
+    if est.get("seen_fraction") is not None:
+        return float(est["seen_fraction"]), est["genome_kmers"]
+    if est.get("kmer_coverage") is None:
+        return None, None
+    return seen_fraction(est["kmer_coverage"], m), est["genome_kmers"]
 
 
 def meta(size, min_count, eligible, length):

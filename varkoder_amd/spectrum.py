@@ -48,19 +48,45 @@ def estimate(row, k, every=1):
     return out
 
 
-def report(row, k, every=1, sketch=None):
+def assembly_estimate(row, k, every=1):
+    """The estimates of an assembly's row (ImageEngine.spectrum_fasta; the rule: INTEGRATION.md, "`--genome-spectrum`: the
+    rule"): an assembly shows every k-mer of its genome once per copy, so genome_kmers = every x distinct,
+    high_copy_fraction is the share of taken windows whose k-mer occurs more than once, seen_fraction is 1, and what
+    describes a library (coverage, errors) is None."""
+    row = np.asarray(row, dtype=np.uint64)
+    taken, distinct, ones = int(row[TAKEN_WINDOWS]), int(row[DISTINCT]), int(row[HIST_AT])
+    out = {name: None for name in ESTIMATES}
+    out.update(genome_kmers=int(every) * distinct, high_copy_fraction=(taken - ones) / taken if taken else None,
+               singleton_fraction=ones / distinct if distinct else None, seen_fraction=1.0, reason="assembly")
+    return out
+
+
+def report(row, k, every=1, sketch=None, assembly=False):
     """The object of `<sample>.spectrum.json`.  sketch (`--spectrum-sketch`: sketch.meta) becomes its `"sketch"` object;
-    without one the object has no such key."""
+    without one the object has no such key.  assembly (`--genome-spectrum`): the row counts records where a library's
+    counts reads, the estimates are assembly_estimate's and the object says `"source": "assembly"`."""
     row = np.asarray(row, dtype=np.uint64)
     hist = [int(x) for x in row[HIST_AT:HIST_AT + BINS - 1]]
     while hist and hist[-1] == 0:
         hist.pop()
-    out = {"k": int(k), "every": int(every), "reads": int(row[READS]), "bases": int(row[BASES]),
+    out = {"k": int(k), "every": int(every), "records" if assembly else "reads": int(row[READS]), "bases": int(row[BASES]),
            "windows": int(row[WINDOWS]), "taken_windows": int(row[TAKEN_WINDOWS]), "distinct": int(row[DISTINCT]),
-           "histogram": hist, "histogram_256_and_more": int(row[HIST_AT + BINS - 1]), "estimates": estimate(row, k, every)}
+           "histogram": hist, "histogram_256_and_more": int(row[HIST_AT + BINS - 1]),
+           "estimates": assembly_estimate(row, k, every) if assembly else estimate(row, k, every)}
+    if assembly:
+        out = {"source": "assembly", **out}
     if sketch is not None:
         out["sketch"] = dict(sketch)
     return out
+
+
+ASSEMBLY_COLUMNS = ("genome_kmers", "high_copy_fraction")
+
+
+def assembly_columns(row, k, every=1):
+    """The stats.csv columns of an assembly's row: the spectrum_* cells that describe a library stay empty."""
+    est = assembly_estimate(row, k, every)
+    return {"spectrum_" + name: (est[name] if name in ASSEMBLY_COLUMNS and est[name] is not None else "") for name in COLUMNS}
 
 
 def columns(row, k, every=1):
