@@ -25,7 +25,10 @@
 #ifndef VK_CLEAN_H
 #define VK_CLEAN_H
 
+// VK_TEXT_STRUCTS_ONLY: the constants and plain structs alone, for a host compiler (vk_textplan.h sizes workspaces with them).
+#ifndef VK_TEXT_STRUCTS_ONLY
 #include <hip/hip_runtime.h>
+#endif
 
 #include <cstdint>
 
@@ -65,6 +68,8 @@ struct ClPlan {          // what a unit writes
     uint32_t m1, t0, m2;       // merged: R1[a1 .. a1 + m1) + rc(R2 kept)[t0 .. t0 + m2)
     uint32_t flags;            // 1 R1 (or the merged read) written, 2 R2 written, 4 merged
 };
+
+#ifndef VK_TEXT_STRUCTS_ONLY
 
 // ------------------------------------------------------------------ helpers --
 
@@ -806,6 +811,8 @@ __global__ void __launch_bounds__(kClThreads) vk_cl_finish_kernel(const ClSample
     const uint64_t end = (n + 15) / 16 * 16;
     for (uint64_t i = n + threadIdx.x; i < end; i += blockDim.x) out[s.out_off + i] = 0;
 }
+
+#endif  // VK_TEXT_STRUCTS_ONLY
 
 }  // namespace
 

@@ -43,6 +43,8 @@ struct EmStep {
     uint32_t sample, whole;
 };
 
+#ifndef VK_TEXT_STRUCTS_ONLY   // (vk_clean.h: the plain structs above are all a host compiler takes)
+
 struct EmRec {               // a record's lines without their '\r': header [h, h + hl), sequence [s, s + L), quality [q, q + Lq)
     uint64_t h, s, q;
     uint32_t hl, L, Lq;
@@ -205,6 +207,8 @@ __global__ void __launch_bounds__(kClThreads) vk_em_pad_kernel(const EmStep* ste
     const uint64_t n = sizes[st], end = (n + 15) / 16 * 16;
     for (uint64_t i = n; i < end; ++i) out[steps[st].out_off + i] = 0;
 }
+
+#endif  // VK_TEXT_STRUCTS_ONLY
 
 }  // namespace
 

@@ -145,11 +145,7 @@ __device__ inline void qc_merge(const QcTile* T, uint64_t* row, uint32_t t, uint
 
 #ifndef VK_QC_LANE_ONLY
 
-struct QcStream {
-    uint64_t off, len;       // text in d_text
-    uint64_t rec0, nrec;     // its budgeted records in the index
-    uint64_t chunk0, chunk1; // its chunks of the newline passes
-};
+using QcStream = EmSample;   // a stream is a sample of the record index: its text, its budgeted records, its chunks (vk_emit.h)
 
 __global__ void __launch_bounds__(kClThreads) vk_qc_status_kernel(const uint8_t* text, const QcStream* streams, uint32_t nstreams,
                                                                  const uint64_t* nl_prefix, uint64_t* rows, uint32_t* status) {

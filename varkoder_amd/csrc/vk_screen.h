@@ -174,14 +174,14 @@ struct ScWalk {
     __device__ inline bool more(uint32_t K) const { return (run > 0 || cr) && extra < K - 1; }
 };
 
-#ifndef VK_SCREEN_LANE_ONLY
-
-// ------------------------------------------------------------------ the set --
-
-struct ScBuildOut {   // what a build leaves in its workspace
+struct ScBuildOut {   // what a build leaves in its workspace (plain: vk_textplan.h sizes the workspace with it)
     unsigned long long windows, distinct;
     uint32_t full, pad;
 };
+
+#ifndef VK_SCREEN_LANE_ONLY
+
+// ------------------------------------------------------------------ the set --
 
 template <bool kInsert>
 __global__ __launch_bounds__(kFaThreads) void vk_sc_build_kernel(const uint8_t* base, FaMeta m, const uint32_t* carry, uint32_t K,

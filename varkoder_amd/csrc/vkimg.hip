@@ -83,6 +83,7 @@
 #include "vk_sketch.h"
 #include "vk_depth.h"
 #include "vk_qc.h"
+#include "vk_textplan.h"
 #include "vk_dist.h"
 
 // ---------------------------------------------------------------- C ABI ------
@@ -1718,18 +1719,7 @@ int vk_last_count_launch(const vk_ctx* ctx, uint32_t* grid, uint32_t* block, uin
 
 namespace {
 
-// the pieces of a vk_clean_device workspace
-struct ClLayout {
-    ClFile* files;
-    uint64_t *fchunk, *unit_base, *ccount, *cprefix, *sums, *hashes, *obytes, *oprefix;
-    ClSample* samples;
-    ClRec* recs;
-    ClPlan* plans;
-    uint32_t *slot_of, *table;
-    size_t total;
-    uint64_t nchunks, nrec, nslots;
-};
-
+// the pieces of a vk_clean_device workspace (ClLayout: vk_textplan.h)
 ClLayout cl_layout(void* d_ws, const uint64_t* lengths, const uint64_t* records, uint32_t nfiles, uint32_t nsamples) {
     ClLayout L{};
     for (uint32_t i = 0; i < nfiles; ++i) {
@@ -1798,56 +1788,7 @@ int cl_scan(vk_ctx* ctx, const uint64_t* in, uint64_t n, uint64_t* sums, uint64_
     return VK_OK;
 }
 
-uint32_t cl_rank(uint32_t role) { return role == VK_CL_ROLE_UNPAIRED ? 2u : role - 1u; }   // a file's group: R1, R2, single reads
-
-// the files in the library's order: by sample, then R1, R2, unpaired, each in the caller's order (no roles: the caller's)
-std::vector<uint32_t> cl_order(const uint32_t* roles, const uint32_t* samples, uint32_t nfiles) {
-    std::vector<uint32_t> order(nfiles);
-    for (uint32_t i = 0; i < nfiles; ++i) order[i] = i;
-    if (roles)
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-            return samples[a] != samples[b] ? samples[a] < samples[b] : cl_rank(roles[a]) < cl_rank(roles[b]);
-        });
-    return order;
-}
-
-// The record index of a launch as the host states it: the file tables that the kernels read and, per group
-// (3 * sample + cl_rank), the ordinal of its first record and the records it gives.
-struct ClIndex {
-    std::vector<ClFile> files;
-    std::vector<uint64_t> fchunk, first, count;
-    uint64_t nchunks = 0, nrec = 0;
-};
-
-// A file gives its budget records[i], the files of a group no more than group_cap between them (detection's evaluation
-// set: a group's first kAdEval records, in the order of its files).  Without records (vk_clean_lines_device) the files
-// stay in the caller's order and nothing is indexed.
-ClIndex cl_index(const uint64_t* offsets, const uint64_t* lengths, const uint64_t* records, const uint32_t* roles,
-                 const uint32_t* samples, uint32_t nfiles, uint32_t nsamples, uint64_t group_cap) {
-    ClIndex ix;
-    ix.files.resize(nfiles);
-    ix.fchunk.resize(nfiles);
-    ix.first.assign(3ull * nsamples, 0);
-    ix.count.assign(3ull * nsamples, 0);
-    const std::vector<uint32_t> order = cl_order(roles, samples, nfiles);
-    for (uint32_t j = 0; j < nfiles; ++j) {
-        const uint32_t i = order[j];
-        uint64_t n = 0;
-        if (records) {
-            const uint64_t g = 3ull * samples[i] + cl_rank(roles[i]);
-            n = std::min(records[i], group_cap - ix.count[g]);
-            // (a group's files are adjacent and those ahead of its first record give none, so this is the ordinal at the
-            // group's first file as well; a group without files keeps 0)
-            if (ix.count[g] == 0) ix.first[g] = ix.nrec;
-            ix.count[g] += n;
-        }
-        ix.files[j] = ClFile{offsets[i], lengths[i], n, ix.nrec, ix.nchunks};
-        ix.fchunk[j] = ix.nchunks;
-        ix.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-        ix.nrec += n;
-    }
-    return ix;
-}
+// (cl_rank, cl_order, ClIndex and cl_index, the host's statement of the record index: vk_textplan.h)
 
 // Uploads the index's tables and has the GPU find every record's line ends.  The sample rows and the stats and status
 // words that the init kernel resets are vk_clean_device's; detection has none (nulls, nsamples 0).
@@ -2202,43 +2143,27 @@ int vk_clean_detect_device(vk_ctx* ctx, const void* d_text, const uint64_t* offs
 
 namespace {
 
-// the pieces of a vk_ladder_emit_device workspace: the record index in vk_clean_device's layout (the pieces of it that
-// cl_index_run fills), then the steps' tables and the items' bytes
-struct EmLayout {
-    ClLayout c;
-    EmSample* samples;
-    EmStep* steps;
-    uint64_t *step_base, *sizes, *obytes, *oprefix;
-    uint32_t* status;
-    size_t total;
-    uint64_t nitems;
-};
-
-EmLayout em_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths, const uint32_t* step_sample,
-                   uint32_t nsteps) {
-    EmLayout L{};
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-        L.c.nrec += records[i];
-    }
-    for (uint32_t j = 0; j < nsteps; ++j) L.nitems += step_sample[j] < nsamples ? records[step_sample[j]] : 0;
-    const uint64_t nb = (std::max(L.c.nchunks, L.nitems) + kClScanBlock - 1) / kClScanBlock;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.c.files, nsamples);
-    take(L.c.fchunk, nsamples);
-    take(L.c.ccount, L.c.nchunks);
-    take(L.c.cprefix, L.c.nchunks + 1);
-    take(L.c.sums, nb + 1);
-    take(L.c.recs, L.c.nrec);
-    take(L.samples, nsamples);
-    take(L.status, nsamples);
-    take(L.steps, nsteps);
-    take(L.step_base, nsteps + 1ull);
-    take(L.sizes, nsteps);
-    take(L.obytes, L.nitems);
-    take(L.oprefix, L.nitems + 1);
-    L.total = take.at;
-    return L;
+// What the calls on record text share (the plans, rules and layouts: vk_textplan.h).
+//
+// Their head: the samples' rows and, where the call has the piece, rec_base go up; then the call's own uploads and resets
+// (`more`); the record index is found; vk_em_status_kernel states every sample's framing (no d_status: vk_qc_device, which
+// has a status kernel of its own).
+template <class F>
+int text_index_run(vk_ctx* ctx, const uint8_t* text, const TextIndex& t, const ClLayout& c, EmSample* d_rows, uint64_t* d_rec_base,
+                   uint32_t* d_status, F&& more) {
+    const uint32_t nsamples = static_cast<uint32_t>(t.rows.size());
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    // (pageable sources: a copy has read its source on return)
+    VK_HIP(ctx, hipMemcpyAsync(d_rows, t.rows.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
+    if (d_rec_base) VK_HIP(ctx, hipMemcpyAsync(d_rec_base, t.rec_base.data(), t.rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    int rc = more();
+    if (rc) return rc;
+    rc = cl_index_run(ctx, text, t.ix, c, nullptr, 0, nullptr, nullptr);
+    if (rc) return rc;
+    if (d_status)
+        hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
+                           d_rows, nsamples, c.recs, c.cprefix, d_status);
+    return VK_OK;
 }
 
 }  // namespace
@@ -2260,20 +2185,12 @@ int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offs
     if (!ctx || nsamples == 0 || !d_fastq || !offsets || !lengths || !records || !status || !d_ws) return VK_EINVAL;
     if (nsteps && (!step_sample || !step_seed || !step_threshold || !step_whole || !out_offsets || !out_lengths)) return VK_EINVAL;
     if (!d_out && out_capacity) return VK_EINVAL;
-    for (uint32_t i = 0; i < nsamples; ++i)
-        if (offsets[i] % 16) return VK_EINVAL;
-    for (uint32_t j = 0; j < nsteps; ++j)
-        if (step_sample[j] >= nsamples || step_threshold[j] > (1ull << 32)) return VK_EINVAL;
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.records = records, c.nsamples = nsamples;
+    if (int rc = emit_check(c, step_sample, step_threshold, nsteps)) return rc;
     const EmLayout L = em_layout(d_ws, records, nsamples, lengths, step_sample, nsteps);
     if (ws_bytes < L.total) return VK_EINVAL;
-    // a sample is one file of the record index
-    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
-    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
-    std::vector<EmSample> smp(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i)
-        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
-                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
+    const TextIndex t = text_index(offsets, lengths, records, nsamples);
     std::vector<EmStep> steps(nsteps);
     std::vector<uint64_t> step_base(nsteps + 1ull, 0);
     for (uint32_t j = 0; j < nsteps; ++j) {
@@ -2281,15 +2198,13 @@ int vk_ladder_emit_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offs
         step_base[j + 1] = step_base[j] + records[step_sample[j]];
     }
     const uint64_t nitems = step_base[nsteps];
-    VK_HIP(ctx, hipSetDevice(ctx->device));
     const auto* text = static_cast<const uint8_t*>(d_fastq);
-    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.step_base, step_base.data(), step_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nsteps) VK_HIP(ctx, hipMemcpyAsync(L.steps, steps.data(), nsteps * sizeof(EmStep), hipMemcpyHostToDevice, ctx->stream));
-    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    int rc = text_index_run(ctx, text, t, L.c, L.samples, nullptr, L.status, [&] {
+        VK_HIP(ctx, hipMemcpyAsync(L.step_base, step_base.data(), step_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (nsteps) VK_HIP(ctx, hipMemcpyAsync(L.steps, steps.data(), nsteps * sizeof(EmStep), hipMemcpyHostToDevice, ctx->stream));
+        return VK_OK;
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
-                       L.samples, nsamples, L.c.recs, L.c.cprefix, L.status);
     if (nitems)
         hipLaunchKernelGGL(vk_em_plan_kernel, dim3((nitems + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
                            L.samples, L.steps, L.step_base, nsteps, nitems, L.c.recs, L.status, L.obytes);
@@ -3259,60 +3174,22 @@ int vk_last_bam_groups(const vk_ctx* ctx, uint64_t* emit_workgroups, uint64_t* w
 
 namespace {
 
-// the pieces of a vk_screen_build_device workspace (the units counted at their smallest size, 64 bytes)
-struct ScBuildLayout {
-    uint64_t* meta;
-    uint32_t *ukey, *carry, *status;
-    ScBuildOut* out;
-    size_t total;
-};
+// (the rules, sc_build_layout and sc_layout: vk_textplan.h)
 
-ScBuildLayout sc_build_layout(void* d_ws, uint64_t length) {
-    ScBuildLayout L{};
-    const uint64_t nunits = (length + kFaLaneBytes - 1) / kFaLaneBytes;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.meta, 6);
-    take(L.ukey, nunits + 1);
-    take(L.carry, nunits + 1);
-    take(L.out, 1);
-    take(L.status, 1);
-    L.total = take.at;
-    return L;
+// The tail of the calls that keep records (screen, depth filter): the scan of the records' kept bytes, the text, and per
+// sample its length and the zeros up to its 16-byte rounded end.
+int kept_text_run(vk_ctx* ctx, const uint8_t* text, const ScLayout& L, uint32_t nsamples, uint64_t nrec, uint8_t* d_out,
+                  uint64_t* d_out_lengths) {
+    int rc = cl_scan(ctx, L.obytes, nrec, L.c.sums, L.oprefix);
+    if (rc) return rc;
+    if (nrec)
+        hipLaunchKernelGGL(vk_sc_write_kernel, dim3(static_cast<uint32_t>(text_record_blocks(nrec))), dim3(kClThreads), 0, ctx->stream,
+                           text, L.rec_base, L.out_offs, nsamples, nrec, L.c.recs, L.oprefix, d_out);
+    hipLaunchKernelGGL(vk_sc_pad_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.rec_base,
+                       L.out_offs, nsamples, L.oprefix, d_out, d_out_lengths);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
 }
-
-// the pieces of a vk_screen_device workspace: the record index in vk_clean_device's layout (the pieces of it that
-// cl_index_run fills), then the samples' tables and the records' kept bytes
-struct ScLayout {
-    ClLayout c;
-    EmSample* samples;
-    uint64_t *rec_base, *out_offs, *obytes, *oprefix;
-    size_t total;
-};
-
-ScLayout sc_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
-    ScLayout L{};
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-        L.c.nrec += records[i];
-    }
-    const uint64_t nb = (std::max(L.c.nchunks, L.c.nrec) + kClScanBlock - 1) / kClScanBlock;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.c.files, nsamples);
-    take(L.c.fchunk, nsamples);
-    take(L.c.ccount, L.c.nchunks);
-    take(L.c.cprefix, L.c.nchunks + 1);
-    take(L.c.sums, nb + 1);
-    take(L.c.recs, L.c.nrec);
-    take(L.samples, nsamples);
-    take(L.rec_base, nsamples + 1ull);
-    take(L.out_offs, nsamples);
-    take(L.obytes, L.c.nrec);
-    take(L.oprefix, L.c.nrec + 1);
-    L.total = take.at;
-    return L;
-}
-
-bool sc_slots_ok(uint64_t nslots) { return nslots >= kScMinSlots && nslots <= (1ull << 40) && (nslots & (nslots - 1)) == 0; }
 
 }  // namespace
 
@@ -3327,10 +3204,9 @@ int vk_screen_build_workspace_size(uint64_t length, uint64_t* bytes) {
 int vk_screen_build_device(vk_ctx* ctx, const void* d_fasta, uint64_t length, int k, uint64_t* d_table, uint64_t nslots,
                            void* d_ws, uint64_t ws_bytes, uint64_t* windows, uint64_t* distinct, uint32_t* status) {
     if (!ctx || !d_ws || !windows || !distinct || !status) return VK_EINVAL;
-    if (length > VK_SCREEN_MAX_REF) return VK_EINVAL;   // (before anything is allocated or uploaded)
-    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK)) return VK_EINVAL;
+    // (a reference too long is refused here: before anything is allocated or uploaded)
+    if (int rc = screen_build_check(length, k, d_table != nullptr, nslots)) return rc;
     if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    if ((d_table == nullptr) != (nslots == 0) || (d_table && !sc_slots_ok(nslots))) return VK_EINVAL;
     const ScBuildLayout L = sc_build_layout(d_ws, length);
     if (ws_bytes < L.total) return VK_EINVAL;
     VK_HIP(ctx, hipSetDevice(ctx->device));
@@ -3339,20 +3215,20 @@ int vk_screen_build_device(vk_ctx* ctx, const void* d_fasta, uint64_t length, in
     int rc = fa_plan(ctx, &zero, &length, 1, &pl);
     if (rc) return rc;
     // (pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(L.f.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     VK_HIP(ctx, hipMemsetAsync(L.out, 0, sizeof(ScBuildOut), ctx->stream));
     if (d_table) VK_HIP(ctx, hipMemsetAsync(d_table, 0xFF, nslots * sizeof(uint64_t), ctx->stream));
-    const FaMeta m = pl.on_device(L.meta);
+    const FaMeta m = pl.on_device(L.f.meta);
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
-    rc = fa_header_state(ctx, text, pl, m, L.ukey, L.carry, L.status);
+    rc = fa_header_state(ctx, text, pl, m, L.f.ukey, L.f.carry, L.status);
     if (rc) return rc;
     if (pl.nwg) {
         const dim3 grid(static_cast<uint32_t>(pl.nwg)), block(kFaThreads);
         if (d_table)
-            hipLaunchKernelGGL(vk_sc_build_kernel<true>, grid, block, 0, ctx->stream, text, m, L.carry, static_cast<uint32_t>(k), d_table,
+            hipLaunchKernelGGL(vk_sc_build_kernel<true>, grid, block, 0, ctx->stream, text, m, L.f.carry, static_cast<uint32_t>(k), d_table,
                                nslots, L.out);
         else
-            hipLaunchKernelGGL(vk_sc_build_kernel<false>, grid, block, 0, ctx->stream, text, m, L.carry, static_cast<uint32_t>(k), d_table,
+            hipLaunchKernelGGL(vk_sc_build_kernel<false>, grid, block, 0, ctx->stream, text, m, L.f.carry, static_cast<uint32_t>(k), d_table,
                                nslots, L.out);
         VK_HIP(ctx, hipGetLastError());
     }
@@ -3379,53 +3255,30 @@ int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, 
     if (!ctx || nsamples == 0 || !d_fastq || !offsets || !lengths || !records || !d_table || !d_out || !out_offsets ||
         !d_out_lengths || !d_stats || !d_status || !d_ws)
         return VK_EINVAL;
-    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || min_hits < 1 || !sc_slots_ok(nslots)) return VK_EINVAL;
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if (offsets[i] % 16 || out_offsets[i] % 16) return VK_EINVAL;
-        if (out_offsets[i] > out_capacity || (lengths[i] + 15) / 16 * 16 > out_capacity - out_offsets[i]) return VK_ENOSPC;
-    }
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.records = records, c.nsamples = nsamples;
+    c.out_offsets = out_offsets, c.out_capacity = out_capacity, c.k = k, c.min_hits = min_hits;
+    if (int rc = screen_check(c, nslots)) return rc;
     const ScLayout L = sc_layout(d_ws, records, nsamples, lengths);
     if (ws_bytes < L.total) return VK_EINVAL;
-    // a sample is one file of the record index
-    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
-    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
-    std::vector<EmSample> smp(nsamples);
-    std::vector<uint64_t> rec_base(nsamples + 1ull, 0);
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
-                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
-        rec_base[i + 1] = rec_base[i] + records[i];
-    }
-    const uint64_t nrec = rec_base[nsamples];
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const TextIndex t = text_index(offsets, lengths, records, nsamples);
+    const uint64_t nrec = t.rec_base[nsamples];
     const auto* text = static_cast<const uint8_t*>(d_fastq);
-    // (pageable sources: a copy has read its source on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_stats, 0, nsamples * 4ull * sizeof(uint64_t), ctx->stream));
-    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    int rc = text_index_run(ctx, text, t, L.c, L.samples, L.rec_base, d_status, [&] {
+        VK_HIP(ctx, hipMemcpyAsync(L.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_stats, 0, nsamples * 4ull * sizeof(uint64_t), ctx->stream));
+        return VK_OK;
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
-                       L.samples, nsamples, L.c.recs, L.c.cprefix, d_status);
-    const uint32_t nblocks = static_cast<uint32_t>((nrec + kScRecsPerBlock - 1) / kScRecsPerBlock);
     if (nrec) {
         const ScParams P{d_table, nslots, static_cast<uint32_t>(k), min_hits, keep ? 1u : 0u,
                          ctx->screen_tile ? ctx->screen_tile : kScMaxTile};
-        hipLaunchKernelGGL(vk_sc_match_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.samples, L.rec_base, nsamples,
-                           nrec, L.c.recs, d_status, P, L.obytes, reinterpret_cast<unsigned long long*>(d_stats));
+        hipLaunchKernelGGL(vk_sc_match_kernel, dim3(static_cast<uint32_t>(text_record_blocks(nrec))), dim3(kClThreads), 0, ctx->stream,
+                           text, L.samples, L.rec_base, nsamples, nrec, L.c.recs, d_status, P, L.obytes,
+                           reinterpret_cast<unsigned long long*>(d_stats));
     }
     VK_HIP(ctx, hipGetLastError());
-    rc = cl_scan(ctx, L.obytes, nrec, L.c.sums, L.oprefix);
-    if (rc) return rc;
-    if (nrec)
-        hipLaunchKernelGGL(vk_sc_write_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.rec_base, L.out_offs, nsamples,
-                           nrec, L.c.recs, L.oprefix, d_out);
-    hipLaunchKernelGGL(vk_sc_pad_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, L.rec_base,
-                       L.out_offs, nsamples, L.oprefix, d_out, d_out_lengths);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
+    return kept_text_run(ctx, text, L, nsamples, nrec, d_out, d_out_lengths);
 }
 
 }  // extern "C"
@@ -3434,36 +3287,33 @@ int vk_screen_device(vk_ctx* ctx, const void* d_fastq, const uint64_t* offsets, 
 
 namespace {
 
-// the pieces of a vk_spectrum_device workspace: the record index in vk_clean_device's layout (the pieces of it that
-// cl_index_run fills), then the samples' tables
-struct SpLayout {
-    ClLayout c;
-    EmSample* samples;
-    uint64_t *rec_base, *block_base, *slot_base, *nslots;
-    size_t total;
-};
+// (the rules, the table plan and sp_layout: vk_textplan.h)
 
-SpLayout sp_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
-    SpLayout L{};
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-        L.c.nrec += records[i];
-    }
-    const uint64_t nb = (L.c.nchunks + kClScanBlock - 1) / kClScanBlock;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.c.files, nsamples);
-    take(L.c.fchunk, nsamples);
-    take(L.c.ccount, L.c.nchunks);
-    take(L.c.cprefix, L.c.nchunks + 1);
-    take(L.c.sums, nb + 1);
-    take(L.c.recs, L.c.nrec);
-    take(L.samples, nsamples);
-    take(L.rec_base, nsamples + 1ull);
-    take(L.block_base, nsamples + 1ull);
-    take(L.slot_base, nsamples);
-    take(L.nslots, nsamples);
-    L.total = take.at;
-    return L;
+// The samples' tables, for the spectrum of reads and of assemblies alike: their descriptors go up and the rows are reset ...
+int sp_tables_put(vk_ctx* ctx, const SpTablePieces& T, const std::vector<uint64_t>& block_base, const uint64_t* slot_base,
+                  const uint64_t* nslots, uint32_t nsamples, uint64_t* d_rows) {
+    VK_HIP(ctx, hipMemcpyAsync(T.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(T.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(T.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kSpNstat * sizeof(uint64_t), ctx->stream));
+    return VK_OK;
+}
+
+// ... and the table sequence: every slot freed, the call's count step (`count`, given the rows), the histogram, the rows
+// finished.  nblocks: the table plan's workgroups (block_base[nsamples]).
+template <class F>
+int sp_tables_run(vk_ctx* ctx, const SpTablePieces& T, uint64_t nblocks, uint32_t nsamples, uint64_t* d_keys, uint32_t* d_counts,
+                  uint32_t* d_status, uint64_t* d_rows, F&& count) {
+    const dim3 tgrid(static_cast<uint32_t>(nblocks));
+    auto* rows = reinterpret_cast<unsigned long long*>(d_rows);
+    hipLaunchKernelGGL(vk_sp_init_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, T.block_base, nsamples, T.slot_base, T.nslots, d_keys,
+                       d_counts);
+    count(rows);
+    hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, T.block_base, nsamples, T.slot_base, T.nslots,
+                       d_counts, d_status, rows);
+    hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
 }
 
 }  // namespace
@@ -3482,87 +3332,33 @@ int vk_spectrum_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets,
     if (!ctx || nsamples == 0 || !d_text || !offsets || !lengths || !records || !d_keys || !d_counts || !slot_base || !nslots ||
         !d_rows || !d_status || !d_ws)
         return VK_EINVAL;
-    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
-    std::vector<uint64_t> block_base(nsamples + 1ull, 0), rec_base(nsamples + 1ull, 0);
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        // (a sample of more than 2^33 bytes: a multiplicity is 32-bit)
-        if (offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i])) return VK_EINVAL;
-        block_base[i + 1] = block_base[i] + (nslots[i] + kSpSlotsPerBlock - 1) / kSpSlotsPerBlock;
-        rec_base[i + 1] = rec_base[i] + records[i];
-    }
-    const uint64_t nrec = rec_base[nsamples], nrblocks = (nrec + kScRecsPerBlock - 1) / kScRecsPerBlock;
-    if (block_base[nsamples] >= (1ull << 31) || nrblocks >= (1ull << 31)) return VK_EINVAL;
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.records = records, c.nsamples = nsamples;
+    c.nslots = nslots, c.slot_base = slot_base, c.k = k, c.every = every;
+    std::vector<uint64_t> block_base;
+    if (int rc = spectrum_check(c, &block_base)) return rc;
     const SpLayout L = sp_layout(d_ws, records, nsamples, lengths);
     if (ws_bytes < L.total) return VK_EINVAL;
-    // a sample is one file of the record index
-    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
-    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
-    std::vector<EmSample> smp(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i)
-        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
-                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const TextIndex t = text_index(offsets, lengths, records, nsamples);
+    const uint64_t nrec = t.rec_base[nsamples];
     const auto* text = static_cast<const uint8_t*>(d_text);
-    // (pageable sources: a copy has read its source on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kSpNstat * sizeof(uint64_t), ctx->stream));
-    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    int rc = text_index_run(ctx, text, t, L.c, L.samples, L.rec_base, d_status,
+                            [&] { return sp_tables_put(ctx, L.t, block_base, slot_base, nslots, nsamples, d_rows); });
     if (rc) return rc;
-    hipLaunchKernelGGL(vk_em_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
-                       L.samples, nsamples, L.c.recs, L.c.cprefix, d_status);
-    const dim3 tgrid(static_cast<uint32_t>(block_base[nsamples]));
-    auto* rows = reinterpret_cast<unsigned long long*>(d_rows);
-    hipLaunchKernelGGL(vk_sp_init_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots, d_keys,
-                       d_counts);
-    if (nrec) {
-        const SpParams P{d_keys, d_counts, L.slot_base, L.nslots, static_cast<uint32_t>(k), every,
+    return sp_tables_run(ctx, L.t, block_base[nsamples], nsamples, d_keys, d_counts, d_status, d_rows, [&](unsigned long long* rows) {
+        if (!nrec) return;
+        const SpParams P{d_keys, d_counts, L.t.slot_base, L.t.nslots, static_cast<uint32_t>(k), every,
                          ctx->spectrum_tile ? ctx->spectrum_tile : kScMaxTile, ctx->spectrum_merge};
-        hipLaunchKernelGGL(vk_sp_count_kernel, dim3(static_cast<uint32_t>(nrblocks)), dim3(kClThreads), 0, ctx->stream, text, L.rec_base,
-                           nsamples, nrec, L.c.recs, d_status, P, rows);
-    }
-    hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
-                       d_counts, d_status, rows);
-    hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
+        hipLaunchKernelGGL(vk_sp_count_kernel, dim3(static_cast<uint32_t>(text_record_blocks(nrec))), dim3(kClThreads), 0, ctx->stream,
+                           text, L.rec_base, nsamples, nrec, L.c.recs, d_status, P, rows);
+    });
 }
 
 }  // extern "C"
 
 // ------------------------------------------- the k-mer spectrum of assemblies, from FASTA text (vk_fasta_spectrum.h) ------
 
-namespace {
-
-// the pieces of a vk_spectrum_fasta_device workspace: the FASTA plan's descriptors and header state (sized for the smallest
-// unit VKIMG_FASTA_UNIT_BYTES allows), then the samples' tables
-struct FsLayout {
-    uint64_t* meta;
-    uint32_t *ukey, *carry;
-    uint64_t *block_base, *slot_base, *nslots;
-    size_t total;
-};
-
-FsLayout fs_layout(void* d_ws, const uint64_t* lengths, uint32_t nsamples) {
-    FsLayout L{};
-    uint64_t nunits = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) nunits += (lengths[i] + kFaLaneBytes - 1) / kFaLaneBytes;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.meta, 4ull * nsamples + 2);
-    take(L.ukey, nunits + 1);
-    take(L.carry, nunits + 1);
-    take(L.block_base, nsamples + 1ull);
-    take(L.slot_base, nsamples);
-    take(L.nslots, nsamples);
-    L.total = take.at;
-    return L;
-}
-
-}  // namespace
+// (the rules and fs_layout: vk_textplan.h; the table sequence is the spectrum's, above)
 
 extern "C" {
 
@@ -3579,14 +3375,11 @@ int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* o
         !d_status || !d_ws)
         return VK_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
-    std::vector<uint64_t> block_base(nsamples + 1ull, 0);
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        // (a sample of more than 2^33 bytes: a multiplicity is 32-bit)
-        if (offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i])) return VK_EINVAL;
-        block_base[i + 1] = block_base[i] + (nslots[i] + kSpSlotsPerBlock - 1) / kSpSlotsPerBlock;
-    }
-    if (block_base[nsamples] >= (1ull << 31)) return VK_EINVAL;
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples;
+    c.nslots = nslots, c.slot_base = slot_base, c.k = k, c.every = every;
+    std::vector<uint64_t> block_base;
+    if (int rc = spectrum_check(c, &block_base)) return rc;
     const FsLayout L = fs_layout(d_ws, lengths, nsamples);
     if (ws_bytes < L.total) return VK_EINVAL;
     FaPlan pl;
@@ -3594,58 +3387,26 @@ int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* o
     if (rc) return rc;
     VK_HIP(ctx, hipSetDevice(ctx->device));
     const auto* text = static_cast<const uint8_t*>(d_fasta);
-    // (pageable sources: a copy has read its source on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kSpNstat * sizeof(uint64_t), ctx->stream));
-    const FaMeta m = pl.on_device(L.meta);
-    rc = fa_header_state(ctx, text, pl, m, L.ukey, L.carry, d_status);
+    // (pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(L.f.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = sp_tables_put(ctx, L.t, block_base, slot_base, nslots, nsamples, d_rows);
     if (rc) return rc;
-    const dim3 tgrid(static_cast<uint32_t>(block_base[nsamples]));
-    auto* rows = reinterpret_cast<unsigned long long*>(d_rows);
-    hipLaunchKernelGGL(vk_sp_init_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots, d_keys,
-                       d_counts);
-    if (pl.nwg) {
-        const SpParams P{d_keys, d_counts, L.slot_base, L.nslots, static_cast<uint32_t>(k), every, 0u, 0u};
-        hipLaunchKernelGGL(vk_fs_count_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, L.carry, P,
-                           d_status, rows);
-    }
-    hipLaunchKernelGGL(vk_sp_hist_kernel, tgrid, dim3(kClThreads), 0, ctx->stream, L.block_base, nsamples, L.slot_base, L.nslots,
-                       d_counts, d_status, rows);
-    hipLaunchKernelGGL(vk_sp_finish_kernel, dim3(nsamples), dim3(kClThreads), 0, ctx->stream, d_status, rows);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
+    const FaMeta m = pl.on_device(L.f.meta);
+    rc = fa_header_state(ctx, text, pl, m, L.f.ukey, L.f.carry, d_status);
+    if (rc) return rc;
+    return sp_tables_run(ctx, L.t, block_base[nsamples], nsamples, d_keys, d_counts, d_status, d_rows, [&](unsigned long long* rows) {
+        if (!pl.nwg) return;
+        const SpParams P{d_keys, d_counts, L.t.slot_base, L.t.nslots, static_cast<uint32_t>(k), every, 0u, 0u};
+        hipLaunchKernelGGL(vk_fs_count_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, L.f.carry,
+                           P, d_status, rows);
+    });
 }
 
 }  // extern "C"
 
 // ------------------------------------------- reads kept by their k-mers' depth in the spectrum's tables (vk_depth.h) ------
 
-namespace {
-
-// the pieces of a vk_depth_device workspace: the screen's, then the samples' tables and bands
-struct DpLayout {
-    ScLayout s;
-    uint64_t *slot_base, *nslots;
-    uint32_t *lo, *hi;
-    size_t total;
-};
-
-DpLayout dp_layout(void* d_ws, const uint64_t* records, uint32_t nsamples, const uint64_t* lengths) {
-    DpLayout L{};
-    L.s = sc_layout(d_ws, records, nsamples, lengths);
-    WsTake take{static_cast<uint8_t*>(d_ws), L.s.total};
-    take(L.slot_base, nsamples);
-    take(L.nslots, nsamples);
-    take(L.lo, nsamples);
-    take(L.hi, nsamples);
-    L.total = take.at;
-    return L;
-}
-
-}  // namespace
+// (the rules and dp_layout: vk_textplan.h; the kept-text tail is the screen's)
 
 extern "C" {
 
@@ -3663,61 +3424,37 @@ int vk_depth_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, co
     if (!ctx || nsamples == 0 || !d_text || !offsets || !lengths || !records || !d_keys || !d_counts || !slot_base || !nslots ||
         !d_table_status || !lo || !hi || !d_out || !out_offsets || !d_out_lengths || !d_rows || !d_status || !d_ws)
         return VK_EINVAL;
-    if (k < static_cast<int>(kScMinK) || k > static_cast<int>(kScMaxK) || every < 1) return VK_EINVAL;
-    std::vector<uint64_t> rec_base(nsamples + 1ull, 0);
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if (offsets[i] % 16 || out_offsets[i] % 16 || lengths[i] > (1ull << 33) || !sc_slots_ok(nslots[i]) || lo[i] > hi[i])
-            return VK_EINVAL;
-        // (a region as large as the sample's input, before anything is written)
-        if (out_offsets[i] > out_capacity || (lengths[i] + 15) / 16 * 16 > out_capacity - out_offsets[i]) return VK_EINVAL;
-        rec_base[i + 1] = rec_base[i] + records[i];
-    }
-    const uint64_t nrec = rec_base[nsamples], nrblocks = (nrec + kScRecsPerBlock - 1) / kScRecsPerBlock;
-    if (nrblocks >= (1ull << 31)) return VK_EINVAL;
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.records = records, c.nsamples = nsamples;
+    c.nslots = nslots, c.slot_base = slot_base, c.out_offsets = out_offsets, c.out_capacity = out_capacity;
+    c.lo = lo, c.hi = hi, c.k = k, c.every = every;
+    if (int rc = depth_check(c)) return rc;
     const DpLayout L = dp_layout(d_ws, records, nsamples, lengths);
     if (ws_bytes < L.total) return VK_EINVAL;
-    // a sample is one file of the record index
-    std::vector<uint32_t> roles(nsamples, VK_CL_ROLE_UNPAIRED), owner(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i) owner[i] = i;
-    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nsamples, nsamples, ~0ull);
-    std::vector<EmSample> smp(nsamples);
-    for (uint32_t i = 0; i < nsamples; ++i)
-        smp[i] = EmSample{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
-                          i + 1 < nsamples ? ix.files[i + 1].chunk0 : ix.nchunks};
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const TextIndex t = text_index(offsets, lengths, records, nsamples);
+    const uint64_t nrec = t.rec_base[nsamples];
     const auto* text = static_cast<const uint8_t*>(d_text);
-    // (pageable sources: a copy has read its source on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.s.samples, smp.data(), nsamples * sizeof(EmSample), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.s.rec_base, rec_base.data(), rec_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.s.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.lo, lo, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.hi, hi, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kDpNstat * sizeof(uint64_t), ctx->stream));
-    int rc = cl_index_run(ctx, text, ix, L.s.c, nullptr, 0, nullptr, nullptr);
+    int rc = text_index_run(ctx, text, t, L.s.c, L.s.samples, L.s.rec_base, d_status, [&] {
+        VK_HIP(ctx, hipMemcpyAsync(L.s.out_offs, out_offsets, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.slot_base, slot_base, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.nslots, nslots, nsamples * 8ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.lo, lo, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemcpyAsync(L.hi, hi, nsamples * 4ull, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nsamples) * kDpNstat * sizeof(uint64_t), ctx->stream));
+        return VK_OK;
+    });
     if (rc) return rc;
-    const dim3 sgrid((nsamples + kClThreads - 1) / kClThreads);
-    hipLaunchKernelGGL(vk_em_status_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, text, L.s.samples, nsamples, L.s.c.recs,
-                       L.s.c.cprefix, d_status);
-    hipLaunchKernelGGL(vk_dp_status_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, d_table_status, nsamples, d_status);
-    const uint32_t nblocks = static_cast<uint32_t>(nrblocks);
+    hipLaunchKernelGGL(vk_dp_status_kernel, dim3((nsamples + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream,
+                       d_table_status, nsamples, d_status);
     if (nrec) {
         const DpParams P{d_keys, d_counts, L.slot_base, L.nslots, L.lo, L.hi, static_cast<uint32_t>(k), every,
                          ctx->spectrum_tile ? ctx->spectrum_tile : kScMaxTile, ctx->depth_merge};
-        hipLaunchKernelGGL(vk_dp_match_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.s.samples, L.s.rec_base,
-                           nsamples, nrec, L.s.c.recs, d_status, P, L.s.obytes, reinterpret_cast<unsigned long long*>(d_rows));
+        hipLaunchKernelGGL(vk_dp_match_kernel, dim3(static_cast<uint32_t>(text_record_blocks(nrec))), dim3(kClThreads), 0, ctx->stream,
+                           text, L.s.samples, L.s.rec_base, nsamples, nrec, L.s.c.recs, d_status, P, L.s.obytes,
+                           reinterpret_cast<unsigned long long*>(d_rows));
     }
     VK_HIP(ctx, hipGetLastError());
-    rc = cl_scan(ctx, L.s.obytes, nrec, L.s.c.sums, L.s.oprefix);
-    if (rc) return rc;
-    if (nrec)
-        hipLaunchKernelGGL(vk_sc_write_kernel, dim3(nblocks), dim3(kClThreads), 0, ctx->stream, text, L.s.rec_base, L.s.out_offs,
-                           nsamples, nrec, L.s.c.recs, L.s.oprefix, d_out);
-    hipLaunchKernelGGL(vk_sc_pad_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, L.s.rec_base, L.s.out_offs, nsamples, L.s.oprefix,
-                       d_out, d_out_lengths);
-    VK_HIP(ctx, hipGetLastError());
-    return VK_OK;
+    return kept_text_run(ctx, text, L.s, nsamples, nrec, d_out, d_out_lengths);
 }
 
 }  // extern "C"
@@ -3851,40 +3588,7 @@ int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_q
 
 // ------------------------------------------- quality profiles of FASTQ streams (vk_qc.h) ------
 
-namespace {
-
-// the pieces of a vk_qc_device workspace: the record index in vk_clean_device's layout (the pieces of it that
-// cl_index_run fills), then the streams' tables
-struct QcLayout {
-    ClLayout c;
-    QcStream* streams;
-    uint64_t* block_base;
-    uint32_t* bad;
-    size_t total;
-};
-
-QcLayout qc_layout(void* d_ws, const uint64_t* records, const uint64_t* lengths, uint32_t nstreams) {
-    QcLayout L{};
-    for (uint32_t i = 0; i < nstreams; ++i) {
-        L.c.nchunks += (lengths[i] + kClChunk - 1) / kClChunk;
-        L.c.nrec += records[i];
-    }
-    const uint64_t nb = (L.c.nchunks + kClScanBlock - 1) / kClScanBlock;
-    WsTake take{static_cast<uint8_t*>(d_ws), 0};
-    take(L.c.files, nstreams);
-    take(L.c.fchunk, nstreams);
-    take(L.c.ccount, L.c.nchunks);
-    take(L.c.cprefix, L.c.nchunks + 1);
-    take(L.c.sums, nb + 1);
-    take(L.c.recs, L.c.nrec);
-    take(L.streams, nstreams);
-    take(L.block_base, nstreams + 1ull);
-    take(L.bad, nstreams);
-    L.total = take.at;
-    return L;
-}
-
-}  // namespace
+// (the rules and qc_layout: vk_textplan.h)
 
 extern "C" {
 
@@ -3898,34 +3602,21 @@ int vk_qc_device(vk_ctx* ctx, const void* d_text, const uint64_t* offsets, const
                  uint32_t nstreams, uint64_t* d_rows, uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
     if (!ctx || nstreams == 0 || !d_text || !offsets || !lengths || !records || !d_rows || !d_status || !d_ws) return VK_EINVAL;
     const uint32_t per_block = ctx->qc_merge ? ctx->qc_merge : kQcMerge;
-    uint64_t nblocks = 0;
-    for (uint32_t i = 0; i < nstreams; ++i) {
-        // (a stream of 4 GiB or more: the lanes' sums and a record's lengths are 32-bit)
-        if (offsets[i] % 16 || lengths[i] >= (1ull << 32)) return VK_EINVAL;
-        nblocks += (records[i] + per_block - 1) / per_block;
-    }
-    if (nblocks >= (1ull << 31)) return VK_EINVAL;
+    TextCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.records = records, c.nsamples = nstreams;
+    std::vector<uint64_t> block_base;
+    if (int rc = qc_check(c, per_block, &block_base)) return rc;
+    const uint64_t nblocks = block_base[nstreams];
     const QcLayout L = qc_layout(d_ws, records, lengths, nstreams);
     if (ws_bytes < L.total) return VK_EINVAL;
-    // a stream is one file of the record index
-    std::vector<uint32_t> roles(nstreams, VK_CL_ROLE_UNPAIRED), owner(nstreams);
-    for (uint32_t i = 0; i < nstreams; ++i) owner[i] = i;
-    const ClIndex ix = cl_index(offsets, lengths, records, roles.data(), owner.data(), nstreams, nstreams, ~0ull);
-    std::vector<QcStream> str(nstreams);
-    std::vector<uint64_t> block_base(nstreams + 1ull, 0);
-    for (uint32_t i = 0; i < nstreams; ++i) {
-        str[i] = QcStream{offsets[i], lengths[i], ix.files[i].rec0, ix.files[i].nrec, ix.files[i].chunk0,
-                          i + 1 < nstreams ? ix.files[i + 1].chunk0 : ix.nchunks};
-        block_base[i + 1] = block_base[i] + (records[i] + per_block - 1) / per_block;
-    }
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const TextIndex t = text_index(offsets, lengths, records, nstreams);   // a stream is one file of the record index
     const auto* text = static_cast<const uint8_t*>(d_text);
-    // (pageable sources: a copy has read its source on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.streams, str.data(), nstreams * sizeof(QcStream), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(L.bad, 0, nstreams * sizeof(uint32_t), ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nstreams) * kQcNstat * sizeof(uint64_t), ctx->stream));
-    int rc = cl_index_run(ctx, text, ix, L.c, nullptr, 0, nullptr, nullptr);
+    int rc = text_index_run(ctx, text, t, L.c, L.streams, nullptr, nullptr, [&] {
+        VK_HIP(ctx, hipMemcpyAsync(L.block_base, block_base.data(), block_base.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(L.bad, 0, nstreams * sizeof(uint32_t), ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_rows, 0, static_cast<size_t>(nstreams) * kQcNstat * sizeof(uint64_t), ctx->stream));
+        return VK_OK;
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(vk_qc_status_kernel, dim3((nstreams + kClThreads - 1) / kClThreads), dim3(kClThreads), 0, ctx->stream, text,
                        L.streams, nstreams, L.c.cprefix, d_rows, d_status);

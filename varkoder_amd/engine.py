@@ -908,6 +908,23 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_clean_heads_device")
         return totals, counted
 
+    def _workspace(self, size_fn, *args):
+        """A workspace tensor of the size that `size_fn` (a vk_*_workspace_size) states for `args`, of 256 bytes at least."""
+        ws_bytes = C.c_uint64()
+        _capi.check(self.ctx, size_fn(*args, C.byref(ws_bytes)), size_fn.__name__)
+        torch = _torch()
+        return torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+
+    def _records(self, text, offs, lens, records, one_each=None):
+        """The samples' record counts in the C ABI's type: the caller's or, with None, every record of the text (clean_lines
+        here).  one_each: the caller's message when they are not one per sample (None: not checked)."""
+        if records is None:
+            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
+        recs = np.ascontiguousarray(records, dtype=np.uint64)
+        if one_each is not None and len(recs) != len(offs):
+            raise ValueError(one_each)
+        return recs
+
     def _clean_call(self, offsets, lengths, records, roles, samples, nsamples, size_fn):
         """What clean() and detect_adapters() do alike ahead of their call: the files' arrays in the C ABI's types, with
         their count, and a workspace tensor of the size `size_fn` (vk_clean_workspace_size or its detect twin) asks."""
@@ -918,11 +935,7 @@ class ImageEngine:
         n = len(offs)
         if not (len(recs) == len(roles) == len(samples) == n):
             raise ValueError("one record budget, role and sample per file")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, size_fn(_u64(lens), _u64(recs), n, nsamples, C.byref(ws_bytes)), size_fn.__name__)
-        torch = _torch()
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
-        return offs, lens, recs, roles, samples, n, ws
+        return offs, lens, recs, roles, samples, n, self._workspace(size_fn, _u64(lens), _u64(recs), n, nsamples)
 
     def detect_adapters(self, fastq, offsets, lengths, records, roles, samples, nsamples, trim_tail=10):
         """Each group's adapter detected from its first reads (vk_clean_detect_device; the files, records, roles and
@@ -1004,13 +1017,8 @@ class ImageEngine:
         ns = len(sidx)
         if not (len(seeds) == len(thr) == len(whole) == ns):
             raise ValueError("one sample, seed, threshold and whole flag per step")
-        if records is None:
-            records = (self.clean_lines(fastq, offs, lens) + np.uint64(1)) // np.uint64(4)
-        recs = np.ascontiguousarray(records, dtype=np.uint64)
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_ladder_emit_workspace_size(_u64(recs), n, _u64(lens), _u32(sidx), ns, C.byref(ws_bytes)),
-                    "vk_ladder_emit_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        recs = self._records(fastq, offs, lens, records)
+        ws = self._workspace(self.L.vk_ladder_emit_workspace_size, _u64(recs), n, _u64(lens), _u32(sidx), ns)
         out_offs = np.zeros(ns, dtype=np.uint64)
         out_lens = np.zeros(ns, dtype=np.uint64)
         status = np.zeros(n, dtype=np.uint32)
@@ -1045,9 +1053,7 @@ class ImageEngine:
             raise ValueError(f"the screen's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
         if length > _capi.VK_SCREEN_MAX_REF:   # (before anything is allocated)
             raise ValueError(f"a screen reference holds at most 2^30 sequence bytes: {length} bytes of text")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_screen_build_workspace_size(length, C.byref(ws_bytes)), "vk_screen_build_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.L.vk_screen_build_workspace_size, length)
         windows, distinct, status = C.c_uint64(), C.c_uint64(), C.c_uint32()
 
         def call(table, n):
@@ -1078,19 +1084,10 @@ class ImageEngine:
         n = len(offs)
         if int(min_hits) < 1:
             raise ValueError("min_hits is at least 1")
-        if records is None:
-            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
-        recs = np.ascontiguousarray(records, dtype=np.uint64)
-        if len(recs) != n:
-            raise ValueError("one record count per sample")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_screen_workspace_size(_u64(recs), n, _u64(lens), C.byref(ws_bytes)), "vk_screen_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
-        rounded = (lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)
-        out_offs = np.zeros(n, dtype=np.uint64)
-        if n > 1:
-            out_offs[1:] = np.cumsum(rounded[:-1])
-        total = int(rounded.sum()) + 16
+        recs = self._records(text, offs, lens, records, "one record count per sample")
+        ws = self._workspace(self.L.vk_screen_workspace_size, _u64(recs), n, _u64(lens))
+        out_offs, total = slots16(lens)
+        total += 16
         out = torch.empty(total, dtype=torch.uint8, device=self.device)
         out_lens = torch.empty(n, dtype=torch.int64, device=self.device)
         stats = torch.empty((n, 4), dtype=torch.int64, device=self.device)
@@ -1113,14 +1110,8 @@ class ImageEngine:
         n = len(offs)
         if n == 0:
             return np.zeros((0, _capi.VK_QC_NSTAT), dtype=np.uint64), np.zeros(0, dtype=np.uint32)
-        if records is None:
-            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
-        recs = np.ascontiguousarray(records, dtype=np.uint64)
-        if len(recs) != n:
-            raise ValueError("one record budget per stream")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_qc_workspace_size(_u64(recs), _u64(lens), n, C.byref(ws_bytes)), "vk_qc_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        recs = self._records(text, offs, lens, records, "one record budget per stream")
+        ws = self._workspace(self.L.vk_qc_workspace_size, _u64(recs), _u64(lens), n)
         rows = torch.empty((n, _capi.VK_QC_NSTAT), dtype=torch.int64, device=self.device)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
         st = self.L.vk_qc_device(self.ctx, self._ptr(text), _u64(offs), _u64(lens), _u64(recs), n, self._ptr(rows),
@@ -1158,6 +1149,57 @@ class ImageEngine:
                               "count a sample of the keys with a larger --spectrum-every") from e
         return group, g, nsl, base, keys, counts
 
+    def _spectrum_results(self, n, k, every, sketch):
+        """What spectrum() and spectrum_fasta() check and make alike ahead of their groups: k and every, the rows and status
+        of n samples and, with sketch=(s, m), the sketches' arrays.  Returns (k, every, rows, status, sk) with sk None or
+        (s, m, hashes, info)."""
+        k, every = int(k), int(every)
+        if not _capi.VK_SCREEN_MIN_K <= k <= _capi.VK_SCREEN_MAX_K:
+            raise ValueError(f"the spectrum's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
+        if every < 1:
+            raise ValueError("every is at least 1")
+        rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        sk = None
+        if sketch is not None:
+            sk_s, sk_m = self._sketch_args(*sketch)
+            sk = (sk_s, sk_m, np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64), np.zeros((n, 2), dtype=np.uint64))
+        return k, every, rows, status, sk
+
+    def _spectrum_groups(self, lens, every, slots, slots_rule, table_bytes, count, rows, status, sk, depth_step=None):
+        """The loop of spectrum() and spectrum_fasta() over their groups: a group's tables (_table_group), the call
+        (count(g, keys, counts, base, nsl, d_rows, d_status) returns the workspace it made, kept until the kernels are
+        waited for), the sketches while the tables lie there, the rows and status copied back, the depth step
+        (depth_step(group, g, keys, counts, base, nsl, d_status)), and the samples whose table filled queued again with four
+        times the slots.  slots_rule: spectrum_slots or spectrum_fasta_slots."""
+        torch = _torch()
+        n = len(lens)
+        if slots is None:
+            want = [slots_rule(x, every) for x in lens]
+            most = [slots_rule(x, 1) for x in lens]
+        else:
+            want = most = [int(slots)] * n
+        todo = list(range(n))
+        while todo:
+            group, g, nsl, base, keys, counts = self._table_group(todo, want, table_bytes)
+            d_rows = torch.empty((len(group), _capi.VK_SPEC_NSTAT), dtype=torch.int64, device=self.device)
+            d_status = torch.empty(len(group), dtype=torch.int32, device=self.device)
+            ws = count(g, keys, counts, base, nsl, d_rows, d_status)
+            # (the copies below wait for the kernels: the tables and the workspace are free after them)
+            if sk is not None:   # (while the tables lie there)
+                sk[2][g], sk[3][g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk[0], sk[1])
+            rows[g] = d_rows.cpu().numpy().view(np.uint64)
+            status[g] = d_status.cpu().numpy().astype(np.uint32)
+            if depth_step is not None:   # (while the tables lie there; the bands from the rows just read)
+                depth_step(group, g, keys, counts, base, nsl, d_status)
+            del keys, counts, ws
+            # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
+            # the slots -- a bounded loop over a status; at slots_rule(., 1) it cannot fill
+            again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
+            for i in again:
+                want[i] = min(4 * want[i], most[i])
+            todo = again + todo
+
     def spectrum(self, text, offs, lens, k=21, every=1, records=None, slots=None, table_bytes=16 << 30, sketch=None, depth=None):
         """The k-mer spectra of cleaned samples in HBM (vk_spectrum_device; the rule: INTEGRATION.md, "`--kmer-spectrum`:
         the rule"): sample i is text[offs[i] .. + lens[i]), k in 16..31, a key is taken when the high half of its mix is
@@ -1185,81 +1227,47 @@ class ImageEngine:
         torch = _torch()
         offs, lens = self._desc(offs, lens)
         n = len(offs)
-        k, every = int(k), int(every)
-        if not _capi.VK_SCREEN_MIN_K <= k <= _capi.VK_SCREEN_MAX_K:
-            raise ValueError(f"the spectrum's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
-        if every < 1:
-            raise ValueError("every is at least 1")
-        rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
-        status = np.zeros(n, dtype=np.uint32)
-        if sketch is not None:
-            sk_s, sk_m = self._sketch_args(*sketch)
-            hashes = np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64)
-            info = np.zeros((n, 2), dtype=np.uint64)
-        ret = lambda: (rows, status) + (() if sketch is None else (hashes, info)) + (() if depth is None else dp)   # noqa: E731
+        k, every, rows, status, sk = self._spectrum_results(n, k, every, sketch)
+        ret = lambda: (rows, status) + (() if sk is None else sk[2:]) + (() if depth is None else dp)   # noqa: E731
         if depth is not None:
             from . import depth as depth_rules
+            from . import spectrum as spectrum_rules
             asked = list(depth) if isinstance(depth, list) else [depth] * n
             if len(asked) != n:
                 raise ValueError("one band per sample")
             asked = [depth_rules.parse_band(b) if isinstance(b, str) else b for b in asked]
-            rounded = (lens + np.uint64(15)) // np.uint64(16) * np.uint64(16)
-            out_offs = np.zeros(n, dtype=np.uint64)
-            if n > 1:
-                out_offs[1:] = np.cumsum(rounded[:-1])
+            out_offs, total = slots16(lens)
             # (one text for all n samples, allocated once: a group writes its samples' regions)
-            out = torch.empty(int(rounded.sum()) + 16, dtype=torch.uint8, device=self.device)
+            out = torch.empty(total + 16, dtype=torch.uint8, device=self.device)
             out_lens = np.zeros(n, dtype=np.uint64)
             depth_rows = np.zeros((n, _capi.VK_DEPTH_NSTAT), dtype=np.uint64)
             bands = [None] * n
             dp = (out, out_offs, out_lens, depth_rows, bands)
         if n == 0:
             return ret()
-        if records is None:
-            records = (self.clean_lines(text, offs, lens) + np.uint64(1)) // np.uint64(4)
-        recs = np.ascontiguousarray(records, dtype=np.uint64)
-        if len(recs) != n:
-            raise ValueError("one record count per sample")
-        if slots is None:
-            want = [self.spectrum_slots(x, every) for x in lens]
-            most = [self.spectrum_slots(x, 1) for x in lens]
-        else:
-            want = most = [int(slots)] * n
-        todo = list(range(n))
-        while todo:
-            group, g, nsl, base, keys, counts = self._table_group(todo, want, table_bytes)
+        recs = self._records(text, offs, lens, records, "one record count per sample")
+
+        def count(g, keys, counts, base, nsl, d_rows, d_status):
             o, l, r = offs[g].copy(), lens[g].copy(), recs[g].copy()
-            ws_bytes = C.c_uint64()
-            _capi.check(self.ctx, self.L.vk_spectrum_workspace_size(_u64(r), len(group), _u64(l), C.byref(ws_bytes)),
-                        "vk_spectrum_workspace_size")
-            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
-            d_rows = torch.empty((len(group), _capi.VK_SPEC_NSTAT), dtype=torch.int64, device=self.device)
-            d_status = torch.empty(len(group), dtype=torch.int32, device=self.device)
-            st = self.L.vk_spectrum_device(self.ctx, self._ptr(text), _u64(o), _u64(l), _u64(r), len(group), k, every,
+            ws = self._workspace(self.L.vk_spectrum_workspace_size, _u64(r), len(g), _u64(l))
+            st = self.L.vk_spectrum_device(self.ctx, self._ptr(text), _u64(o), _u64(l), _u64(r), len(g), k, every,
                                            self._ptr(keys), self._ptr(counts), _u64(base), _u64(nsl), self._ptr(d_rows),
                                            self._ptr(d_status), self._ptr(ws), ws.numel())
             _capi.check(self.ctx, st, "vk_spectrum_device")
-            # (the copies below wait for the kernels: the tables and the workspace are free after them)
-            if sketch is not None:   # (while the tables lie there)
-                hashes[g], info[g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk_s, sk_m)
-            rows[g] = d_rows.cpu().numpy().view(np.uint64)
-            status[g] = d_status.cpu().numpy().astype(np.uint32)
-            if depth is not None:   # (while the tables lie there; the bands from the rows just read)
-                from . import spectrum as spectrum_rules
-                for i in group:
-                    b = asked[i]
-                    bands[i] = (depth_rules.resolve(b, spectrum_rules.estimate(rows[i], k, every))
-                                if isinstance(b, depth_rules.Band) else (int(b[0]), int(b[1]), True, None))
-                out_lens[g], depth_rows[g], _ = self.depth_filter(text, o, l, keys, counts, base, nsl, d_status,
-                                                                  [bands[i][0] for i in group], [bands[i][1] for i in group],
-                                                                  k, every, r, out, out_offs[g].copy())
-            del keys, counts, ws
-            # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
-            # the slots -- a bounded loop over a status; at spectrum_slots(., 1) it cannot fill
-            again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
-            for i in again:
-                want[i] = min(4 * want[i], most[i])
-            todo = again + todo
+            return ws
+
+        def depth_step(group, g, keys, counts, base, nsl, d_status):
+            for i in group:
+                b = asked[i]
+                bands[i] = (depth_rules.resolve(b, spectrum_rules.estimate(rows[i], k, every))
+                            if isinstance(b, depth_rules.Band) else (int(b[0]), int(b[1]), True, None))
+            out_lens[g], depth_rows[g], _ = self.depth_filter(text, offs[g].copy(), lens[g].copy(), keys, counts, base, nsl,
+                                                              d_status, [bands[i][0] for i in group],
+                                                              [bands[i][1] for i in group], k, every, recs[g].copy(), out,
+                                                              out_offs[g].copy())
+
+        self._spectrum_groups(lens, every, slots, self.spectrum_slots, table_bytes, count, rows, status, sk,
+                              depth_step if depth is not None else None)
         return ret()
 
     @staticmethod
@@ -1285,57 +1293,25 @@ class ImageEngine:
         sketch=(s, 1): also the samples' bottom-s MinHash sketches (sketch_tables), taken from each group's tables before
         they are freed -- a sample counted again from the attempt that succeeded.  Returns (rows, status, hashes
         uint64[n, s], info uint64[n, 2] = eligible, length) then.  Synchronises."""
-        torch = _torch()
         offs, lens = self._desc(offs, lens)
         n = len(offs)
-        k, every = int(k), int(every)
-        if not _capi.VK_SCREEN_MIN_K <= k <= _capi.VK_SCREEN_MAX_K:
-            raise ValueError(f"the spectrum's k is {_capi.VK_SCREEN_MIN_K}..{_capi.VK_SCREEN_MAX_K}: {k}")
-        if every < 1:
-            raise ValueError("every is at least 1")
-        rows = np.zeros((n, _capi.VK_SPEC_NSTAT), dtype=np.uint64)
-        status = np.zeros(n, dtype=np.uint32)
-        if sketch is not None:
-            sk_s, sk_m = self._sketch_args(*sketch)
-            if sk_m != 1:
-                raise ValueError("an assembly's sketch takes every k-mer: its minimum multiplicity is 1")
-            hashes = np.full((n, sk_s), np.uint64(2 ** 64 - 1), dtype=np.uint64)
-            info = np.zeros((n, 2), dtype=np.uint64)
-        ret = lambda: (rows, status) + (() if sketch is None else (hashes, info))   # noqa: E731
+        k, every, rows, status, sk = self._spectrum_results(n, k, every, sketch)
+        if sk is not None and sk[1] != 1:
+            raise ValueError("an assembly's sketch takes every k-mer: its minimum multiplicity is 1")
         if n == 0:
-            return ret()
-        if slots is None:
-            want = [self.spectrum_fasta_slots(x, every) for x in lens]
-            most = [self.spectrum_fasta_slots(x, 1) for x in lens]
-        else:
-            want = most = [int(slots)] * n
-        todo = list(range(n))
-        while todo:
-            group, g, nsl, base, keys, counts = self._table_group(todo, want, table_bytes)
+            return (rows, status) + (() if sk is None else sk[2:])
+
+        def count(g, keys, counts, base, nsl, d_rows, d_status):
             o, l = offs[g].copy(), lens[g].copy()
-            ws_bytes = C.c_uint64()
-            _capi.check(self.ctx, self.L.vk_spectrum_fasta_workspace_size(_u64(l), len(group), C.byref(ws_bytes)),
-                        "vk_spectrum_fasta_workspace_size")
-            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
-            d_rows = torch.empty((len(group), _capi.VK_SPEC_NSTAT), dtype=torch.int64, device=self.device)
-            d_status = torch.empty(len(group), dtype=torch.int32, device=self.device)
-            st = self.L.vk_spectrum_fasta_device(self.ctx, self._ptr(fasta), _u64(o), _u64(l), len(group), k, every,
+            ws = self._workspace(self.L.vk_spectrum_fasta_workspace_size, _u64(l), len(g))
+            st = self.L.vk_spectrum_fasta_device(self.ctx, self._ptr(fasta), _u64(o), _u64(l), len(g), k, every,
                                                  self._ptr(keys), self._ptr(counts), _u64(base), _u64(nsl), self._ptr(d_rows),
                                                  self._ptr(d_status), self._ptr(ws), ws.numel())
             _capi.check(self.ctx, st, "vk_spectrum_fasta_device")
-            # (the copies below wait for the kernels: the tables and the workspace are free after them)
-            if sketch is not None:   # (while the tables lie there)
-                hashes[g], info[g] = self.sketch_tables(keys, counts, base, nsl, d_status, sk_s, 1)
-            rows[g] = d_rows.cpu().numpy().view(np.uint64)
-            status[g] = d_status.cpu().numpy().astype(np.uint32)
-            del keys, counts, ws
-            # a table that filled (every > 1: the taken keys were more than their expected share): again with four times
-            # the slots -- a bounded loop over a status; at spectrum_fasta_slots(., 1) it cannot fill
-            again = [i for i in group if status[i] == _capi.VK_SPEC_TABLE_FULL and want[i] < most[i]]
-            for i in again:
-                want[i] = min(4 * want[i], most[i])
-            todo = again + todo
-        return ret()
+            return ws
+
+        self._spectrum_groups(lens, every, slots, self.spectrum_fasta_slots, table_bytes, count, rows, status, sk)
+        return (rows, status) + (() if sk is None else sk[2:])
 
     def depth_filter(self, text, offs, lens, keys, counts, base, nslots, table_status, lo, hi, k, every, records, out, out_offs):
         """Cleaned samples in HBM filtered record by record by their median k-mer depth in counting tables that lie in HBM
@@ -1357,9 +1333,7 @@ class ImageEngine:
             raise ValueError("one record count, base, slot count, status, band and output offset per sample")
         if n and int((base + nslots).max()) > min(int(keys.numel()), int(counts.numel())):
             raise ValueError("a sample's slots lie past the tables")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_depth_workspace_size(_u64(recs), n, _u64(lens), C.byref(ws_bytes)), "vk_depth_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.L.vk_depth_workspace_size, _u64(recs), n, _u64(lens))
         d_lens = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
         d_rows = torch.empty((max(n, 1), _capi.VK_DEPTH_NSTAT), dtype=torch.int64, device=self.device)
         d_status = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
@@ -1396,9 +1370,7 @@ class ImageEngine:
             raise ValueError("one base, one slot count and one status per sample")
         if n and int((base + nslots).max()) > min(int(keys.numel()), int(counts.numel())):
             raise ValueError("a sample's slots lie past the tables")
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_sketch_workspace_size(_u64(nslots), n, s, C.byref(ws_bytes)), "vk_sketch_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.L.vk_sketch_workspace_size, _u64(nslots), n, s)
         d_hashes = torch.empty((n, s), dtype=torch.int64, device=self.device)
         d_info = torch.empty((n, 2), dtype=torch.int64, device=self.device)
         st = self.L.vk_sketch_device(self.ctx, self._ptr(keys), self._ptr(counts), _u64(base), _u64(nslots), n, self._ptr(status),
@@ -1464,10 +1436,7 @@ class ImageEngine:
                 if g.shape != (count,):
                     raise ValueError("one group id per image")
                 groups[i] = torch.from_numpy(g.view(np.int32)).to(self.device)
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_dist_workspace_size(nq, nr, npix, n if 0 <= n < 2 ** 32 else 0, int(matrix), C.byref(ws_bytes)),
-                    "vk_dist_workspace_size")
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(self.L.vk_dist_workspace_size, nq, nr, npix, n if 0 <= n < 2 ** 32 else 0, int(matrix))
         idx = torch.empty((nq, n), dtype=torch.int32, device=self.device)
         d2 = torch.empty((nq, n), dtype=torch.int64, device=self.device)
         mat = torch.empty((nq, nr), dtype=torch.int64, device=self.device) if matrix else None
@@ -1497,10 +1466,8 @@ class ImageEngine:
         n = len(offs)
         if n == 0:
             return torch.empty(0, dtype=torch.uint8, device=self.device), offs, lens
-        ws_bytes = C.c_uint64()
-        _capi.check(self.ctx, self.L.vk_deflate_workspace_size(_u64(lens), n, C.byref(ws_bytes)), "vk_deflate_workspace_size")
+        ws = self._workspace(self.L.vk_deflate_workspace_size, _u64(lens), n)
         cap = self.deflate_bound(lens)
-        ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
         out = torch.empty(cap, dtype=torch.uint8, device=self.device)
         out_offs = np.zeros(n, dtype=np.uint64)
         out_lens = np.zeros(n, dtype=np.uint64)
@@ -1561,9 +1528,7 @@ class ImageEngine:
             base = int(offs[i0])
             cost = (ends[i0:] - base) + (np.arange(1, n - i0 + 1, dtype=np.int64) * int(ws1.value + 64))
             m = max(1, int(np.searchsorted(cost, PNG_CALL_BYTES, side="right")))
-            ws_bytes = C.c_uint64()
-            _capi.check(self.ctx, self.L.vk_unpng_workspace_size(side, m, C.byref(ws_bytes)), "vk_unpng_workspace_size")
-            ws = torch.empty(max(int(ws_bytes.value), 256), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(self.L.vk_unpng_workspace_size, side, m)
             end = int(ends[i0 + m - 1])
             dev = torch.zeros(end - base + 1024, dtype=torch.uint8, device=self.device)
             dev[:end - base].copy_(buf[base:end])
