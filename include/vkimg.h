@@ -802,7 +802,14 @@ int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* o
  * query i and reference j, with Sa and Sb their sketches: d_seen[i][j] = min(s, |Sa u Sb|) and d_shared[i][j] = the
  * number of values among the d_seen[i][j] smallest of Sa u Sb that lie in both, u32 each; empty against empty gives 0
  * and 0.  VK_EINVAL for a null pointer, s outside VK_SKETCH_MIN .. VK_SKETCH_MAX, nq or nr of 0 or above 2^20, or
- * nq * nr above 2^32.  Allocates nothing and does not synchronise. */
+ * nq * nr above 2^32.  Allocates nothing and does not synchronise.
+ *
+ * vk_sketch_pair_blocks_device: the same arguments and the same pair, its two counts split by BLOCK for `tree
+ * --replicates` ("`tree`: the rule").  A value h belongs to block h & 63 (the values are outputs of the
+ * mix, so their low bits are uniform).  d_seen[i][j][b] and d_shared[i][j][b], u32 [nq][nr][VK_SKETCH_BLOCKS]: among the
+ * min(s, |Sa u Sb|) smallest values of Sa u Sb, those of block b, and those of block b that lie in both; over b they sum
+ * to vk_sketch_pairs_device's d_seen[i][j] and d_shared[i][j].  VK_EINVAL as there, and for nq * nr above 2^26. */
+#define VK_SKETCH_BLOCKS 64u
 #define VK_SKETCH_MIN 64u
 #define VK_SKETCH_MAX (1u << 20)
 int vk_sketch_workspace_size(const uint64_t* nslots, uint32_t nsamples, uint32_t s, uint64_t* bytes);
@@ -811,6 +818,8 @@ int vk_sketch_device(vk_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_coun
                      uint64_t* d_hashes, uint64_t* d_info, void* d_ws, uint64_t ws_bytes);
 int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
                            const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen);
+int vk_sketch_pair_blocks_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
+                                 const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen);
 
 /* `image / query --kmer-spectrum --depth-filter`: cleaned reads kept by the depth of their own k-mers in their sample's
  * spectrum table, while that lies in HBM.  The rule is this project's ("`--depth-filter`: the rule", and
@@ -877,6 +886,47 @@ int vk_dist_workspace_size(uint64_t nq, uint64_t nr, uint64_t npix, uint32_t n_n
 int vk_dist_device(vk_ctx* ctx, const void* d_q, uint64_t nq, const void* d_r, uint64_t nr, uint64_t npix, const uint32_t* d_qgroup,
                    const uint32_t* d_rgroup, uint32_t n_neighbours, uint32_t* d_idx, uint64_t* d_d2, uint64_t* d_matrix, void* d_ws,
                    uint64_t ws_bytes);
+
+/* `tree`: neighbour joining of a batch of distance matrices, one record of joins and branch lengths per matrix.  There is
+ * no reference interface: neither the reference nor any other call here builds a tree, and the rule is this project's
+ * ("`tree`: the rule", and tests/tree_ref.py).
+ *
+ * d_dist: f64 [ntrees][n][n], 8-byte aligned; the call OVERWRITES it.  All arithmetic is IEEE double, one operation at a
+ * time in the order written below, never a fused multiply-add, so a record does not depend on the launch.  A matrix is
+ * valid when every entry is finite, >= 0 and <= 1e100, the diagonal is 0 and D[i][j] equals D[j][i] bit for bit; an
+ * invalid matrix gets d_status[t] = VK_TREE_BAD_VALUE and an all-zero record and disturbs no other tree of the call.
+ * Slots are 0 .. n - 1, all active at the start.  R[i] is the sum of D[i][k] over active k != i, taken as 256 partial
+ * sums -- partial p adds the entries with k % 256 == p in rising k, starting from +0.0 -- folded by p[t] += p[t + s] for
+ * s = 128, 64, .., 1.  A step with m > 3 active slots: over active i < j, Q = ((double)(m - 2) * D[i][j] - R[i]) - R[j];
+ * the joined pair has the smallest Q, ties going to the smaller i, then the smaller j.  Li = 0.5 * D[i][j] + (R[i] - R[j])
+ * / (2.0 * (double)(m - 2)) and Lj = D[i][j] - Li.  For every active k other than i and j, Du[k] = 0.5 * ((D[i][k] +
+ * D[j][k]) - D[i][j]) and R[k] = ((R[k] - D[i][k]) - D[j][k]) + Du[k].  The new node takes slot i (Du becomes its row and
+ * column, the diagonal stays 0), slot j goes inactive, and R[i] is taken afresh by the 256-partial rule.
+ *
+ * d_nodes u32 and d_lengths f64, [ntrees][2 (n - 3) + 3]: step t writes i and j at 2t and 2t + 1 of d_nodes and Li and Lj
+ * at the same places of d_lengths; the last three active slots a < b < c close the record with La = 0.5 * ((D[a][b] +
+ * D[a][c]) - D[b][c]), Lb = 0.5 * ((D[a][b] + D[b][c]) - D[a][c]), Lc = 0.5 * ((D[a][c] + D[b][c]) - D[a][b]).  Lengths are
+ * recorded as computed, negative ones included.  n = 3 has no step: the record is the closing three.
+ *
+ * d_ws: caller-allocated device workspace of vk_tree_workspace_size bytes (same n and ntrees), 16-byte aligned.
+ * VK_EINVAL for a null pointer, n outside VK_TREE_MIN_LEAVES .. VK_TREE_MAX_LEAVES, ntrees of 0 or above
+ * VK_TREE_MAX_TREES, a misaligned d_dist or d_ws, or a workspace that is too small.  The call is 2 (n - 3) + 2 launches
+ * enqueued on the context's stream; it allocates nothing, reads no device value on the host and does not synchronise. */
+#define VK_TREE_MIN_LEAVES 3u
+#define VK_TREE_MAX_LEAVES 16384u
+#define VK_TREE_MAX_TREES 4096u
+#define VK_TREE_BAD_VALUE 1u
+int vk_tree_workspace_size(uint32_t n, uint32_t ntrees, uint64_t* bytes);
+int vk_tree_nj_device(vk_ctx* ctx, double* d_dist /* [ntrees][n][n], overwritten */, uint32_t n, uint32_t ntrees,
+                      uint32_t* d_nodes /* [ntrees][2(n-3)+3] */, double* d_lengths /* [ntrees][2(n-3)+3] */,
+                      uint32_t* d_status /* [ntrees] */, void* d_ws, uint64_t ws_bytes);
+
+/* Measurement (tools/tree_time.py): vk_tree_nj_device's first launch, which checks the matrices and sums their rows, and
+ * then `launches` times the search launch of its first step (all n >= 4 slots active), nothing else; d_dist is only
+ * read.  The time of a call with many launches less that of a call with few, over the difference, is the search alone.
+ * Arguments and VK_EINVAL as there.  Does not synchronise. */
+int vk_tree_search_probe_device(vk_ctx* ctx, const double* d_dist, uint32_t n, uint32_t ntrees, uint32_t launches,
+                                uint32_t* d_status, void* d_ws, uint64_t ws_bytes);
 
 /* Introspection used by bench.py / tests: workgroups and LDS bytes of the last
  * vk_count_device launch. */

@@ -24,7 +24,8 @@ VK_SCREEN_MAX_REF, VK_SCREEN_MIN_SLOTS, VK_SCREEN_MIN_K, VK_SCREEN_MAX_K = 1 << 
 VK_QC_BAD_FRAMING, VK_QC_CYCLES, VK_QC_NSTAT = 16, 1024, 11461
 VK_QC_QUAL_HIST, VK_QC_READQ_HIST, VK_QC_LEN_HIST, VK_QC_CYCLE_BASE, VK_QC_CYCLE_QSUM = 8, 102, 196, 1221, 6341
 VK_SPEC_NSTAT, VK_SPEC_HIST, VK_SPEC_TABLE_FULL = 261, 5, 32
-VK_SKETCH_MIN, VK_SKETCH_MAX = 64, 1 << 20
+VK_SKETCH_MIN, VK_SKETCH_MAX, VK_SKETCH_BLOCKS = 64, 1 << 20, 64
+VK_TREE_MIN_LEAVES, VK_TREE_MAX_LEAVES, VK_TREE_MAX_TREES, VK_TREE_BAD_VALUE = 3, 16384, 4096, 1
 VK_DEPTH_NSTAT, VK_DEPTH_HIST = 261, 5
 VK_DIST_NO_GROUP, VK_DIST_NO_IDX, VK_DIST_NO_D2, VK_DIST_MAX_NEIGHBOURS = 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 64
 VK_UNPNG_BAD_STREAM,VK_UNPNG_TRUNCATED, VK_UNPNG_BAD_SIZE, VK_UNPNG_BAD_ADLER, VK_UNPNG_BAD_FILTER = 1, 2, 4, 8, 16
@@ -47,7 +48,8 @@ SYMBOLS = ("vk_abi_version", "vk_strerror", "vk_last_hip_error", "vk_ctx_create"
            "vk_screen_workspace_size", "vk_screen_device", "vk_qc_workspace_size", "vk_qc_device",
            "vk_spectrum_workspace_size", "vk_spectrum_device",
            "vk_spectrum_fasta_workspace_size", "vk_spectrum_fasta_device",
-           "vk_sketch_workspace_size", "vk_sketch_device", "vk_sketch_pairs_device",
+           "vk_sketch_workspace_size", "vk_sketch_device", "vk_sketch_pairs_device", "vk_sketch_pair_blocks_device",
+           "vk_tree_workspace_size", "vk_tree_nj_device", "vk_tree_search_probe_device",
            "vk_depth_workspace_size", "vk_depth_device",
            "vk_dist_workspace_size", "vk_dist_device", "vk_last_count_pull")
 
@@ -156,6 +158,10 @@ def lib():
     L.vk_sketch_workspace_size.argtypes = [u64p, C.c_uint32, C.c_uint32, u64p]
     L.vk_sketch_device.argtypes = [vp, vp, vp, u64p, u64p, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64]
     L.vk_sketch_pairs_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, vp, vp]
+    L.vk_sketch_pair_blocks_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, vp, vp]
+    L.vk_tree_workspace_size.argtypes = [C.c_uint32, C.c_uint32, u64p]
+    L.vk_tree_nj_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64]
+    L.vk_tree_search_probe_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64]
     L.vk_depth_workspace_size.argtypes = [u64p, C.c_uint32, u64p, u64p]
     L.vk_depth_device.argtypes = [vp, vp, u64p, u64p, u64p, C.c_uint32, C.c_int, C.c_uint32, vp, vp, u64p, u64p, vp, u32p, u32p, vp,
                                   u64p, C.c_uint64, vp, vp, vp, vp, C.c_uint64]

@@ -283,6 +283,41 @@ def setup_parser():
                    help="also write every pair: shared.npy, seen.npy (uint32), corrected_distance.npy (float64, NaN where "
                         "there is none) with distances_rows.txt and distances_cols.txt.")
     d.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
+    t = sub.add_parser("tree", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                       usage="%(prog)s SPECTRA OUT [--distance corrected|mash] [--jukes-cantor] [--replicates R] [--seed N] "
+                             "[--no-negative-branches] [-x]\n       %(prog)s --matrix-from DIR OUT [--no-negative-branches] [-x]",
+                       help="A neighbour-joining tree of the sketched samples of a folder (as `distance` reads it), or of "
+                            "a matrix that `distance --matrix` or `compare --matrix` wrote; every matrix is joined on the "
+                            "GPU (not in the reference; rule and limits: INTEGRATION.md, \"`tree`: the rule\"). Writes "
+                            "tree.nwk (Newick, unrooted) and tree.json (the join record and every split's support).")
+    t.add_argument("paths", nargs="+", metavar="PATH",
+                   help="SPECTRA OUT: the folder with the samples' .spectrum.json and .sketch.npy files, and the folder "
+                        "where tree.nwk and tree.json will be written. With --matrix-from: OUT alone.")
+    t.add_argument("--matrix-from", metavar="DIR",
+                   help="join the square matrix of DIR instead: corrected_distance.npy (`distance --matrix`) or "
+                        "distances.npy (`compare --matrix`, uint64, refused above 2^53) with distances_rows.txt and "
+                        "distances_cols.txt, which must agree. No replicates in this mode.")
+    t.add_argument("--distance", choices=("corrected", "mash"), default="corrected",
+                   help="the distance of every pair: the depth-corrected one or the Mash distance (`distance` writes "
+                        "both). A pair without one (nothing seen, a sample without estimates) is refused by name.")
+    t.add_argument("--jukes-cantor", action="store_true", default=False,
+                   help="transform every distance D to -0.75 ln(1 - 4D/3), substitutions per site under Jukes and "
+                        "Cantor's model; a D of 0.75 or more is refused by name.")
+    t.add_argument("--replicates", type=int, default=0, metavar="R",
+                   help="support values from R delete-half jackknife replicates: each keeps 32 of the 64 blocks the "
+                        "sketch values fall into (by their low 6 bits) and builds its tree from the kept blocks' counts; "
+                        "an inner node is labelled with the percentage of replicate trees that hold its split. This "
+                        "measures the sampling variance of the SKETCH, not variance among reads or loci: a split can be "
+                        "well supported and wrong, and support rises with the sketch size. A replicate with an undefined "
+                        "distance is dropped and counted; more than half dropped is refused. At most 4095.")
+    t.add_argument("--seed", type=int, default=1, metavar="N",
+                   help="seed of the replicates' block choice (a generator written out in tree.py: the same blocks with "
+                        "every NumPy).")
+    t.add_argument("--no-negative-branches", action="store_true", default=False,
+                   help="in tree.nwk set a negative length of a joined pair to 0 and give the difference to its sibling "
+                        "(Kuhner and Felsenstein 1994: the path through the pair keeps its length); tree.json keeps the "
+                        "lengths as computed.")
+    t.add_argument("-x", "--overwrite", action="store_true", help="overwrite existing results.")
     return main
 
 
@@ -463,6 +498,20 @@ def parse_args(argv=None):
     if args.command == "distance":
         if args.neighbours < 1:
             parser.error("-N/--neighbours: at least 1")
+        return args
+    if args.command == "tree":
+        want = 1 if args.matrix_from else 2
+        if len(args.paths) != want:
+            parser.error("tree: --matrix-from DIR OUT, or SPECTRA OUT")
+        args.input, args.outdir = (args.matrix_from, args.paths[0]) if args.matrix_from else args.paths   # (input: what must exist)
+        if args.matrix_from and args.replicates:
+            parser.error("--replicates: not with --matrix-from (a matrix carries no sketch to resample)")
+        if args.matrix_from and args.jukes_cantor:
+            parser.error("--jukes-cantor: not with --matrix-from (the matrix is joined as it is)")
+        if not 0 <= args.replicates <= 4095:
+            parser.error("--replicates: 0 to 4095")
+        if not 0 <= args.seed < 2 ** 64:
+            parser.error("--seed: 0 to 2^64 - 1")
         return args
     if args.command == "query" and args.from_raw and args.images:
         parser.error("--from-raw: not with -I/--images")
@@ -1245,6 +1294,9 @@ def main(argv=None):
     elif args.command == "distance":
         from .distance import run_distance
         run_distance(args)
+    elif args.command == "tree":
+        from .tree import run_tree
+        run_tree(args)
     eprint("DONE")
 
 

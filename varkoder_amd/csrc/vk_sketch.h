@@ -22,8 +22,10 @@
 //                           buffer of the call, a level past a sample's candidates copies
 //   vk_sk_finish_kernel     the first `length` candidates to the row, eligible and length to d_info
 // vk_sketch_pairs_device is vk_sk_pairs_kernel alone: a wavefront per pair cuts the two-list merge into 64 diagonals.
+// vk_sketch_pair_blocks_device is vk_sk_pair_blocks_kernel alone: the same pair, its counts split by the block h & 63 of
+// each value (`tree --replicates`: the delete-half jackknife sums the blocks it keeps).
 //
-// The lane-local code (sk_eligible, sk_under, sk_digit, sk_candidate, sk_diag, sk_walk, sk_merge) compiles for the host:
+// The lane-local code (sk_eligible, sk_under, sk_digit, sk_candidate, sk_diag, sk_walk, sk_walk_blocks, sk_merge) compiles for the host:
 // tests/emul/sketch_emul.cpp runs it, a lane at a time, against tests/sketch_ref.py.
 #ifndef VK_SKETCH_H
 #define VK_SKETCH_H
@@ -46,6 +48,8 @@ constexpr uint64_t kSkMinPerBlock = kSpSlotsPerBlock;        // slots per workgr
 constexpr uint64_t kSkMaxBlocksPerSample = 1024;
 constexpr uint32_t kSkAll = 0, kSkUpTo = 1, kSkStrict = 2;   // SkState::mode
 constexpr uint64_t kSkMaxSide = 1ull << 20, kSkMaxPairs = 1ull << 32;
+constexpr uint32_t kSkBlocks = 64;                           // jackknife blocks: a value h lies in block h & 63
+constexpr uint64_t kSkMaxBlockPairs = 1ull << 26;            // pairs of a vk_sketch_pair_blocks_device call
 
 __device__ inline bool sk_eligible(uint64_t key, uint32_t count, uint32_t min_count) { return key != kScEmpty && count >= min_count; }
 
@@ -89,6 +93,30 @@ __device__ inline void sk_walk(const uint64_t* A, uint32_t la, const uint64_t* B
     }
     *distinct = nd;
     *dups = du;
+}
+
+// The walk once more, for the per-block counts of the jackknife (block of a value h: h & 63): every distinct value whose
+// ordinal -- base and the distinct values up to it, itself included -- is at most limit goes to seen(h), every duplicate
+// that sk_walk would count to shared(h).
+template <class Seen, class Shared>
+__device__ inline void sk_walk_blocks(const uint64_t* A, uint32_t la, const uint64_t* B, uint32_t lb, uint32_t i, uint32_t j,
+                                      uint32_t steps, uint64_t base, uint64_t limit, Seen seen, Shared shared) {
+    uint32_t nd = 0;
+    for (uint32_t t = 0; t < steps; ++t) {
+        if (j >= lb || (i < la && A[i] <= B[j])) {
+            ++nd;
+            if (base + nd <= limit) seen(A[i]);
+            ++i;
+        } else {
+            if (i > 0u && A[i - 1u] == B[j]) {
+                if (base + nd <= limit) shared(B[j]);
+            } else {
+                ++nd;
+                if (base + nd <= limit) seen(B[j]);
+            }
+            ++j;
+        }
+    }
 }
 
 // n values of the merge from (i, j) on to out (n <= la - i + lb - j)
@@ -369,6 +397,50 @@ __global__ void __launch_bounds__(kClThreads) vk_sk_pairs_kernel(const uint64_t*
     if (lane == 0) {
         shared[pair] = mine;
         seen[pair] = sn;
+    }
+}
+
+// vk_sk_pairs_kernel's pair, counted per block: the same diagonals, scan and stop; then every lane whose segment begins at
+// or before the stop walks it again and adds into its wave's 2 x 64 counters in LDS.  Lane b writes block b.
+__global__ void __launch_bounds__(kClThreads) vk_sk_pair_blocks_kernel(const uint64_t* q, const uint64_t* qlen, uint32_t nq,
+                                                                      const uint64_t* r, const uint64_t* rlen, uint32_t nr, uint32_t s,
+                                                                      uint32_t* shared, uint32_t* seen) {
+    __shared__ uint32_t s_ctr[kSkPairsPerBlock][2][kSkBlocks];
+    const uint32_t wave = sc_uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint64_t pair = static_cast<uint64_t>(blockIdx.x) * kSkPairsPerBlock + wave;
+    const bool valid = pair < static_cast<uint64_t>(nq) * nr;   // (the wave's)
+    s_ctr[wave][0][lane] = 0;
+    s_ctr[wave][1][lane] = 0;
+    __syncthreads();
+    if (valid) {
+        const uint32_t qi = sc_uniform(static_cast<uint32_t>(pair / nr)), ri = sc_uniform(static_cast<uint32_t>(pair % nr));
+        const uint64_t qn = qlen[qi], rn = rlen[ri];
+        const uint32_t la = sc_uniform(static_cast<uint32_t>(qn < s ? qn : s)), lb = sc_uniform(static_cast<uint32_t>(rn < s ? rn : s));
+        const uint64_t* A = q + static_cast<uint64_t>(s) * qi;
+        const uint64_t* B = r + static_cast<uint64_t>(s) * ri;
+        const uint32_t n = la + lb, seg = (n + 63u) / 64u;
+        const uint32_t d0 = min(lane * seg, n), d1 = min(d0 + seg, n);
+        const uint32_t i0 = sk_diag(A, la, B, lb, d0);
+        uint32_t distinct, dups;
+        sk_walk(A, la, B, lb, i0, d0 - i0, d1 - d0, 0, ~0ull, &distinct, &dups);
+        uint32_t incl = distinct;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t t = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += t;
+        }
+        const uint32_t all = sc_uniform(static_cast<uint32_t>(__shfl(incl, 63, 64)));
+        const uint32_t sn = all < s ? all : s, excl = incl - distinct;
+        uint32_t* c_shared = s_ctr[wave][0];
+        uint32_t* c_seen = s_ctr[wave][1];
+        if (excl <= sn)
+            sk_walk_blocks(A, la, B, lb, i0, d0 - i0, d1 - d0, excl, sn,
+                           [c_seen](uint64_t h) { atomicAdd(c_seen + (h & (kSkBlocks - 1u)), 1u); },
+                           [c_shared](uint64_t h) { atomicAdd(c_shared + (h & (kSkBlocks - 1u)), 1u); });
+    }
+    __syncthreads();
+    if (valid) {
+        shared[pair * kSkBlocks + lane] = s_ctr[wave][0][lane];
+        seen[pair * kSkBlocks + lane] = s_ctr[wave][1][lane];
     }
 }
 

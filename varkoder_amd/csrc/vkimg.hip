@@ -36,6 +36,7 @@
 //   vk_sp_*_kernel (vk_spectrum.h): the k-mer spectrum of cleaned reads (`--kmer-spectrum`): wave per record, scattered atomics into a counting table in HBM, its histogram.
 //   vk_fs_count_kernel (vk_fasta_spectrum.h): the k-mer spectrum of assemblies (`--genome-spectrum`): the same tables filled straight from FASTA text, lane per 64 bytes, windows rolled from registers.
 //   vk_sk_*_kernel (vk_sketch.h): bottom-s MinHash sketches from the spectrum's tables (`--spectrum-sketch`: radix select, compaction, LDS runs, merge path) and all pairs of sketches compared (`distance`: a wavefront per pair).
+//   vk_tr_*_kernel (vk_tree.h): neighbour-joining trees of a batch of distance matrices (`tree`): per step a search of the upper triangle by tiles and strips, then a workgroup per tree that joins.
 //   vk_sc_*_kernel (vk_screen.h): reads screened against a reference's k-mer set (`--exclude-fasta`, `--keep-fasta`): wave per record, probes of a table in HBM.
 #include <hip/hip_runtime.h>
 
@@ -85,6 +86,7 @@
 #include "vk_qc.h"
 #include "vk_textplan.h"
 #include "vk_dist.h"
+#include "vk_tree.h"
 
 // ---------------------------------------------------------------- C ABI ------
 
@@ -3584,6 +3586,18 @@ int vk_sketch_pairs_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_q
     return VK_OK;
 }
 
+int vk_sketch_pair_blocks_device(vk_ctx* ctx, const uint64_t* d_q, const uint64_t* d_qlen, uint64_t nq, const uint64_t* d_r,
+                                 const uint64_t* d_rlen, uint64_t nr, uint32_t s, uint32_t* d_shared, uint32_t* d_seen) {
+    if (!ctx || !d_q || !d_qlen || !d_r || !d_rlen || !d_shared || !d_seen || s < kSkMinS || s > kSkMaxS) return VK_EINVAL;
+    if (nq < 1 || nr < 1 || nq > kSkMaxSide || nr > kSkMaxSide || nq * nr > kSkMaxBlockPairs) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t blocks = (nq * nr + kSkPairsPerBlock - 1) / kSkPairsPerBlock;   // (2^24 at most)
+    hipLaunchKernelGGL(vk_sk_pair_blocks_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kClThreads), 0, ctx->stream, d_q, d_qlen,
+                       static_cast<uint32_t>(nq), d_r, d_rlen, static_cast<uint32_t>(nr), s, d_shared, d_seen);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------- quality profiles of FASTQ streams (vk_qc.h) ------
@@ -3702,6 +3716,85 @@ int vk_dist_device(vk_ctx* ctx, const void* d_q, uint64_t nq, const void* d_r, u
         hipLaunchKernelGGL(vk_dist_select_kernel, dim3(rows), dim3(kDistSelThreads), 0, ctx->stream, L.strip, q0,
                            static_cast<uint32_t>(nr), d_qgroup, d_rgroup, n_neighbours, bits, d_idx, d_d2);
     }
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------- neighbour-joining trees of distance matrices (vk_tree.h) ------
+
+namespace {
+
+// the pieces of a vk_tree_nj_device workspace
+struct TrLayout {
+    double* R;          // [ntrees][n], -inf for a retired slot
+    TrBest* parts;      // [ntrees][strips][tiles]: the search workgroups' candidates
+    uint32_t tiles, strips;
+    size_t total;
+};
+
+bool tr_args_ok(uint32_t n, uint32_t ntrees) {
+    return n >= kTrMinLeaves && n <= kTrMaxLeaves && ntrees >= 1 && ntrees <= kTrMaxTrees;
+}
+
+TrLayout tr_layout(void* d_ws, uint32_t n, uint32_t ntrees) {
+    TrLayout L{};
+    L.tiles = (n + kTrTile) / kTrTile;   // (columns 0 .. n: a lane's pair of an odd row begins one column early)
+    L.strips = (n - 1 + kTrStrip - 1) / kTrStrip;
+    WsTake take{static_cast<uint8_t*>(d_ws), 0};
+    take(L.R, static_cast<size_t>(ntrees) * n);
+    take(L.parts, static_cast<size_t>(ntrees) * L.tiles * L.strips);
+    L.total = take.at;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_tree_workspace_size(uint32_t n, uint32_t ntrees, uint64_t* bytes) {
+    if (!bytes || !tr_args_ok(n, ntrees)) return VK_EINVAL;
+    *bytes = tr_layout(nullptr, n, ntrees).total;
+    return VK_OK;
+}
+
+int vk_tree_nj_device(vk_ctx* ctx, double* d_dist, uint32_t n, uint32_t ntrees, uint32_t* d_nodes, double* d_lengths,
+                      uint32_t* d_status, void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || !d_dist || !d_nodes || !d_lengths || !d_status || !d_ws || !tr_args_ok(n, ntrees)) return VK_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_dist) & 7u) || (reinterpret_cast<uintptr_t>(d_ws) & 15u)) return VK_EINVAL;
+    const TrLayout L = tr_layout(d_ws, n, ntrees);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    const size_t rec = static_cast<size_t>(ntrees) * tr_record_len(n);
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipMemsetAsync(d_status, 0, static_cast<size_t>(ntrees) * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_nodes, 0, rec * sizeof(uint32_t), ctx->stream));
+    VK_HIP(ctx, hipMemsetAsync(d_lengths, 0, rec * sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(vk_tr_init_kernel, dim3(n, ntrees), dim3(kClThreads), 0, ctx->stream, d_dist, n, L.R, d_status);
+    const dim3 sgrid(L.tiles, L.strips, ntrees);
+    for (uint32_t step = 0; step + 3 < n; ++step) {   // m = n - step active slots
+        hipLaunchKernelGGL(vk_tr_search_kernel, sgrid, dim3(kClThreads), 0, ctx->stream, d_dist, n, n - step, L.R, d_status, L.R,
+                           L.parts);
+        hipLaunchKernelGGL(vk_tr_join_kernel, dim3(ntrees), dim3(kClThreads), 0, ctx->stream, d_dist, n, n - step, step, L.R, d_status,
+                           L.parts, L.tiles * L.strips, d_nodes, d_lengths);
+    }
+    hipLaunchKernelGGL(vk_tr_close_kernel, dim3(ntrees), dim3(kClThreads), 0, ctx->stream, d_dist, n, L.R, d_status, d_nodes, d_lengths);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+int vk_tree_search_probe_device(vk_ctx* ctx, const double* d_dist, uint32_t n, uint32_t ntrees, uint32_t launches, uint32_t* d_status,
+                                void* d_ws, uint64_t ws_bytes) {
+    if (!ctx || !d_dist || !d_status || !d_ws || !tr_args_ok(n, ntrees) || n < 4) return VK_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_dist) & 7u) || (reinterpret_cast<uintptr_t>(d_ws) & 15u)) return VK_EINVAL;
+    const TrLayout L = tr_layout(d_ws, n, ntrees);
+    if (ws_bytes < L.total) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    VK_HIP(ctx, hipMemsetAsync(d_status, 0, static_cast<size_t>(ntrees) * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(vk_tr_init_kernel, dim3(n, ntrees), dim3(kClThreads), 0, ctx->stream, d_dist, n, L.R, d_status);
+    for (uint32_t i = 0; i < launches; ++i)
+        hipLaunchKernelGGL(vk_tr_search_kernel, dim3(L.tiles, L.strips, ntrees), dim3(kClThreads), 0, ctx->stream, d_dist, n, n, L.R,
+                           d_status, L.R, L.parts);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
 }

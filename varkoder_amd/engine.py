@@ -1407,6 +1407,71 @@ class ImageEngine:
         _capi.check(self.ctx, st, "vk_sketch_pairs_device")
         return shared.cpu().numpy().view(np.uint32), seen.cpu().numpy().view(np.uint32)
 
+    def sketch_pair_blocks(self, q, qlen, r, rlen, s):
+        """sketch_pairs with both counts split by block (vk_sketch_pair_blocks_device; `tree --replicates`): a value h
+        belongs to block h & 63.  Returns (shared uint32[nq, nr, 64], seen uint32[nq, nr, 64]); over the last axis they
+        sum to sketch_pairs' two outputs.  nq * nr is at most 2^26.  Synchronises."""
+        torch = _torch()
+        s = self._sketch_args(s, 1)[0]
+
+        def up(h, ln):
+            h = np.ascontiguousarray(h, dtype=np.uint64)
+            ln = np.ascontiguousarray(ln, dtype=np.uint64)
+            if h.ndim != 2 or h.shape[1] != s or ln.shape != (h.shape[0],):
+                raise ValueError(f"sketches are uint64 [n, {s}] with one length each")
+            if len(ln) and int(ln.max()) > s:
+                raise ValueError("a sketch is longer than its row")
+            return (torch.from_numpy(h.view(np.int64)).to(self.device), torch.from_numpy(ln.view(np.int64)).to(self.device))
+        dq, dql = up(q, qlen)
+        dr, drl = (dq, dql) if r is q else up(r, rlen)
+        nq, nr, nb = int(dq.shape[0]), int(dr.shape[0]), _capi.VK_SKETCH_BLOCKS
+        if nq == 0 or nr == 0:
+            return np.zeros((nq, nr, nb), dtype=np.uint32), np.zeros((nq, nr, nb), dtype=np.uint32)
+        if nq * nr > 1 << 26:
+            raise ValueError(f"per-block counts of at most 2^26 pairs in a call: {nq} x {nr}")
+        shared = torch.empty((nq, nr, nb), dtype=torch.int32, device=self.device)
+        seen = torch.empty((nq, nr, nb), dtype=torch.int32, device=self.device)
+        st = self.L.vk_sketch_pair_blocks_device(self.ctx, self._ptr(dq), self._ptr(dql), nq, self._ptr(dr), self._ptr(drl), nr, s,
+                                                 self._ptr(shared), self._ptr(seen))
+        _capi.check(self.ctx, st, "vk_sketch_pair_blocks_device")
+        return shared.cpu().numpy().view(np.uint32), seen.cpu().numpy().view(np.uint32)
+
+    def nj(self, dist):
+        """Neighbour-joining trees of a batch of distance matrices (vk_tree_nj_device; the rule: INTEGRATION.md, "`tree`:
+        the rule"): dist float64 [ntrees, n, n] or [n, n] (a NumPy array, left as it is).  Returns (status uint32[ntrees]:
+        0 or VK_TREE_BAD_VALUE, nodes uint32[ntrees, 2 (n - 3) + 3], lengths float64 of the same shape): step t joined
+        slots nodes[2t] < nodes[2t + 1] with those branch lengths, the last three entries are the closing slots; a matrix
+        with a status has an all-zero record.  Synchronises."""
+        torch = _torch()
+        d = np.ascontiguousarray(dist, dtype=np.float64)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1] != d.shape[2]:
+            raise ValueError("distance matrices are float64 [ntrees, n, n]")
+        ntrees, n = int(d.shape[0]), int(d.shape[1])
+        if not _capi.VK_TREE_MIN_LEAVES <= n <= _capi.VK_TREE_MAX_LEAVES or not 1 <= ntrees <= _capi.VK_TREE_MAX_TREES:
+            raise ValueError(f"a tree has {_capi.VK_TREE_MIN_LEAVES}..{_capi.VK_TREE_MAX_LEAVES} leaves and a call 1.."
+                             f"{_capi.VK_TREE_MAX_TREES} trees: {n} leaves, {ntrees} trees")
+        if not d.flags.writeable:
+            d = d.copy()
+        dd = torch.from_numpy(d).to(self.device)   # (the device's copy is overwritten)
+        return self.nj_device(dd)
+
+    def nj_device(self, dd):
+        """nj on a float64 device tensor [ntrees, n, n], which is OVERWRITTEN."""
+        torch = _torch()
+        ntrees, n = int(dd.shape[0]), int(dd.shape[1])
+        rec = 2 * (n - 3) + 3
+        ws = self._workspace(self.L.vk_tree_workspace_size, n, ntrees)
+        nodes = torch.empty((ntrees, rec), dtype=torch.int32, device=self.device)
+        lengths = torch.empty((ntrees, rec), dtype=torch.float64, device=self.device)
+        status = torch.empty((ntrees,), dtype=torch.int32, device=self.device)
+        st = self.L.vk_tree_nj_device(self.ctx, self._ptr(dd), n, ntrees, self._ptr(nodes), self._ptr(lengths), self._ptr(status),
+                                      self._ptr(ws), ws.numel())
+        _capi.check(self.ctx, st, "vk_tree_nj_device")
+        # (the copies below wait for the kernels: the workspace is free after them)
+        return status.cpu().numpy().view(np.uint32), nodes.cpu().numpy().view(np.uint32), lengths.cpu().numpy()
+
     def neighbours(self, q, r, n=10, qgroup=None, rgroup=None, matrix=False):
         """The n nearest references of every query image by exact squared Euclidean distance (vk_dist_device; the rule:
         INTEGRATION.md, "`compare`: the rule").  q, r: uint8 device tensors [nq, side, side] or [nq, P] of equal P; `q is

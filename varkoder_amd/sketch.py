@@ -60,6 +60,51 @@ def corrected_distance_eta(j, k, every, a1, g1, eta1, a2, g2, eta2):
     return 1.0 - min(1.0, x) ** (1.0 / k)
 
 
+def _map(fn, x):
+    """fn over the distinct values of a float64 array: the scalar function itself decides every value, so an array
+    function built on it cannot differ from it in a last bit (NumPy's own log and power may, from one build to the next)."""
+    uniq, inv = np.unique(x, return_inverse=True)
+    return np.array([fn(float(v)) for v in uniq], dtype=np.float64)[inv.reshape(x.shape)]
+
+
+def jaccard_np(shared, seen):
+    """jaccard over integer arrays: float64, NaN where nothing was seen."""
+    shared, seen = np.asarray(shared, dtype=np.float64), np.asarray(seen, dtype=np.float64)
+    return np.where(seen > 0, shared / np.where(seen > 0, seen, 1.0), np.nan)
+
+
+def mash_distance_np(shared, seen, k):
+    """mash_distance(jaccard(shared, seen), k) of every entry, exactly: float64, NaN where it is None."""
+    j = jaccard_np(shared, seen)
+    ok = ~np.isnan(j)
+    pos = ok & (j > 0)
+    ratio = np.where(pos, 2.0 * j / (1.0 + j), 1.0)
+    d = -_map(math.log, ratio) / k
+    d = np.where(d > 0.0, d, 0.0)   # (max(0.0, d) as Python takes it: +0.0 unless d is greater)
+    return np.where(pos, d, np.where(ok, 1.0, np.nan))
+
+
+def corrected_distance_np(shared, seen, k, every, a, g, eta):
+    """corrected_distance_eta of every pair of a square comparison, exactly: shared and seen integer arrays [n, n] (or
+    [r, n, n]); a (eligible counts), g (genome_kmers) and eta per sample [n], NaN where a sample has none.  float64, NaN
+    where the scalar function gives None."""
+    j = jaccard_np(shared, seen)
+    a = np.asarray(a, dtype=np.float64)
+    g = np.array([np.nan if v is None else v for v in g], dtype=np.float64)
+    eta = np.array([np.nan if v is None else v for v in eta], dtype=np.float64)
+    e2 = eta[:, None] * eta[None, :]
+    g2 = g[:, None] + g[None, :]
+    a2 = a[:, None] + a[None, :]
+    with np.errstate(invalid="ignore"):
+        ok = ~np.isnan(j) & ~np.isnan(e2) & ~np.isnan(g2) & (e2 > 0.0) & (g2 > 0.0)
+    jj = np.where(ok, j, 0.0)
+    inter = jj * a2 / (1.0 + jj)
+    x = 2.0 * every * inter / np.where(ok, e2 * g2, 1.0)
+    root = 1.0 / k
+    p = _map(lambda v: v ** root, np.where(ok, np.minimum(1.0, x), 1.0))
+    return np.where(ok, 1.0 - p, np.nan)
+
+
 def sample_eta(est, m):
     """(eta, G) of a sample from its spectrum estimates: eta is `seen_fraction` when the estimates state it (an assembly:
     1.0), else P(Poisson(kmer_coverage) >= m) with m the sample's own min_count; (None, None) without estimates."""
