@@ -14,7 +14,8 @@ CSRC = os.path.join(ROOT, "varkoder_amd", "csrc")
 SRC = os.path.join(HERE, "emul", "textplan_emul.cpp")
 INCLUDES = ["-I", os.path.join(HERE, "emul", "stub"), "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 DEPS = [SRC, os.path.join(ROOT, "include", "vkimg.h")] + [os.path.join(CSRC, h) for h in (
-    "vk_textplan.h", "vk_clean.h", "vk_emit.h", "vk_lane.h", "vk_fasta.h", "vk_screen.h", "vk_spectrum.h", "vk_ws.h")]
+    "vk_textplan.h", "vk_faplan.h", "vk_clean.h", "vk_emit.h", "vk_lane.h", "vk_fasta.h", "vk_fasta_ladder.h", "vk_fasta_records.h",
+    "vk_fasta_windows.h", "vk_screen.h", "vk_spectrum.h", "vk_ws.h")]
 CHUNK, SCAN_BLOCK = 16384, 4096   # kClChunk, kClScanBlock
 VK_OK, VK_EINVAL, VK_ENOSPC = 0, 1, 6
 # the size functions, and the entry points that answer to the same number in a check case

@@ -118,8 +118,6 @@ struct FaWalk {
     }
 };
 
-#ifndef VK_FASTA_LANE_ONLY
-
 struct FaMeta {
     const uint64_t* offs;        // [nsamples] byte offset of each sample (multiple of 16)
     const uint64_t* lens;        // [nsamples]
@@ -127,6 +125,8 @@ struct FaMeta {
     const uint64_t* unit_first;  // [nsamples + 1] first unit of each sample (index into ukey / carry)
     uint32_t nsamples, unit_bytes, span_units;
 };
+
+#ifndef VK_FASTA_LANE_ONLY
 
 // Exclusive running maximum of `key` over the lanes of the workgroup, in lane order (all kFaThreads lanes call it);
 // *total = the maximum over all of them.  s_wave: kFaThreads / 64 words of LDS.

@@ -133,8 +133,6 @@ struct FaFragWalk {
     }
 };
 
-#ifndef VK_FASTA_LANE_ONLY
-
 struct FaPairs {
     const uint64_t* sample;      // [npairs] the pair's sample
     const uint64_t* seed;        // [npairs]
@@ -143,6 +141,8 @@ struct FaPairs {
     const uint64_t* wg_first;    // [npairs + 1] first workgroup of each pair
     uint32_t npairs, frag_len;
 };
+
+#ifndef VK_FASTA_LANE_ONLY
 
 // Exclusive sum of v over the lanes of the workgroup, in lane order (all kFaThreads lanes call it); *total = the sum of
 // all.  s_wave: kFaThreads / 64 elements of LDS.

@@ -46,6 +46,7 @@ namespace {
 
 constexpr uint64_t kFaNoWindow = 0xFFFFFFFFFFFFFFFFull;   // VK_FA_NO_WINDOW
 constexpr uint32_t kFaMaxSteps = 64;                      // m = N / S
+constexpr uint32_t kFawSumCodes = 1024;   // codes of a row a workgroup of the sum handles (4^5: every k has whole chunks)
 
 // Where the k-mer that the NEXT sequence byte of a record would complete starts: its tile and the offset in it.  A
 // record's first K - 1 bytes complete nothing: there the offset is negative and the tile 0.
@@ -122,8 +123,6 @@ __device__ inline uint32_t faw_lane_count(const uint32_t* w, uint32_t n, FaWalk&
     return hb;
 }
 
-#ifndef VK_FASTA_LANE_ONLY
-
 // What the count knows of a record (vk_faw_plan_kernel writes it).
 struct FawRec {
     uint64_t ord0;     // joined bytes of the batch before the record's (the count subtracts the sample's first record's)
@@ -131,6 +130,8 @@ struct FawRec {
     uint32_t t_cnt;    // how many it needs from there on
     uint32_t slot0;    // the row of tile t_lo in the target buffer (d_hist, or the tile workspace)
 };
+
+#ifndef VK_FASTA_LANE_ONLY
 
 // One workgroup.  recs has nrec + 1 entries (the last: ord0 alone).  m == 1: the rows are d_hist's, cap = nrows.  m > 1:
 // they are the tile workspace's, cap of them; *tiles_used = how many are used.
@@ -316,8 +317,6 @@ __global__ __launch_bounds__(kFaThreads) void vk_faw_count_kernel(const uint8_t*
         }
     }
 }
-
-constexpr uint32_t kFawSumCodes = 1024;   // codes of a row a workgroup of the sum handles (4^5: every k has whole chunks)
 
 // m > 1.  A workgroup per (tile row x of the workspace, chunk of codes): x is tile j of the record whose tiles hold it;
 // if the m tiles from it on are the record's, they are a window, and its row of d_hist is their sum.

@@ -34,6 +34,7 @@
 #include "vk_fasta.h"
 #include "vk_spectrum.h"
 #endif
+#include "vk_faplan.h"
 #include "vk_ws.h"
 
 namespace {
@@ -252,20 +253,8 @@ inline void text_index_take(WsTake& take, ClLayout& c, const uint64_t* lengths, 
     take(c.recs, c.nrec);
 }
 
-// The FASTA plan's descriptors and the header state of a batch of FASTA texts (vk_fasta.h), the units counted at their
-// smallest size, kFaLaneBytes.
-struct FaStatePieces {
-    uint64_t* meta;
-    uint32_t *ukey, *carry;
-};
-
-inline void fa_state_take(WsTake& take, FaStatePieces& p, const uint64_t* lengths, uint32_t nsamples) {
-    uint64_t nunits = 0;
-    for (uint32_t i = 0; i < nsamples; ++i) nunits += (lengths[i] + kFaLaneBytes - 1) / kFaLaneBytes;
-    take(p.meta, 4ull * nsamples + 2);
-    take(p.ukey, nunits + 1);
-    take(p.carry, nunits + 1);
-}
+// (FaStatePieces, fa_state_take -- the FASTA plan's descriptors and the header state of a batch of FASTA texts, the units
+// counted at their smallest size: vk_faplan.h)
 
 // the samples' counting tables as the table kernels read them
 struct SpTablePieces {

@@ -75,6 +75,7 @@
 #include "vk_fasta_ladder.h"
 #include "vk_fasta_records.h"
 #include "vk_fasta_windows.h"
+#include "vk_faplan.h"
 #include "vk_bam.h"
 #include "vk_bam_groups.h"
 #include "vk_bamplan.h"
@@ -720,11 +721,7 @@ int vk_ctx_create(int device, void* stream, int own_stream, vk_ctx** out) {
     ctx->k1_static = env_flag("VKIMG_K1_STATIC");
     env_uint("VKIMG_K1_HELPERS", &ctx->k1_helpers);
     env_uint("VKIMG_FASTA_UNIT_BYTES", &ctx->fasta_unit_bytes);
-    if (ctx->fasta_unit_bytes) {
-        ctx->fasta_unit_bytes = ctx->fasta_unit_bytes / kFaLaneBytes * kFaLaneBytes;
-        if (ctx->fasta_unit_bytes < kFaLaneBytes) ctx->fasta_unit_bytes = kFaLaneBytes;
-        if (ctx->fasta_unit_bytes > kFaUnitBytes) ctx->fasta_unit_bytes = kFaUnitBytes;
-    }
+    ctx->fasta_unit_bytes = fa_unit_clamp(ctx->fasta_unit_bytes);
     env_uint("VKIMG_BAM_SEG_BYTES", &ctx->bam_seg_bytes);
     if (ctx->bam_seg_bytes && ctx->bam_seg_bytes < 64) ctx->bam_seg_bytes = 64;
     if (ctx->bam_seg_bytes > kBamSegBytes) ctx->bam_seg_bytes = kBamSegBytes;
@@ -2482,51 +2479,62 @@ int vk_unpng_device(vk_ctx* ctx, const void* d_streams, const uint64_t* offsets,
 }  // extern "C"
 
 // ---------------------------------------------------------------- FASTA count (vk_fasta.h, vk_fasta_ladder.h) ------
+// What a call carries, the rules of its arguments, the plan, the pair table and the workspaces' pieces are vk_faplan.h's
+// (with the warts kept); the entry points, the copies and the launches are here, one sequence per shared stage.
 
 namespace {
 
-// How a batch of FASTA samples is cut: meta = offsets | lengths | first workgroup | first unit of every sample.
-struct FaPlan {
-    std::vector<uint64_t> meta;
-    uint32_t nsamples = 0, unit = 0, span = 0;
-    uint64_t nwg = 0, nunits = 0;
-    const uint64_t* wg_first() const { return meta.data() + 2ull * nsamples; }
-    FaMeta on_device(const uint64_t* d_meta) const {
-        return FaMeta{d_meta, d_meta + nsamples, d_meta + 2ull * nsamples, d_meta + 3ull * nsamples + 1, nsamples, unit, span};
-    }
-};
+bool fa_text_ok(const void* d_fasta) { return d_fasta && (reinterpret_cast<uintptr_t>(d_fasta) & 15u) == 0; }
 
-int fa_plan(const vk_ctx* ctx, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples, FaPlan* pl) {
-    pl->nsamples = nsamples;
-    pl->unit = ctx->fasta_unit_bytes ? ctx->fasta_unit_bytes : kFaUnitBytes;
-    pl->span = ctx->fasta_unit_bytes ? 1u : kFaSpanUnits;
-    pl->meta.assign(4ull * nsamples + 2, 0);
-    uint64_t* wg_first = pl->meta.data() + 2ull * nsamples;
-    uint64_t* unit_first = wg_first + nsamples + 1;
-    for (uint32_t i = 0; i < nsamples; ++i) {
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
-        const uint64_t units = (lengths[i] + pl->unit - 1) / pl->unit;
-        if (units >= (1ull << 30)) return VK_EINVAL;   // (a unit's number takes 31 bits of the scan's key)
-        pl->meta[i] = offsets[i];
-        pl->meta[nsamples + i] = lengths[i];
-        wg_first[i + 1] = wg_first[i] + (units + pl->span - 1) / pl->span;
-        unit_first[i + 1] = unit_first[i] + units;
-    }
-    pl->nwg = wg_first[nsamples];
-    pl->nunits = unit_first[nsamples];
-    return pl->nwg >= (1ull << 31) ? VK_EINVAL : VK_OK;
+// Behind a call's rules: the text where a lane may load it -- looked at only when there is a sample --, then the device.
+// (vk_count_fasta_windows_device has rules between the two and states them itself.)
+int fa_enter(vk_ctx* ctx, const void* d_fasta, uint32_t nsamples) {
+    if (nsamples && !fa_text_ok(d_fasta)) return VK_EINVAL;
+    VK_HIP(ctx, hipSetDevice(ctx->device));
+    return VK_OK;
 }
 
-// The header state that enters every unit (d_carry) and the samples' status words.
-int fa_header_state(vk_ctx* ctx, const uint8_t* text, const FaPlan& pl, const FaMeta& m, uint32_t* d_ukey, uint32_t* d_carry,
-                    uint32_t* d_status) {
+// The header state that enters every unit (f.carry) and the samples' status words: the plan goes up, then the call's own
+// uploads and resets (`more`), then the two kernels.  *m: the plan as the kernels read it.
+template <class F>
+int fa_state_run(vk_ctx* ctx, const uint8_t* text, const FaPlan& pl, const FaStatePieces& f, uint32_t* d_status, FaMeta* m, F&& more) {
+    // (pageable source: the copy has read it on return)
+    VK_HIP(ctx, hipMemcpyAsync(f.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    int rc = more();
+    if (rc) return rc;
+    *m = pl.on_device(f.meta);
     if (pl.nwg) {
-        hipLaunchKernelGGL(vk_fa_summary_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey);
+        hipLaunchKernelGGL(vk_fa_summary_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, *m, f.ukey);
         VK_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(vk_fa_scan_kernel, dim3(pl.nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_ukey, d_carry, d_status);
+    hipLaunchKernelGGL(vk_fa_scan_kernel, dim3(pl.nsamples), dim3(kFaThreads), 0, ctx->stream, text, *m, f.ukey, f.carry, d_status);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
+}
+
+// The lanes' index and the ordinal of every unit's first sequence byte (d_lane, d_unit_ord), the samples' sequence bytes.
+int fa_ord_run(vk_ctx* ctx, const uint8_t* text, const FaPlan& pl, const FaMeta& m, const uint32_t* d_carry, uint32_t* d_lane,
+               unsigned long long* d_unit_ord, unsigned long long* d_bases) {
+    if (pl.nwg) {
+        hipLaunchKernelGGL(vk_fa_ord_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_carry,
+                           d_lane, d_unit_ord);
+        VK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(vk_fa_ordscan_kernel, dim3(pl.nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_unit_ord, d_bases);
+    VK_HIP(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// One kernel templated on K for the runtime k (5..9, checked by the caller), nwg workgroups of kFaThreads, its error
+// checked.  pick(std::integral_constant<int, K>{}) names the kernel: FA_KERNEL(vk_fa_count_kernel).
+#define FA_KERNEL(name) [](auto kc) { return name<decltype(kc)::value>; }
+template <class Pick, class... Args>
+int launch_k(vk_ctx* ctx, int k, uint64_t nwg, Pick pick, Args... args) {
+    return with_k(k, [&](auto kc) {
+        hipLaunchKernelGGL(pick(kc), dim3(static_cast<uint32_t>(nwg)), dim3(kFaThreads), 0, ctx->stream, args...);
+        VK_HIP(ctx, hipGetLastError());
+        return VK_OK;
+    });
 }
 
 }  // namespace
@@ -2535,117 +2543,70 @@ extern "C" {
 
 int vk_count_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                           int k, uint32_t* d_hist, uint32_t* d_status, uint64_t* d_bases) {
-    if (!ctx || !offsets || !lengths || !d_hist || !d_status || !d_bases || k < 5 || k > 9) return VK_EINVAL;
+    if (!ctx || !offsets || !lengths || !d_hist || !d_status || !d_bases) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples, c.k = k;
+    if (int rc = count_fasta_check(c)) return rc;
     if (nsamples == 0) return VK_OK;
-    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = fa_enter(ctx, d_fasta, nsamples);
+    if (rc) return rc;
     FaPlan pl;
-    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    rc = fa_plan(ctx->fasta_unit_bytes, offsets, lengths, nsamples, &pl);
     if (rc) return rc;
-    uint64_t* d_meta = nullptr;
-    uint32_t *d_ukey = nullptr, *d_carry = nullptr;
-    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
-        take(d_meta, pl.meta.size());
-        take(d_ukey, pl.nunits + 1);
-        take(d_carry, pl.nunits + 1);
-    });
+    FaStatePieces f{};
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) { fa_state_take(take, f, nsamples, pl.nunits); });
     if (rc) return rc;
-    // (pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     const size_t ncode = static_cast<size_t>(1) << (2 * k);
-    VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nsamples * ncode * sizeof(uint32_t), ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(d_bases, 0, nsamples * sizeof(uint64_t), ctx->stream));
-    const FaMeta m = pl.on_device(d_meta);
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
-    rc = fa_header_state(ctx, text, pl, m, d_ukey, d_carry, d_status);
-    if (rc) return rc;
-    if (pl.nwg) {
-        rc = with_k(k, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            hipLaunchKernelGGL(vk_fa_count_kernel<K>, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m,
-                               d_carry, d_hist, reinterpret_cast<unsigned long long*>(d_bases));
-            VK_HIP(ctx, hipGetLastError());
-            return VK_OK;
-        });
-        if (rc) return rc;
-    }
-    return VK_OK;
+    FaMeta m;
+    rc = fa_state_run(ctx, text, pl, f, d_status, &m, [&] {
+        VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nsamples * ncode * sizeof(uint32_t), ctx->stream));
+        VK_HIP(ctx, hipMemsetAsync(d_bases, 0, nsamples * sizeof(uint64_t), ctx->stream));
+        return VK_OK;
+    });
+    if (rc || !pl.nwg) return rc;
+    return launch_k(ctx, k, pl.nwg, FA_KERNEL(vk_fa_count_kernel), text, m, f.carry, d_hist, reinterpret_cast<unsigned long long*>(d_bases));
 }
 
 int vk_count_fasta_sampled_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths,
                                   uint32_t nsamples, int k, uint32_t frag_len, uint32_t npairs, const uint32_t* pair_sample,
                                   const uint64_t* seeds, const uint64_t* thresholds, const uint64_t* shifts, uint32_t* d_hist,
                                   uint32_t* d_status, uint64_t* d_bases, uint64_t* d_taken) {
-    if (!ctx || !offsets || !lengths || !d_status || !d_bases || k < 5 || k > 9) return VK_EINVAL;
-    if (frag_len < static_cast<uint32_t>(k) || frag_len >= (1u << 31)) return VK_EINVAL;
+    if (!ctx || !offsets || !lengths || !d_status || !d_bases) return VK_EINVAL;
     if (npairs && (!pair_sample || !seeds || !thresholds || !shifts || !d_hist || !d_taken)) return VK_EINVAL;
-    for (uint32_t i = 0; i < npairs; ++i)   // (q + shift stays below 2^64: ordinals are below 2^63)
-        if (pair_sample[i] >= nsamples || thresholds[i] > (1ull << 32) || shifts[i] >= (1ull << 63)) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples, c.k = k, c.frag_len = frag_len;
+    c.npairs = npairs, c.pair_sample = pair_sample, c.seeds = seeds, c.thresholds = thresholds, c.shifts = shifts;
+    if (int rc = count_fasta_sampled_check(c)) return rc;
     if (nsamples == 0) return VK_OK;
-    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
-    FaPlan pl;
-    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    int rc = fa_enter(ctx, d_fasta, nsamples);
     if (rc) return rc;
-    // sample | seed | threshold | shift | first workgroup of every pair
-    std::vector<uint64_t> pairs(5ull * npairs + 1);
-    uint64_t* pair_wg = pairs.data() + 4ull * npairs;
-    pair_wg[0] = 0;
-    for (uint32_t i = 0; i < npairs; ++i) {
-        pairs[i] = pair_sample[i];
-        pairs[npairs + i] = seeds[i];
-        pairs[2ull * npairs + i] = thresholds[i];
-        pairs[3ull * npairs + i] = shifts[i];
-        pair_wg[i + 1] = pair_wg[i] + (pl.wg_first()[pair_sample[i] + 1] - pl.wg_first()[pair_sample[i]]);
-    }
-    const uint64_t pair_nwg = pair_wg[npairs];
-    if (pair_nwg >= (1ull << 31)) return VK_EINVAL;
-    const uint32_t lanes = pl.unit / kFaLaneBytes;
-    uint64_t *d_meta = nullptr, *d_pairs = nullptr;
-    uint32_t *d_ukey = nullptr, *d_carry = nullptr, *d_lane = nullptr;
-    unsigned long long* d_unit_ord = nullptr;
-    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
-        take(d_meta, pl.meta.size());
-        take(d_pairs, pairs.size());
-        take(d_ukey, pl.nunits + 1);
-        take(d_carry, pl.nunits + 1);
-        take(d_unit_ord, pl.nunits + 1);
-        take(d_lane, pl.nunits * lanes + 1);   // the index: a word per lane of text, 1/16 of it
+    FaPlan pl;
+    rc = fa_plan(ctx->fasta_unit_bytes, offsets, lengths, nsamples, &pl);
+    if (rc) return rc;
+    FaPairPlan pp;
+    rc = fa_pair_plan(c, pl, &pp);
+    if (rc) return rc;
+    FaSampledPieces p{};
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) { fa_sampled_take(take, p, pl, npairs); });
+    if (rc) return rc;
+    const size_t ncode = static_cast<size_t>(1) << (2 * k);
+    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
+    FaMeta m;
+    rc = fa_state_run(ctx, text, pl, p.f, d_status, &m, [&] {
+        // (pageable source: the copy has read it on return)
+        VK_HIP(ctx, hipMemcpyAsync(p.pairs, pp.words.data(), pp.words.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (npairs) {
+            VK_HIP(ctx, hipMemsetAsync(d_hist, 0, npairs * ncode * sizeof(uint32_t), ctx->stream));
+            VK_HIP(ctx, hipMemsetAsync(d_taken, 0, npairs * sizeof(uint64_t), ctx->stream));
+        }
+        return VK_OK;
     });
     if (rc) return rc;
-    // (pageable sources: the copies have read them on return)
-    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    const size_t ncode = static_cast<size_t>(1) << (2 * k);
-    if (npairs) {
-        VK_HIP(ctx, hipMemsetAsync(d_hist, 0, npairs * ncode * sizeof(uint32_t), ctx->stream));
-        VK_HIP(ctx, hipMemsetAsync(d_taken, 0, npairs * sizeof(uint64_t), ctx->stream));
-    }
-    const FaMeta m = pl.on_device(d_meta);
-    const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
-    rc = fa_header_state(ctx, text, pl, m, d_ukey, d_carry, d_status);
-    if (rc) return rc;
-    if (pl.nwg) {
-        hipLaunchKernelGGL(vk_fa_ord_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, m, d_carry,
-                           d_lane, d_unit_ord);
-        VK_HIP(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(vk_fa_ordscan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, m, d_unit_ord,
-                       reinterpret_cast<unsigned long long*>(d_bases));
-    VK_HIP(ctx, hipGetLastError());
-    if (pair_nwg) {
-        const FaPairs ps{d_pairs, d_pairs + npairs, d_pairs + 2ull * npairs, d_pairs + 3ull * npairs, d_pairs + 4ull * npairs, npairs,
-                         frag_len};
-        rc = with_k(k, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            hipLaunchKernelGGL(vk_fa_frag_count_kernel<K>, dim3(static_cast<uint32_t>(pair_nwg)), dim3(kFaThreads), 0, ctx->stream, text,
-                               m, ps, d_lane, d_unit_ord, d_hist, reinterpret_cast<unsigned long long*>(d_taken));
-            VK_HIP(ctx, hipGetLastError());
-            return VK_OK;
-        });
-        if (rc) return rc;
-    }
-    return VK_OK;
+    rc = fa_ord_run(ctx, text, pl, m, p.f.carry, p.lane, p.unit_ord, reinterpret_cast<unsigned long long*>(d_bases));
+    if (rc || !pp.pair_nwg) return rc;
+    return launch_k(ctx, k, pp.pair_nwg, FA_KERNEL(vk_fa_frag_count_kernel), text, m, pp.pairs_on_device(p.pairs, frag_len), p.lane,
+                    p.unit_ord, d_hist, reinterpret_cast<unsigned long long*>(d_taken));
 }
 
 int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k, uint32_t* hist, uint32_t* status, uint64_t* bases) {
@@ -2679,57 +2640,41 @@ int vk_count_fasta_host(vk_ctx* ctx, const uint8_t* fasta, size_t nbytes, int k,
 
 namespace {
 
-// What the three per-record calls share: the plan on the device, the header state and the header count that enter every
-// unit (d_carry, d_uhdr), the samples' status words and record counts.  `extra` states the call's own pieces.
+// What the three per-record calls and the windows share: the plan on the device, the header state and the header count
+// that enter every unit (p.carry, p.uhdr), the samples' status words and record counts.
 struct FarState {
     FaPlan pl;
     FaMeta m;
-    uint32_t *d_ukey = nullptr, *d_carry = nullptr, *d_uhdr = nullptr, *d_status = nullptr, *d_nrec = nullptr;
-    uint64_t* d_rec_first = nullptr;
+    FarPieces p;
+    uint32_t *d_status = nullptr, *d_nrec = nullptr;   // the caller's, or p's
 };
 
 // rec_first: null (the counting call) or host u64[nsamples + 1], checked by the caller.  d_status, d_nrec: the caller's,
 // or null for pieces of the workspace.
 int far_prepare(vk_ctx* ctx, const uint8_t* text, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                 const uint64_t* rec_first, uint32_t* d_status, uint32_t* d_nrec, FarState* st) {
-    int rc = fa_plan(ctx, offsets, lengths, nsamples, &st->pl);
+    int rc = fa_plan(ctx->fasta_unit_bytes, offsets, lengths, nsamples, &st->pl);
     if (rc) return rc;
     const FaPlan& pl = st->pl;
-    uint64_t* d_meta = nullptr;
-    uint32_t *ws_status = nullptr, *ws_nrec = nullptr;
-    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) {
-        take(d_meta, pl.meta.size());
-        take(st->d_rec_first, nsamples + 1ull);
-        take(st->d_ukey, pl.nunits + 1);
-        take(st->d_carry, pl.nunits + 1);
-        take(st->d_uhdr, pl.nunits + 1);
-        take(ws_status, nsamples);
-        take(ws_nrec, nsamples);
-    });
+    FarPieces& p = st->p;
+    rc = ws_carve(ctx, &ctx->d_fasta, &ctx->fasta_cap, [&](WsTake& take) { far_take(take, p, pl); });
     if (rc) return rc;
-    st->d_status = d_status ? d_status : ws_status;
-    st->d_nrec = d_nrec ? d_nrec : ws_nrec;
+    st->d_status = d_status ? d_status : p.status;
+    st->d_nrec = d_nrec ? d_nrec : p.nrec;
     // (pageable sources: the copies have read them on return)
-    VK_HIP(ctx, hipMemcpyAsync(d_meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    VK_HIP(ctx, hipMemcpyAsync(p.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     if (rec_first)
-        VK_HIP(ctx, hipMemcpyAsync(st->d_rec_first, rec_first, (nsamples + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    st->m = pl.on_device(d_meta);
+        VK_HIP(ctx, hipMemcpyAsync(p.rec_first, rec_first, (nsamples + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    st->m = pl.on_device(p.meta);
     if (pl.nwg) {
         hipLaunchKernelGGL(vk_far_summary_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st->m,
-                           st->d_ukey, st->d_uhdr);
+                           p.ukey, p.uhdr);
         VK_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(vk_far_scan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, st->m, st->d_ukey, st->d_carry,
-                       st->d_uhdr, st->d_status, st->d_nrec);
+    hipLaunchKernelGGL(vk_far_scan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, st->m, p.ukey, p.carry, p.uhdr,
+                       st->d_status, st->d_nrec);
     VK_HIP(ctx, hipGetLastError());
     return VK_OK;
-}
-
-bool far_rec_first_ok(const uint64_t* rec_first, uint32_t nsamples) {
-    if (rec_first[0] != 0) return false;
-    for (uint32_t i = 0; i < nsamples; ++i)
-        if (rec_first[i + 1] < rec_first[i]) return false;
-    return true;
 }
 
 }  // namespace
@@ -2739,9 +2684,11 @@ extern "C" {
 int vk_fasta_records_count_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                                   uint32_t* d_nrec, uint32_t* d_status) {
     if (!ctx || !offsets || !lengths || !d_nrec || !d_status) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples;
+    if (int rc = fasta_records_count_check(c)) return rc;
     if (nsamples == 0) return VK_OK;
-    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = fa_enter(ctx, d_fasta, nsamples)) return rc;
     FarState st;
     return far_prepare(ctx, static_cast<const uint8_t*>(d_fasta), offsets, lengths, nsamples, nullptr, d_status, d_nrec, &st);
 }
@@ -2749,13 +2696,15 @@ int vk_fasta_records_count_device(vk_ctx* ctx, const void* d_fasta, const uint64
 int vk_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                             const uint64_t* rec_first, uint64_t* d_rec_start, uint64_t* d_rec_bases, uint8_t* d_rec_name) {
     if (!ctx || !offsets || !lengths || !rec_first || !d_rec_start || !d_rec_bases || !d_rec_name) return VK_EINVAL;
-    if (!far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples, c.rec_first = rec_first;
+    if (int rc = fasta_records_check(c)) return rc;
     if (nsamples == 0) return VK_OK;
-    if (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = fa_enter(ctx, d_fasta, nsamples);
+    if (rc) return rc;
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
     FarState st;
-    int rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
+    rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
     if (rc) return rc;
     const uint64_t total = rec_first[nsamples];
     if (total == 0) return VK_OK;
@@ -2764,7 +2713,7 @@ int vk_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* of
     VK_HIP(ctx, hipMemsetAsync(d_rec_name, 0, total * kFaNameBytes, ctx->stream));
     if (st.pl.nwg) {
         hipLaunchKernelGGL(vk_far_table_kernel, dim3(static_cast<uint32_t>(st.pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m,
-                           st.d_carry, st.d_uhdr, FaRecs{st.d_rec_first}, reinterpret_cast<unsigned long long*>(d_rec_start),
+                           st.p.carry, st.p.uhdr, FaRecs{st.p.rec_first}, reinterpret_cast<unsigned long long*>(d_rec_start),
                            reinterpret_cast<unsigned long long*>(d_rec_bases), d_rec_name);
         VK_HIP(ctx, hipGetLastError());
     }
@@ -2773,47 +2722,41 @@ int vk_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* of
 
 int vk_count_fasta_records_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                                   int k, const uint64_t* rec_first, const uint32_t* d_slot, uint32_t nslots, uint32_t* d_hist) {
-    if (!ctx || !offsets || !lengths || !rec_first || !d_slot || !d_hist || k < 5 || k > 9 || nslots == 0) return VK_EINVAL;
-    if (nslots == kFaNoSlot || !far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
-    if (nsamples && (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0)) return VK_EINVAL;
-    VK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx || !offsets || !lengths || !rec_first || !d_slot || !d_hist) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples, c.k = k, c.rec_first = rec_first, c.nslots = nslots;
+    if (int rc = count_fasta_records_check(c)) return rc;
+    int rc = fa_enter(ctx, d_fasta, nsamples);
+    if (rc) return rc;
     const size_t ncode = static_cast<size_t>(1) << (2 * k);
-    for (uint32_t i = 0; i < nsamples; ++i)
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+    // (the wart: the offsets before the reset, the rest of the plan's rules behind it)
+    if (!fa_offsets_ok(offsets, nsamples)) return VK_EINVAL;
     VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nslots * ncode * sizeof(uint32_t), ctx->stream));
     if (nsamples == 0 || rec_first[nsamples] == 0) return VK_OK;
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
     FarState st;
-    int rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
-    if (rc) return rc;
-    if (st.pl.nwg) {
-        rc = with_k(k, [&](auto kc) {
-            constexpr int K = decltype(kc)::value;
-            hipLaunchKernelGGL(vk_far_count_kernel<K>, dim3(static_cast<uint32_t>(st.pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text,
-                               st.m, st.d_carry, st.d_uhdr, st.d_nrec, FaRecs{st.d_rec_first}, d_slot, nslots, d_hist);
-            VK_HIP(ctx, hipGetLastError());
-            return VK_OK;
-        });
-        if (rc) return rc;
-    }
-    return VK_OK;
+    rc = far_prepare(ctx, text, offsets, lengths, nsamples, rec_first, nullptr, nullptr, &st);
+    if (rc || !st.pl.nwg) return rc;
+    return launch_k(ctx, k, st.pl.nwg, FA_KERNEL(vk_far_count_kernel), text, st.m, st.p.carry, st.p.uhdr, st.d_nrec,
+                    FaRecs{st.p.rec_first}, d_slot, nslots, d_hist);
 }
 
 int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* offsets, const uint64_t* lengths, uint32_t nsamples,
                                   int k, const uint64_t* rec_first, const uint64_t* d_rec_bases, const uint64_t* d_win_first,
                                   uint32_t win_len, uint32_t win_step, uint64_t row_lo, uint32_t nrows, uint32_t tile_rows,
                                   uint32_t* d_hist) {
-    if (!ctx || !offsets || !lengths || !rec_first || !d_rec_bases || !d_win_first || !d_hist || k < 5 || k > 9) return VK_EINVAL;
-    if (win_step < static_cast<uint32_t>(k) || win_len >= (1u << 31) || win_len < win_step || win_len % win_step != 0) return VK_EINVAL;
-    const uint32_t steps = win_len / win_step;
-    if (steps > kFaMaxSteps || nrows == 0 || (steps > 1 && tile_rows == 0)) return VK_EINVAL;
-    if (!far_rec_first_ok(rec_first, nsamples)) return VK_EINVAL;
-    if (nsamples && (!d_fasta || (reinterpret_cast<uintptr_t>(d_fasta) & 15u) != 0)) return VK_EINVAL;
-    for (uint32_t i = 0; i < nsamples; ++i)
-        if ((offsets[i] & 15u) != 0) return VK_EINVAL;
+    if (!ctx || !offsets || !lengths || !rec_first || !d_rec_bases || !d_win_first || !d_hist) return VK_EINVAL;
+    FaCall c{};
+    c.offsets = offsets, c.lengths = lengths, c.nsamples = nsamples, c.k = k, c.rec_first = rec_first;
+    c.win_len = win_len, c.win_step = win_step, c.nrows = nrows, c.tile_rows = tile_rows;
+    uint32_t steps = 0;
+    uint64_t sum_wgs = 0;
+    if (int rc = count_fasta_windows_check(c, &steps)) return rc;
+    if (nsamples && !fa_text_ok(d_fasta)) return VK_EINVAL;
+    // (the wart: the offsets before the reset, the rest of the plan's rules behind it)
+    if (!fa_offsets_ok(offsets, nsamples)) return VK_EINVAL;
+    if (int rc = faw_sum_check(c, steps, &sum_wgs)) return rc;
     const size_t ncode = static_cast<size_t>(1) << (2 * k);
-    const uint64_t sum_wgs = steps > 1 ? static_cast<uint64_t>(tile_rows) * (ncode / kFawSumCodes) : 0;
-    if (sum_wgs >= (1ull << 31)) return VK_EINVAL;
     VK_HIP(ctx, hipSetDevice(ctx->device));
     VK_HIP(ctx, hipMemsetAsync(d_hist, 0, nrows * ncode * sizeof(uint32_t), ctx->stream));
     const uint64_t total = nsamples ? rec_first[nsamples] : 0;
@@ -2824,41 +2767,22 @@ int vk_count_fasta_windows_device(vk_ctx* ctx, const void* d_fasta, const uint64
     if (rc) return rc;
     const FaPlan& pl = st.pl;
     if (pl.nwg == 0) return VK_OK;
-    const uint32_t lanes = pl.unit / kFaLaneBytes;
-    uint32_t *d_lane = nullptr, *d_used = nullptr, *d_tiles = nullptr;
-    unsigned long long *d_unit_ord = nullptr, *d_bases = nullptr;
-    FawRec* d_recs = nullptr;
-    rc = ws_carve(ctx, &ctx->d_fawin, &ctx->fawin_cap, [&](WsTake& take) {
-        take(d_lane, pl.nunits * lanes + 1);   // the index: a word per lane of text, 1/16 of it
-        take(d_unit_ord, pl.nunits + 1);
-        take(d_bases, nsamples);
-        take(d_recs, total + 1);
-        take(d_used, 1);
-        take(d_tiles, steps > 1 ? tile_rows * ncode : 1);
-    });
+    FawPieces w{};
+    rc = ws_carve(ctx, &ctx->d_fawin, &ctx->fawin_cap, [&](WsTake& take) { faw_take(take, w, pl, total, steps, tile_rows, k); });
     if (rc) return rc;
-    if (steps > 1) VK_HIP(ctx, hipMemsetAsync(d_tiles, 0, tile_rows * ncode * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(vk_fa_ord_kernel, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m, st.d_carry,
-                       d_lane, d_unit_ord);
-    VK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(vk_fa_ordscan_kernel, dim3(nsamples), dim3(kFaThreads), 0, ctx->stream, text, st.m, d_unit_ord, d_bases);
-    VK_HIP(ctx, hipGetLastError());
+    if (steps > 1) VK_HIP(ctx, hipMemsetAsync(w.tiles, 0, tile_rows * ncode * sizeof(uint32_t), ctx->stream));
+    rc = fa_ord_run(ctx, text, pl, st.m, st.p.carry, w.lane, w.unit_ord, w.bases);
+    if (rc) return rc;
     const uint32_t cap = steps > 1 ? tile_rows : nrows;
     hipLaunchKernelGGL(vk_faw_plan_kernel, dim3(1), dim3(kFaThreads), 0, ctx->stream, reinterpret_cast<const unsigned long long*>(d_rec_bases),
-                       reinterpret_cast<const unsigned long long*>(d_win_first), total, win_len, win_step, row_lo, nrows, cap, d_recs, d_used);
+                       reinterpret_cast<const unsigned long long*>(d_win_first), total, win_len, win_step, row_lo, nrows, cap, w.recs, w.used);
     VK_HIP(ctx, hipGetLastError());
-    rc = with_k(k, [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL(vk_faw_count_kernel<K>, dim3(static_cast<uint32_t>(pl.nwg)), dim3(kFaThreads), 0, ctx->stream, text, st.m,
-                           st.d_carry, st.d_uhdr, st.d_nrec, FaRecs{st.d_rec_first}, d_lane, d_unit_ord, d_recs, win_step,
-                           steps > 1 ? d_tiles : d_hist, cap);
-        VK_HIP(ctx, hipGetLastError());
-        return VK_OK;
-    });
+    rc = launch_k(ctx, k, pl.nwg, FA_KERNEL(vk_faw_count_kernel), text, st.m, st.p.carry, st.p.uhdr, st.d_nrec, FaRecs{st.p.rec_first},
+                  w.lane, w.unit_ord, w.recs, win_step, steps > 1 ? w.tiles : d_hist, cap);
     if (rc) return rc;
     if (steps > 1) {
-        hipLaunchKernelGGL(vk_faw_sum_kernel, dim3(static_cast<uint32_t>(sum_wgs)), dim3(kFaThreads), 0, ctx->stream, d_recs,
-                           reinterpret_cast<const unsigned long long*>(d_win_first), total, d_used, d_tiles, static_cast<uint32_t>(ncode),
+        hipLaunchKernelGGL(vk_faw_sum_kernel, dim3(static_cast<uint32_t>(sum_wgs)), dim3(kFaThreads), 0, ctx->stream, w.recs,
+                           reinterpret_cast<const unsigned long long*>(d_win_first), total, w.used, w.tiles, static_cast<uint32_t>(ncode),
                            steps, row_lo, nrows, d_hist);
         VK_HIP(ctx, hipGetLastError());
     }
@@ -3214,15 +3138,15 @@ int vk_screen_build_device(vk_ctx* ctx, const void* d_fasta, uint64_t length, in
     VK_HIP(ctx, hipSetDevice(ctx->device));
     FaPlan pl;
     const uint64_t zero = 0;
-    int rc = fa_plan(ctx, &zero, &length, 1, &pl);
+    int rc = fa_plan(ctx->fasta_unit_bytes, &zero, &length, 1, &pl);
     if (rc) return rc;
-    // (pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.f.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    VK_HIP(ctx, hipMemsetAsync(L.out, 0, sizeof(ScBuildOut), ctx->stream));
-    if (d_table) VK_HIP(ctx, hipMemsetAsync(d_table, 0xFF, nslots * sizeof(uint64_t), ctx->stream));
-    const FaMeta m = pl.on_device(L.f.meta);
     const uint8_t* text = static_cast<const uint8_t*>(d_fasta);
-    rc = fa_header_state(ctx, text, pl, m, L.f.ukey, L.f.carry, L.status);
+    FaMeta m;
+    rc = fa_state_run(ctx, text, pl, L.f, L.status, &m, [&] {
+        VK_HIP(ctx, hipMemsetAsync(L.out, 0, sizeof(ScBuildOut), ctx->stream));
+        if (d_table) VK_HIP(ctx, hipMemsetAsync(d_table, 0xFF, nslots * sizeof(uint64_t), ctx->stream));
+        return VK_OK;
+    });
     if (rc) return rc;
     if (pl.nwg) {
         const dim3 grid(static_cast<uint32_t>(pl.nwg)), block(kFaThreads);
@@ -3385,16 +3309,13 @@ int vk_spectrum_fasta_device(vk_ctx* ctx, const void* d_fasta, const uint64_t* o
     const FsLayout L = fs_layout(d_ws, lengths, nsamples);
     if (ws_bytes < L.total) return VK_EINVAL;
     FaPlan pl;
-    int rc = fa_plan(ctx, offsets, lengths, nsamples, &pl);
+    int rc = fa_plan(ctx->fasta_unit_bytes, offsets, lengths, nsamples, &pl);
     if (rc) return rc;
     VK_HIP(ctx, hipSetDevice(ctx->device));
     const auto* text = static_cast<const uint8_t*>(d_fasta);
-    // (pageable source: the copy has read it on return)
-    VK_HIP(ctx, hipMemcpyAsync(L.f.meta, pl.meta.data(), pl.meta.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    rc = sp_tables_put(ctx, L.t, block_base, slot_base, nslots, nsamples, d_rows);
-    if (rc) return rc;
-    const FaMeta m = pl.on_device(L.f.meta);
-    rc = fa_header_state(ctx, text, pl, m, L.f.ukey, L.f.carry, d_status);
+    FaMeta m;
+    rc = fa_state_run(ctx, text, pl, L.f, d_status, &m,
+                      [&] { return sp_tables_put(ctx, L.t, block_base, slot_base, nslots, nsamples, d_rows); });
     if (rc) return rc;
     return sp_tables_run(ctx, L.t, block_base[nsamples], nsamples, d_keys, d_counts, d_status, d_rows, [&](unsigned long long* rows) {
         if (!pl.nwg) return;
