@@ -1,6 +1,8 @@
 """`compare`'s device call on the GPU (ImageEngine.neighbours, vk_dist_device) against the rule in NumPy
-(tests/dist_ref.py): idx, d2 and the matrix equal, exactly, on every case of tests/dist_cases.py; strip seams
-(VKIMG_DIST_STRIP); self mode; refusals."""
+(tests/dist_ref.py): idx, d2 and the matrix equal, exactly, on every case of tests/dist_cases.py (its docstring names the
+paths: grids of several tiles both ways, slices, a wavefront's second look with more than one entry per lane); strip
+seams (VKIMG_DIST_STRIP), also across grids with several reference tiles and rows of several entries per thread; the
+second look run twice on copies; self mode; refusals."""
 import ctypes as C
 import os
 
@@ -68,14 +70,31 @@ def test_black_against_white_at_512_squared(dist_engines):
     assert int(m[0, 1]) == DC.D2_BLACK_WHITE_512 and int(m[0, 0]) == 0 and int(m[1, 1]) == 0
 
 
-@pytest.mark.parametrize("name", ["tile_edges_257x63", "tile_edges_129x31", "structured", "ties", "groups_mixed"])
+@pytest.mark.parametrize("name", ["tile_edges_257x63", "tile_edges_129x31", "structured", "ties", "groups_mixed", "grid_257x385",
+                                  "grid_structured_300x200", "select_1000"])
 def test_strips_of_64_rows_give_the_same(dist_engines, name):
-    """Four seams across the 257 queries of tile_edges; strips that are no multiple of the tile."""
+    """Four seams across the 257 queries of tile_edges; strips that are no multiple of the tile; in the grids every strip
+    is a launch of its own over 4 or 2 reference tiles."""
     assert name in NAMES
     small = run(dist_engines("small"), DC.by_name(name))
     check(small, name, "VKIMG_DIST_STRIP=64")
     for a, b in zip(small, run(dist_engines("default"), DC.by_name(name))):
         assert np.array_equal(a, b)
+
+
+def test_the_second_look_keeps_no_state_between_calls(dist_engines):
+    """select_ties_16700 twice, on copies: nothing of the look through a winner's entries depends on an earlier call."""
+    import torch
+    eng, c = dist_engines("default"), DC.by_name("select_ties_16700")
+    q, r = on_device(eng, c.q), on_device(eng, c.r)
+    outs = []
+    for _ in range(2):
+        idx, d2, m = eng.neighbours(q.clone(), r.clone(), n=c.n, matrix=True)
+        outs.append((idx, d2, m.cpu().numpy().view(np.uint64)))
+    assert torch.equal(q.cpu(), torch.from_numpy(np.array(c.q))) and torch.equal(r.cpu(), torch.from_numpy(np.array(c.r)))
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+    check(outs[1], c.name, "second call")
 
 
 def test_without_the_matrix(dist_engines):

@@ -2,7 +2,17 @@
 join), 4, 5, 64 and 65; n = 257 (a row crosses a partial stride, several strips, odd rows whose 16-byte pairs begin a
 column early); n = 600 (two column tiles, 38 strips, the fold of their partials); the tie matrices; calls of 5
 different matrices of which one is invalid -- a NaN, a negative entry, an asymmetric pair, a non-zero diagonal -- whose
-status is set and record zeroed while the others are exact; the same matrix 3 times; two calls on copies; every VK_EINVAL."""
+status is set and record zeroed while the others are exact; the same matrix 3 times; two calls on copies; every VK_EINVAL.
+
+The second column tile and the odd rows: n = 511, 512 and 513 at an even base (513 is the first size whose odd rows reach
+tile 1: its lane 0 holds columns 511 and 512, takes R[511] from the slot in front of the tile's own, and column 1023 would
+be the next tile's); two trees of n = 513 and 601 in one call (the second at an odd multiple of 8 bytes, the parity of its
+rows alternating the other way); an even n at an odd base (every row odd: at n = 512 column 511 is met in the extra tile
+alone; also 64, 65 and 600, one tree and two).  Ties across workgroups: all ones at 513 and 600 leaves (every step a tie
+of every pair, through the workgroups' minima, the partials and the join's strided fold), and
+tree_cases.exact_cherries of 600 leaves with equal cherries in different tiles and strips, the winner once in tile 1 and
+once in tile 0.  In each of these runs later joins retire all 16 rows of a strip (a search workgroup with no row
+listed) and leave blocks wholly below the diagonal (skipped): both paths are entered without a test of their own."""
 import ctypes as C
 import functools
 
@@ -28,9 +38,16 @@ def eng():
 def want(kind, n, seed):
     """(D, the rule's (status, nodes, lengths)): computed once and shared."""
     D = {"additive": lambda: TC.additive(n, seed)[0], "noisy": lambda: TC.noisy(n, seed), "arbitrary": lambda: TC.arbitrary(n, seed),
-         "ones": lambda: TC.ones(n), "three_identical": lambda: TC.three_identical(n, seed)}[kind]()
+         "ones": lambda: TC.ones(n), "three_identical": lambda: TC.three_identical(n, seed),
+         "cherries": lambda: TC.exact_cherries(n, CHERRIES[seed], seed)}[kind]()
     D.setflags(write=False)
     return D, R.nj_np(D)
+
+
+# exact_cherries' pairs by seed: columns 40 | 520, 590 lie in tiles 0 | 1; rows 3, 4 | 17 | 530 in strips 0 | 1 | 33
+CHERRIES = {1: ((3, 520), (17, 40), (530, 590)),    # the winner in tile 1, a tile-0 pair of a later strip beaten
+            2: ((3, 40), (17, 520), (530, 590)),    # the mirror: the winner in tile 0
+            3: ((3, 520), (4, 40), (530, 590))}     # winner and runner-up in one strip, tiles 1 and 0
 
 
 def same(got, i, ref):
@@ -74,6 +91,61 @@ def test_ties_go_to_the_smaller_i_then_the_smaller_j(eng):
     same(eng.nj(D), 0, ref)
     D, ref = want("three_identical", 7, 5)
     same(eng.nj(D), 0, ref)
+
+
+def at_odd_base(eng, mats):
+    """The matrices on the device in one block that begins at an odd multiple of 8 bytes."""
+    import torch
+    t, n = len(mats), len(mats[0])
+    flat = torch.zeros(1 + t * n * n + 1, dtype=torch.float64, device=eng.device)
+    dd = flat[1:1 + t * n * n].view(t, n, n)
+    dd.copy_(torch.from_numpy(np.stack(mats)))
+    assert dd.data_ptr() % 16 == 8 and dd.is_contiguous()
+    return dd
+
+
+@pytest.mark.parametrize("n", [511, 512, 513])
+def test_rows_around_the_second_column_tile(eng, n):
+    D, ref = want("noisy", n, 5)
+    same(eng.nj(D), 0, ref)
+
+
+@pytest.mark.parametrize("n", [513, 601])
+@pytest.mark.parametrize("kind", ["noisy", "arbitrary"])
+def test_two_trees_of_an_odd_n_past_one_tile(eng, kind, n):
+    """The second tree lies at an odd base: the rows whose pairs begin a column early are the even ones there."""
+    (D, ref), (D2, ref2) = want(kind, n, 5), want(kind, n, 4)
+    got = eng.nj(np.stack([D, D2]))
+    same(got, 0, ref)
+    same(got, 1, ref2)
+
+
+@pytest.mark.parametrize("n", [64, 65, 512, 600])
+def test_a_matrix_at_an_odd_multiple_of_8_bytes(eng, n):
+    """An even n there makes every row odd; one tree, then two."""
+    (D, ref), (D2, ref2) = want("noisy", n, 5), want("noisy", n, 4)
+    same(eng.nj_device(at_odd_base(eng, [D])), 0, ref)
+    got = eng.nj_device(at_odd_base(eng, [D, D2]))
+    same(got, 0, ref)
+    same(got, 1, ref2)
+
+
+@pytest.mark.parametrize("n", [513, 600])
+def test_all_ones_tie_across_every_workgroup(eng, n):
+    D, ref = want("ones", n, 0)
+    assert ref[1][:4].tolist() == [0, 1, 0, 2]
+    same(eng.nj(D), 0, ref)
+
+
+@pytest.mark.parametrize("seed", sorted(CHERRIES))
+def test_equal_cherries_in_different_tiles_and_strips(eng, seed):
+    D, ref = want("cherries", 600, seed)
+    pairs = sorted(CHERRIES[seed])
+    assert ref[0] == 0 and ref[1][:6].reshape(3, 2).tolist() == [list(p) for p in pairs]   # the smaller i, then the smaller j
+    assert ref[2][:6].tolist() == [2.0, 4.0] * 3 and np.array_equal(ref[2], np.round(ref[2]))   # integers: the ties are real
+    same(eng.nj(D), 0, ref)
+    if seed == 1:   # every row odd as well
+        same(eng.nj_device(at_odd_base(eng, [D])), 0, ref)
 
 
 @pytest.mark.parametrize("kind", ["nan", "negative", "asymmetric", "diagonal", "inf", "too_large"])

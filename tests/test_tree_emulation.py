@@ -1,8 +1,11 @@
 """The lane-local device code of `tree`, run on the host (tests/emul/tree_emul.cpp compiles the product's csrc/vk_tree.h and
 csrc/vk_sketch.h with -ffp-contract=off) against tests/tree_ref.py, bit for bit: additive, noisy and arbitrary matrices of
 3 to 257 leaves, each laid at an even and at an odd multiple of 8 bytes (the two places a row's 16-byte pairs can fall),
-the tie matrices, every invalid matrix; and the per-block walk of the pairs kernel on every pair of
-tests/sketch_cases.seam_pairs.  The program is stand-alone (its own main): built once plainly and once with the address
+the tie matrices, every invalid matrix; 512 and 513 leaves, where an odd row's pairs reach the second column tile (its
+lane 0 holds columns 511 and 512 and takes its R from the slot before the tile's own; at 512 leaves laid odd EVERY row is
+odd and column 511 is met in the extra tile alone), as noise and as all ones (every step a tie across the tiles and
+strips); 600 leaves with equal cherries in different tiles and strips (tree_cases.exact_cherries); and the per-block
+walk of the pairs kernel on every pair of tests/sketch_cases.seam_pairs.  The program is stand-alone (its own main): built once plainly and once with the address
 and undefined-behaviour sanitizers, run as a program, never loaded into python.  Its header says what it does not cover
 (the kernels around the lane-local code: the GPU tests)."""
 import functools
@@ -24,6 +27,7 @@ CSRC = os.path.join(os.path.dirname(HERE), "varkoder_amd", "csrc")
 SRC = os.path.join(HERE, "emul", "tree_emul.cpp")
 INCLUDES = ["-I", os.path.join(HERE, "emul", "stub"), "-I", CSRC]
 PAIR_S = 64
+CHERRIES_600 = ((3, 520), (17, 40), (530, 590))   # the winner in column tile 1, the others in tile 0 and in strip 33
 
 
 @pytest.fixture(scope="module")
@@ -44,6 +48,8 @@ def expected():
     mats += [("arbitrary_%d" % n, TC.arbitrary(n, 200 + n)) for n in (7, 33)]
     mats += [("ones_%d" % n, TC.ones(n)) for n in (4, 9)] + [("three_identical", TC.three_identical())]
     mats += [("invalid_" + kind, TC.invalid(kind)) for kind in TC.INVALID]
+    mats += [("noisy_%d" % n, TC.noisy(n, 100 + n)) for n in (512, 513)] + [("ones_513", TC.ones(513))]
+    mats += [("exact_cherries_600", TC.exact_cherries(600, CHERRIES_600, 7))]
     runs = [(name, D, odd) for name, D in mats for odd in (0, 1)]
     want = {name: R.nj_np(D) for name, D in mats}
     for name, D in mats:
@@ -51,6 +57,9 @@ def expected():
             st, nodes, lengths = R.nj_loop(D)
             assert st == want[name][0] and nodes == want[name][1].tolist(), name   # the two statements agree
             assert np.array(lengths).tobytes() == want[name][2].tobytes(), name
+    st, nodes, lengths = want["exact_cherries_600"]
+    assert st == 0 and tuple(nodes[:2].tolist()) == min(CHERRIES_600)         # of equal Q the smaller i, then the smaller j
+    assert np.array_equal(lengths, np.round(lengths)) and lengths[:2].tolist() == [2.0, 4.0]   # integers throughout: real ties
     pairs = SC.seam_pairs(PAIR_S)
     return runs, want, pairs, [R.pair_blocks_loop(a, b, PAIR_S) for _, a, b in pairs]
 

@@ -1,5 +1,11 @@
 """The matrices of the `tree` tests: additive trees (whose topology and edge lengths neighbour joining must return), noisy
-and arbitrary symmetric matrices (where only the rule decides), the tie matrices, and the invalid ones."""
+and arbitrary symmetric matrices (where only the rule decides), the tie matrices, and the invalid ones.
+
+The tie matrices: `ones` (every pair ties at every step: at 513 and 600 leaves across every tile, strip and workgroup of
+the search), `three_identical`, and `exact_cherries`: an additive tree of even integer branch lengths, so that every R,
+Q, Du and length of the run is an integer that a double holds exactly and equal values are equal bit for bit, in which
+chosen pairs of slots -- in different column tiles and row strips of the search -- are cherries of one and the same
+smallest Q: the smaller (i, j) must win whichever workgroup found it."""
 import random
 
 import numpy as np
@@ -89,6 +95,46 @@ def arbitrary(n, seed):
 
 def ones(n):
     return np.ones((n, n)) - np.eye(n)
+
+
+def exact_cherries(n, pairs, seed):
+    """Slots a < b of every one of `pairs` are a cherry with leaf lengths 2 and 4 whose parent hangs by one long edge from
+    a hub; the other leaves form a random tree of edge lengths 2 .. 8 around the hub.  The cherries are alike (the same
+    lengths, the same distances to every other leaf and to each other's leaves): their Q is the same integer, and the
+    long edge makes it the smallest of the matrix.  Asserted here for step 0, in NumPy."""
+    pairs = [tuple(p) for p in pairs]
+    special = [s for p in pairs for s in p]
+    assert all(0 <= a < b < n for a, b in pairs) and len(set(special)) == len(special) and n - len(special) >= 3
+    rng = random.Random(seed)
+    rest = n - len(special)                      # leaves 0 .. rest - 1 of the random tree; leaf `rest` becomes the hub
+    length = lambda: 2.0 * rng.randint(1, 4)     # noqa: E731
+    edges = [(0, rest + 1, length()), (1, rest + 1, length()), (2, rest + 1, length())]
+    inner = rest + 2
+    for leaf in range(3, rest + 1):
+        u, v, w = edges.pop(rng.randrange(len(edges)))
+        edges += [(u, inner, w), (inner, v, length()), (leaf, inner, length())]
+        inner += 1
+    hub = rest
+    depth = tree_distances(rest + 1, edges)[hub].max()
+    far = 2.0 * (int(depth) // 2 + 1)            # the long edge: past every leaf's distance from the hub
+    # relabel: the tree's leaves keep their order in the slots the pairs leave free; nodes from n on are inner
+    free = [s for s in range(n) if s not in set(special)]
+    name = {leaf: free[leaf] for leaf in range(rest)}
+    name.update({node: n + node for node in range(rest, inner)})
+    edges = [(name[u], name[v], w) for u, v, w in edges]
+    top = n + inner
+    for a, b in pairs:
+        edges += [(a, top, 2.0), (b, top, 4.0), (top, name[hub], far)]
+        top += 1
+    D = tree_distances(n, edges)
+    assert np.array_equal(D, D.T) and np.array_equal(D, 2.0 * np.round(D / 2.0)) and D.max() < 2.0 ** 20   # even integers
+    R = D.sum(axis=1)                            # (integers far below 2^53: exact in any order)
+    Q = (float(n - 2) * D - R[:, None]) - R[None, :]
+    Q[np.tril_indices(n)] = np.inf
+    least = Q.min()
+    assert all(Q[a, b].tobytes() == least.tobytes() for a, b in pairs), "the cherries do not share the smallest Q"
+    assert sorted(zip(*(x.tolist() for x in np.nonzero(Q == least)))) == sorted(pairs), "another pair ties with the cherries"
+    return D
 
 
 def three_identical(n=7, seed=5):
